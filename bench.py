@@ -11,11 +11,22 @@ gradient all-reduce over RCCL (N > 1) -> fused Adam-amsgrad + weight-operand ref
 BASELINE.json configs[1]: plants_128 (z = 64, 16 x 3 x 128 x 128 clips, per-GPU batch 20, bf16 matrix-core inputs).
 Rank 0 prints ONE JSON line; `value` is the whole-job frames/s (weak scaling: per-GPU batch fixed).
 
-Extra objects in the line:
+A plain run sets up, warms up, times the --steps steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step = wall-clock milliseconds of one timed step).  Everything that takes runs of its own is behind --full:
+
   roofline     -- the flow's dominant contraction (NICE 1x1 conv, a [B*64, 2048] x [2048, 2048] implicit GEMM) timed with
-                  HIP events on its own launches; algorithmic FLOPs / launch over the dense bf16 MFMA peak.
+                  HIP events on its own launches; algorithmic FLOPs / launch over the dense bf16 MFMA peak.  Per configuration:
+                  one extra, untimed step with HIP events around every launch of the dominant kernel families (in situ).
+  secondary    -- c4, c5, c3 and the f32 lines of c2 / c4 / c5, each timed in a child process (--no-secondary skips them).
   cpu_baseline -- the CPU oracle (oracle/, plain PyTorch fp32 restatement pinned to the reference's goldens) doing
-                  the same step on a bounded sample of the same workload, on this box's host cores.
+                  the same step on a bounded sample of the same workload, on the host cores (--no-cpu-baseline skips it).
+  hipgraph     -- c5: the captured-graph and two-batches-in-flight variants of the sampling loop (--quick skips them).
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32, or float64 where the step computed
+float64), right behind the timed loop and before anything --full adds: the tensors the timed call returns and, for the train
+steps, the flow parameters it updated.  Arrays above SAMPLE_ELEMS elements are reduced to a fixed, seeded sample of their
+flattened elements; the whole dump stays under DUMP_LIMIT_BYTES.  Inputs and initial weights are seeded, so two builds run
+with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -51,6 +62,52 @@ def synthetic_batch(B, T, size, seed, device):
     poke = [torch.randn(B, 2, size, size, generator=g) * mask, torch.zeros(B, 5, 2, dtype=torch.int64)]
     batch = {"images": images, "flow": flow, "poke": poke, "sample_ids": torch.zeros(B, T, dtype=torch.int64)}
     return {k: ([p.to(device) for p in v] if isinstance(v, list) else v.to(device)) for k, v in batch.items()}
+
+
+DUMP_LIMIT_BYTES = 64 << 20         # --dump-outputs: the whole dump
+SAMPLE_ELEMS = 1 << 21              # --dump-outputs: larger arrays are written as this many seeded samples of their elements
+SAMPLE_SEED = 1234
+
+
+def named_tensors(obj, name):
+    """The tensors of a step's result (a tensor, or lists / tuples / dicts of them) as {name: tensor}; other values are dropped."""
+    if isinstance(obj, torch.Tensor):
+        return {name: obj}
+    if isinstance(obj, (list, tuple)):
+        out = {}
+        for i, v in enumerate(obj):
+            out.update(named_tensors(v, f"{name}_{i}"))
+        return out
+    if isinstance(obj, dict):
+        out = {}
+        for k, v in obj.items():
+            out.update(named_tensors(v, f"{name}_{k}".replace("/", "_")))
+        return out
+    return {}
+
+
+def dump_outputs(dirname, arrays):
+    """Write {name: tensor} as dirname/<name>.npy.  float64 stays float64, every other dtype becomes float32; an array of more than
+    SAMPLE_ELEMS elements (fewer when many arrays share the DUMP_LIMIT_BYTES budget) becomes a fixed, seeded sample of its flattened
+    elements (sorted indices, the same for every run and build), written beside it as <name>_index.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    n_files = sum(2 if t.numel() > SAMPLE_ELEMS else 1 for t in arrays.values())
+    cap = max(1, min(SAMPLE_ELEMS, DUMP_LIMIT_BYTES // (8 * max(1, n_files))))
+    total = 0
+    for name, t in arrays.items():
+        flat = t.detach()
+        wide = flat.dtype == torch.float64
+        if flat.numel() > cap:
+            g = torch.Generator().manual_seed(SAMPLE_SEED)
+            idx = torch.randint(0, flat.numel(), (cap,), generator=g).sort().values
+            flat = flat.reshape(-1)[idx.to(flat.device)]
+            np.save(os.path.join(dirname, f"{name}_index.npy"), idx.numpy().astype(np.float64))
+            total += cap * 8
+        a = flat.to(torch.float64 if wide else torch.float32).cpu().numpy()
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+        total += a.nbytes
+    assert total <= DUMP_LIMIT_BYTES, total
 
 
 def build_model(cfg, dtype, device, seed=0):
@@ -317,8 +374,8 @@ def secondary_subprocess(config, steps, warmup, timeout_s=600, extra=()):
     script in a child process -- same timing contract, fresh HIP context -- and return the fields of its JSON line that matter beside
     the headline (incl. the configuration's OWN roofline objects)."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--config", config, "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline",
-           "--no-secondary"] + list(extra)
+    cmd = [sys.executable, os.path.abspath(__file__), "--config", config, "--steps", str(steps), "--warmup", str(warmup), "--full",
+           "--no-cpu-baseline", "--no-secondary"] + list(extra)
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
@@ -386,7 +443,7 @@ def secondary(args, cfg, rank, world, device):
                                                             "d_t": d_t, "d_s": d_s, "data": {"max_frames": T - 1}}, vgg_loss=vgg)
         eps = torch.randn(B, z, 8, 8, generator=torch.Generator().manual_seed(7 + rank)).to(device)
         rng = np.random.RandomState(3)
-        step = lambda i: gan.step(batch["images"], eps, *gan.draw(batch["images"], rng))["loss"]
+        step = lambda i: gan.step(batch["images"], eps, *gan.draw(batch["images"], rng))      # the log dict; its "loss" is reported
         metric, frames = "video-frames/sec (first-stage adversarial train step: L1 + KL + VGG + d_t hinge/GP + d_s + generator terms)", world * B * T
         workload = (f"first_stage {T}x3x{size}x{size} clips, z={z}, generator fwd+bwd, 3-D ResNet-18 discriminator on {d_t['max_frames']} frames "
                     f"(4 forward + tangent pass + backward), PatchGAN on {d_s['n_examples']} frames, VGG-19 perceptual loss on {B * (T - 1)} frame pairs, three Adam steps; per-GPU batch {B}")
@@ -400,7 +457,7 @@ def secondary(args, cfg, rank, world, device):
         trainer = FirstStageTrainer(model)
         eps = torch.randn(B, z, 8, 8, generator=torch.Generator().manual_seed(7 + rank)).to(device)
         trainer.enable_data_parallel()             # N > 1: flat-buffer all-reduce of the gradients, mean folded into the Adam update
-        step = lambda i: trainer.step(batch["images"], eps)[0]
+        step = lambda i: trainer.step(batch["images"], eps)          # (loss, reconstruction); the loss is reported
         metric, frames = "video-frames/sec (first-stage VAE train step, L1 + KL)", world * B * T
         workload = f"first_stage {T}x3x{size}x{size} clips, z={z}, encoder + ConvGRU + SPADE decoder fwd+bwd, per-GPU batch {B}"
     else:
@@ -426,12 +483,15 @@ def secondary(args, cfg, rank, world, device):
         handoff_timeouts = list(model.flow.engine.handoff_timeouts())
         if any(handoff_timeouts):
             raise SystemExit(f"in-launch hand-off time-outs {handoff_timeouts}: the timed steps are invalid")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, named_tensors(out, "out"))
+    loss = out[0] if args.config == "c4" else out["loss"] if args.config == "c4gan" else None
     # one extra step on EVERY rank (the data-parallel hook of c4 holds a collective) with the per-family event timing on -- taken right
     # behind the timed eager loop, BEFORE the hipGraph / two-batches-in-flight variants of c5 (round 5 took it after them and its
     # single-stream families summed to more than the step: the variants leave other streams and graph state behind)
-    fams = config_rooflines(lambda: step(args.warmup + args.steps), args.dtype) if args.config != "fvd" else []
+    fams = config_rooflines(lambda: step(args.warmup + args.steps), args.dtype) if args.full and args.config != "fvd" else []
     graph = None
-    if args.config == "c5" and not args.quick:
+    if args.config == "c5" and args.full and not args.quick:
         def timed_again():
             for i in range(3):
                 step(i)
@@ -493,7 +553,7 @@ def secondary(args, cfg, rank, world, device):
             line["step_mfma_frac_executed"] = round(done / (ms * 1e-3) / peak, 4)
             line["kernel_time_share"] = {"timed_families_ms": round(sum(f["total_us_in_step"] for f in fams) / 1e3, 2), "step_ms": round(ms, 2)}
         if args.config in ("c4", "c4gan"):
-            line["loss"] = round(float(out.item()), 4)
+            line["loss"] = round(float(loss.item()), 4)
         if args.config == "fvd":
             peak = MFMA_BF16_PEAK_TFLOPS if args.dtype == "bf16" else MFMA_F32_PEAK_TFLOPS
             line["algorithmic_tflop_per_step_per_gpu"] = round(gflop / 1e3, 3)
@@ -539,12 +599,16 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch override")
     ap.add_argument("--fvd-dtype", default="f32", choices=["bf16", "f32"], help="arithmetic of --config fvd (the reference's I3D runs fp32)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: rooflines, the secondary configurations, the CPU baseline, c5's hipGraph variants")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, seeded samples of large arrays)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-clips", type=int, default=2, help="clips per CPU-baseline step (the per-step Adam / weight stream is amortised over them)")
     ap.add_argument("--cpu-timeout", type=int, default=600)
-    ap.add_argument("--no-secondary", action="store_true", help="skip the c4 / c5 lines attached to the default c2 line")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the c4 / c5 / c3 / f32 lines attached to the c2 line")
     ap.add_argument("--secondary-steps", type=int, default=10)
-    ap.add_argument("--quick", action="store_true", help="c5: the eager latency only (no hipGraph / two-batches-in-flight variants)")
+    ap.add_argument("--quick", action="store_true", help="c5 --full: the eager latency only (no hipGraph / two-batches-in-flight variants)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_baseline_only:
@@ -552,10 +616,12 @@ def main():
         return
 
     relaunch = self_launch_command(sys.argv[1:], args.gpus, os.environ)
-    if relaunch is not None:                 # plain `python bench.py --gpus N`: become the N-rank job (same stdout, same exit code)
+    if relaunch is not None:                 # plain `python bench.py --gpus N`: run the N-rank job as a child (same stdout, same exit code)
+        import subprocess
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")        # dmabuf IPC: RCCL across processes needs it on this driver
         sys.stdout.flush()
-        os.execv(sys.executable, relaunch)
+        rc = subprocess.run(relaunch).returncode
+        sys.exit(rc if rc >= 0 else 128 - rc)
 
     _lib.require_gpu()
     rank, world, local = D.init_from_env()
@@ -599,6 +665,12 @@ def main():
     handoff_timeouts = list(model.flow.engine.handoff_timeouts())      # (row-split unit, fused conv3 + coupling) launches that gave up: must be 0, 0
     if any(handoff_timeouts):
         raise SystemExit(f"in-launch hand-off time-outs {handoff_timeouts}: the timed steps are invalid")
+    if args.dump_outputs and rank == 0:
+        # train_step returns the loss; the rest of what the step computed is the flow's parameters after its optimizer update
+        outs = {"loss": loss}
+        outs.update({f"loss_{k}": v for k, v in model.logged.items() if isinstance(v, torch.Tensor)})
+        outs["flow_params"] = model.flow.flat_params
+        dump_outputs(args.dump_outputs, outs)
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     median_ms = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
     loss_val = float(loss.item())
@@ -607,9 +679,9 @@ def main():
     value = frames / (elapsed / args.steps)
 
     insitu = insitu_rooflines(lambda: trainer.train_step(batch, args.warmup + args.steps, next_batch=batch), B, z, args.dtype) \
-        if args.dtype == "bf16" else None
+        if args.full and args.dtype == "bf16" else None
     if rank == 0:
-        roof = kernel_roofline(B, args.dtype)
+        roof = kernel_roofline(B, args.dtype) if args.full else None
         if insitu:                       # the dominant kernel as it runs INSIDE the step; the isolated figure is kept beside it
             iso = roof
             roof = dict(insitu[0]); roof["traffic"] = iso["traffic"]; roof["traffic_unit"] = iso["traffic_unit"]; roof["traffic_source"] = iso["traffic_source"]
@@ -634,7 +706,7 @@ def main():
         }
         if insitu:
             line["roofline_other_kernels"] = insitu[1:]
-        if not args.no_secondary and world == 1 and args.config == "c2":
+        if args.full and not args.no_secondary and world == 1 and args.config == "c2":
             # BASELINE configs[3] / configs[4], timed by the same driver invocation (their own lines: --config c4 / c5)
             del model, trainer, batch
             torch.cuda.empty_cache()
@@ -647,7 +719,7 @@ def main():
                 line["secondary"]["c2_f32"] = secondary_subprocess("c2", args.secondary_steps, 3, extra=("--dtype", "f32"))
                 line["secondary"]["c4_f32"] = secondary_subprocess("c4", 5, 2, extra=("--dtype", "f32"))
                 line["secondary"]["c5_f32"] = secondary_subprocess("c5", 5, 2, extra=("--dtype", "f32", "--quick"))
-        if not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (the other ranks would idle at the barrier)
+        if args.full and not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (the other ranks would idle at the barrier)
             line["cpu_baseline"] = cpu_baseline_subprocess(args.config, args.cpu_clips, args.cpu_timeout)
         # LAST key: every configuration's ms per step in one short object (a 2 KB tail of the line still shows all of them)
         summ = {args.config if args.dtype == "bf16" else args.config + "_f32": round(ms, 3)}

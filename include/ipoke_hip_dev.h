@@ -21,6 +21,12 @@ int ipoke_set_dispatch_override(const char* name, int value);
 /* Test hook: the kernel family the calling thread's last ipoke_conv_forward was dispatched to */
 enum { IPOKE_KERNEL_NONE = 0, IPOKE_KERNEL_IGEMM = 1, IPOKE_KERNEL_S8 = 2, IPOKE_KERNEL_HALO = 3, IPOKE_KERNEL_HALO16 = 4, IPOKE_KERNEL_C64 = 5, IPOKE_KERNEL_K8 = 6 };
 int ipoke_last_conv_kernel(void);
+/* Test hook: the weight-gradient kernel the calling thread's last ipoke_conv_wgrad / ipoke_conv_wgrad_batched was dispatched to
+ * (TN: igemm_tn_kernel, the generic form -- f32 and unaligned operands; TN_GLDS / TN_NARROW: the LDS-DMA kernel, 128 x 128 / 64 x 256
+ * tiles; LAT8: wgrad3x3_lat8 on the 8x8 latent; HALO: wgrad3x3_halo on large maps) */
+enum { IPOKE_WGRAD_KERNEL_NONE = 0, IPOKE_WGRAD_KERNEL_TN = 1, IPOKE_WGRAD_KERNEL_TN_GLDS = 2, IPOKE_WGRAD_KERNEL_TN_NARROW = 3,
+       IPOKE_WGRAD_KERNEL_LAT8 = 4, IPOKE_WGRAD_KERNEL_HALO = 5 };
+int ipoke_last_wgrad_kernel(void);
 
 /* developer probe (IPOKE_SIDE_DELAY_US): one wave spinning for about `us` microseconds on `stream` */
 int ipoke_spin_delay(int us, void* stream);

@@ -140,6 +140,7 @@ SIGNATURES = {
     "ipoke_conv_forward_repeat": (c_int, [POINTER(ConvDesc), c_int, c_int, _P]),
     "ipoke_set_dispatch_override": (c_int, [c_char_p, c_int]),
     "ipoke_last_conv_kernel": (c_int, []),
+    "ipoke_last_wgrad_kernel": (c_int, []),
     "ipoke_gru_set_fused": (c_int, [c_int]),
     "ipoke_gru_workspace_bytes": (c_int64, [POINTER(GruDesc), c_int]),
     "ipoke_gru_unroll_forward": (c_int, [POINTER(GruDesc), _P, c_int, _P, c_int, POINTER(c_void_p), _P, _P, c_int, c_int, _P]),
@@ -364,6 +365,7 @@ import contextlib
 
 
 KERNEL_NONE, KERNEL_IGEMM, KERNEL_S8, KERNEL_HALO, KERNEL_HALO16, KERNEL_C64, KERNEL_K8 = range(7)       # ipoke_last_conv_kernel
+WGRAD_NONE, WGRAD_TN, WGRAD_TN_GLDS, WGRAD_TN_NARROW, WGRAD_LAT8, WGRAD_HALO = range(6)                      # ipoke_last_wgrad_kernel
 
 
 @contextlib.contextmanager

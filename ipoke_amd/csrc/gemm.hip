@@ -4110,9 +4110,12 @@ static int launch_lat8(const TnParams& t, hipStream_t s, int nbatch) {
   return IPOKE_OK;
 }
 
+static thread_local int g_last_wgrad_kernel = IPOKE_WGRAD_KERNEL_NONE;     // (see ipoke_last_wgrad_kernel)
+
 template <typename T>
 static int launch_tn(TnParams& p, hipStream_t s, int nbatch = 1) {
   constexpr int RM = 128 / (int)sizeof(T);
+  g_last_wgrad_kernel = IPOKE_WGRAD_KERNEL_TN;
   p.tiles_n = ceil_div(p.Nout, 128);
   p.tiles_k = ceil_div(p.Ktot, 128);
   const int nmb = ceil_div(p.g.M, RM);
@@ -4124,9 +4127,9 @@ static int launch_tn(TnParams& p, hipStream_t s, int nbatch = 1) {
   p.mb_per_split = ceil_div(nmb, p.splitm);
   if constexpr (sizeof(T) == 2) {
     // batched 3x3 problems on the 8x8 latent (conv1 / conv3 of the coupling nets): the stationary-input kernel
-    if (lat8_applicable(p, nbatch)) return launch_lat8(p, s, nbatch);
+    if (lat8_applicable(p, nbatch)) { g_last_wgrad_kernel = IPOKE_WGRAD_KERNEL_LAT8; return launch_lat8(p, s, nbatch); }
     // 3x3 / 3x3x3 stride-1 problems on large maps (first-stage training): the halo-staged kernel
-    if (nbatch == 1 && halo_wgrad_applicable(p)) return launch_halo_wgrad(p, s);
+    if (nbatch == 1 && halo_wgrad_applicable(p)) { g_last_wgrad_kernel = IPOKE_WGRAD_KERNEL_HALO; return launch_halo_wgrad(p, s); }
   }
   const size_t lds = 4 * 128 * kPitch + 256 * sizeof(int);
   // LDS-DMA + transposed-read kernel: bf16, dense operands with 16-byte aligned rows
@@ -4146,6 +4149,7 @@ static int launch_tn(TnParams& p, hipStream_t s, int nbatch = 1) {
     static const int narrow_on = getenv("IPOKE_TN_NARROW") ? atoi(getenv("IPOKE_TN_NARROW")) : 1;      // developer A/B
     const bool narrow = narrow_on && NST == 2 && p.batch != nullptr && p.Nout <= 64 && p.Ktot >= 512 && p.max_wgs <= 0;
     if (narrow) p.tiles_k = ceil_div(p.Ktot, 256);
+    g_last_wgrad_kernel = narrow ? IPOKE_WGRAD_KERNEL_TN_NARROW : IPOKE_WGRAD_KERNEL_TN_GLDS;
     const int nst_n = narrow_on == 3 ? 3 : 2;                  // (developer A/B: IPOKE_TN_NARROW=3 = three ring slots, 144 KB)
     const size_t lds2 = narrow ? (size_t)nst_n * 3 * 64 * 256 + 256 * sizeof(int) : (size_t)NST * 2 * 64 * 256 + 256 * sizeof(int);
     const bool adam = p.ad_p != nullptr;
@@ -4220,6 +4224,7 @@ extern "C" int ipoke_set_dispatch_override(const char* name, int value) {
 }
 
 extern "C" int ipoke_last_conv_kernel(void) { return g_last_kernel; }
+extern "C" int ipoke_last_wgrad_kernel(void) { return g_last_wgrad_kernel; }
 
 namespace ipoke {
 // descriptor -> kernel parameters (validation shared by ipoke_conv_forward and ipoke_conv3x3_coupling)

@@ -146,13 +146,14 @@ def test_first_stage_train_mode_step(golden, monkeypatch, variant, dtype):
     grad_report(m, g, dtype, f"c4-train-mode/{variant}")
 
 
-@pytest.mark.parametrize("dtype,copies", [("f32", 4), ("bf16", 4), ("bf16", 10)])
+@pytest.mark.parametrize("dtype,copies", [("f32", 4), ("bf16", 4), ("bf16", 10), ("bf16", 20)])
 def test_first_stage_train_mode_batch_of_copies(golden, dtype, copies):
-    """B = 4 / 10, T = 16: clips are independent, so copies of the golden clip reproduce the golden reconstruction in every slot, and the
-    mean-loss gradients equal the single clip's (checked against the reference's checksums of every tensor).  B = 10 is the size class
-    of ``bench.py --config c4``: the decoder sees 150 images per launch -- 9 600 patches of 16 x 16 pixels at the
-    128 x 128 layers, conv3x3_c64 by the default rule with ~38 patches per persistent workgroup (forward, data gradient, the four
-    scattered sub-pixel phases), conv3x3_halo16 on the 64 x 64 / 128-channel layers, ~512-workgroup split-M weight gradients."""
+    """B = 4 / 10 / 20, T = 16: clips are independent, so copies of the golden clip reproduce the golden reconstruction in every slot, and
+    the mean-loss gradients equal the single clip's (checked against the reference's checksums of every tensor).  B = 20 is the batch of
+    ``bench.py --config c4`` (configs.py): the decoder sees 300 images per launch.  B = 10 (150 images) is half of it: 9 600 patches of
+    16 x 16 pixels at the 128 x 128 layers, conv3x3_c64 by the default rule with ~38 patches per persistent workgroup (forward, data
+    gradient, the four scattered sub-pixel phases), conv3x3_halo16 on the 64 x 64 / 128-channel layers, ~512-workgroup split-M weight
+    gradients."""
     g = golden("g13_first_stage_train_mode_128")
     m = train_model(dtype)
     X, eps = clip(g, copies=copies)

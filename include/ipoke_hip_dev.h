@@ -15,8 +15,7 @@ extern "C" {
 /* n back-to-back native launches of the same convolution (kernel timing without host round trips) */
 int ipoke_conv_forward_repeat(const ipoke_conv_desc* d, int dtype, int n, void* stream);
 /* Test hook: kernel-dispatch switch `name` ("c64": conv3x3_c64, "halo16": conv3x3_halo16) <- value (0 off, 1 the measured default
- * rule, 2 wherever the kernel can run; < 0: back to the environment default IPOKE_C64 / IPOKE_HALO16).  The switches are read from the
- * environment once per process -- no getenv on the launch path. */
+ * rule, 2 wherever the kernel can run; < 0: back to the default rule 1). */
 int ipoke_set_dispatch_override(const char* name, int value);
 /* Test hook: the kernel family the calling thread's last ipoke_conv_forward was dispatched to */
 enum { IPOKE_KERNEL_NONE = 0, IPOKE_KERNEL_IGEMM = 1, IPOKE_KERNEL_S8 = 2, IPOKE_KERNEL_HALO = 3, IPOKE_KERNEL_HALO16 = 4, IPOKE_KERNEL_C64 = 5, IPOKE_KERNEL_K8 = 6 };

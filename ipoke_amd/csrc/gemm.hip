@@ -2554,24 +2554,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 
 // Dispatch switches of the two persistent / wide 3 x 3 kernels: 0 off, 1 (default) where measured faster, 2 wherever the kernel can run.
-// Read from the environment ONCE (IPOKE_C64 / IPOKE_HALO16, developer A/B); the parity tests move them at run time through
-// ipoke_set_dispatch_override (no getenv on the launch path, atomics because launches on distinct streams may come from distinct threads).
-static std::atomic<int> g_c64_mode{-1}, g_halo16_mode{-1};
-static int dispatch_mode(std::atomic<int>& slot, const char* env_name) {
-  int m = slot.load(std::memory_order_relaxed);
-  if (m < 0) {
-    const char* e = getenv(env_name);
-    m = e ? atoi(e) : 1;
-    if (m < 0 || m > 2) m = 1;
-    int expect = -1;
-    if (!slot.compare_exchange_strong(expect, m)) m = expect;      // somebody else (or the override hook) was first
-  }
-  return m;
-}
+// The parity tests move them at run time through ipoke_set_dispatch_override (atomics because launches on distinct streams may come
+// from distinct threads).
+static std::atomic<int> g_c64_mode{1}, g_halo16_mode{1};
 
 static bool c64_applicable(const NtParams& p) {
   // mode 1 (default): at >= 512 patches (two per CU)
-  const int mode = dispatch_mode(g_c64_mode, "IPOKE_C64");
+  const int mode = g_c64_mode.load(std::memory_order_relaxed);
   const GeomDev& g = p.g;
   if (!mode) return false;
   // window offsets a - ph (forward) / ph - a (data gradient) must lie within the one-pixel halo
@@ -2600,11 +2589,10 @@ static int launch_conv3x3_c64(NtParams& p, hipStream_t s) {
 }
 
 static bool halo16_applicable(const NtParams& p) {
-  const int mode = dispatch_mode(g_halo16_mode, "IPOKE_HALO16");
+  const int mode = g_halo16_mode.load(std::memory_order_relaxed);
   const GeomDev& g = p.g;
-  // the four-tap sub-pixel phase of a stride-2 ConvTranspose2d (2 x 2 window, no padding, scattered output rows; IPOKE_HALO16_PHASE=0: developer A/B)
-  static const bool phase_on = !(getenv("IPOKE_HALO16_PHASE") && atoi(getenv("IPOKE_HALO16_PHASE")) == 0);
-  const bool phase4 = phase_on && g.taps == 4 && g.khw == 4 && g.kw == 2 && g.ph == 0 && g.pw == 0 && !g.transposed && g.Di == 1 && g.Do == 1 && g.pd == 0 &&
+  // the four-tap sub-pixel phase of a stride-2 ConvTranspose2d (2 x 2 window, no padding, scattered output rows)
+  const bool phase4 = g.taps == 4 && g.khw == 4 && g.kw == 2 && g.ph == 0 && g.pw == 0 && !g.transposed && g.Di == 1 && g.Do == 1 && g.pd == 0 &&
                       g.sd == 1 && p.c_scatter && !p.dact;
   if (!mode || p.a_f32) return false;
   if (!phase4 && (p.c_scatter || !(g.taps == 9 || g.taps == 27) || g.khw != 9 || g.kw != 3)) return false;
@@ -2639,26 +2627,24 @@ static int launch_conv3x3_halo16(NtParams& p, hipStream_t s) {
 }
 
 static bool halo_applicable(const NtParams& p) {
-  static const int on = getenv("IPOKE_HALO") ? atoi(getenv("IPOKE_HALO")) : 1;         // developer A/B: IPOKE_HALO=0 turns the kernel off
   const GeomDev& g = p.g;
-  static const int on3 = getenv("IPOKE_HALO3D") ? atoi(getenv("IPOKE_HALO3D")) : 1;    // the 3 x 3 x 3 form alone
   const bool flat = g.taps == 9 && g.Di == 1 && g.Do == 1 && g.pd == 0;
-  const bool deep = on3 && g.taps == 27 && g.Di == g.Do && g.pd == 1 && (p.a_sd & 7) == 0;
+  const bool deep = g.taps == 27 && g.Di == g.Do && g.pd == 1 && (p.a_sd & 7) == 0;
   if (!(flat || deep) || p.c_scatter || kLdsHalo > device_max_lds()) return false;
-  if (deep) {     // measured (scripts/probe_halo3d.py, B = 20): 64 channels 16x64x64: 670 vs 997 us, 12x32x32: 126 vs 185 us; but 128
+  if (deep) {     // measured against the 27-tap implicit GEMM (B = 20): 64 channels 16x64x64: 670 vs 997 us, 12x32x32: 126 vs 185 us; but 128
                   // channels 8x32x32: 271 vs 230, 256 channels 4x16x16: 141 vs 101, 512 channels: 255 vs 177 -> 64 input channels only
     if (p.Kc > 64) return false;
-    return on && !p.a_f32 && g.khw == 9 && g.kw == 3 && g.Hi == g.Ho && g.Wi == g.Wo && g.Ho % 8 == 0 && g.Wo % 16 == 0 &&
+    return !p.a_f32 && g.khw == 9 && g.kw == 3 && g.Hi == g.Ho && g.Wi == g.Wo && g.Ho % 8 == 0 && g.Wo % 16 == 0 &&
            g.sd == 1 && g.sh == 1 && g.sw == 1 && g.ph == 1 && g.pw == 1 && p.Kc % 64 == 0 && p.Kc_real == p.Kc && (p.a_coff & 7) == 0 &&
            p.ldw >= p.Ktot && p.splitk == 1 && !p.c_acc && ((p.a_sn | p.a_sh | p.a_sw) & 7) == 0 &&
            (long)(g.M / g.S) * p.a_sn + (long)g.Di * p.a_sd + p.Kc < (1L << 31) && (long)p.Nout * p.ldw < (1L << 31) && g.M >= 4096;
   }
-  return on && !p.a_f32 && g.taps == 9 && g.khw == 9 && g.kw == 3 && g.Di == 1 && g.Do == 1 && g.Hi == g.Ho && g.Wi == g.Wo &&
+  return !p.a_f32 && g.taps == 9 && g.khw == 9 && g.kw == 3 && g.Di == 1 && g.Do == 1 && g.Hi == g.Ho && g.Wi == g.Wo &&
          g.Ho % 8 == 0 && g.Wo % 16 == 0 && g.sd == 1 && g.sh == 1 && g.sw == 1 && g.pd == 0 && g.ph == 1 && g.pw == 1 &&
          p.Kc % 64 == 0 && p.Kc_real == p.Kc && (p.a_coff & 7) == 0 && p.ldw >= p.Ktot && p.splitk == 1 && !p.c_acc &&
          ((p.a_sn | p.a_sh | p.a_sw) & 7) == 0 && (long)(g.M / g.S) * p.a_sn + (long)g.Hi * p.a_sh + p.Kc < (1L << 31) &&
          (long)p.Nout * p.ldw < (1L << 31) && g.M >= 4096 &&
-         // measured against the implicit-GEMM kernel (scripts/probe_halo.py, B = 32): 64 channels at 128 x 128: 139 vs 181 us,
+         // measured against the implicit-GEMM kernel (B = 32): 64 channels at 128 x 128: 139 vs 181 us,
          // 64 -> 3: 129 vs 168, 256 channels at 16 x 16: 18 vs 32 us, 512 at 16 x 16 (N = 300): 486 vs 682; but 128 channels at
          // 64 x 64: 91 vs 86 and 256 at 32 x 32: 68 vs 67 -- there the nine-tap re-fetch is hidden and the generic tile map wins
          (p.Kc <= 64 || g.Ho * g.Wo <= 256);
@@ -2814,9 +2800,8 @@ __global__ __launch_bounds__(256) void conv3x3_k8_kernel(const NtParams p) {
   }
 }
 static bool k8_applicable(const NtParams& p) {
-  static const int on = getenv("IPOKE_K8") ? atoi(getenv("IPOKE_K8")) : 1;      // developer A/B: 0 keeps the implicit GEMM
   const GeomDev& g = p.g;
-  return on && !p.a_f32 && !p.c_f32 && !p.c_acc && p.splitk == 1 && !p.dact && !p.bias && p.act == IPOKE_ACT_NONE && !p.row_scale && !p.c_scatter &&
+  return !p.a_f32 && !p.c_f32 && !p.c_acc && p.splitk == 1 && !p.dact && !p.bias && p.act == IPOKE_ACT_NONE && !p.row_scale && !p.c_scatter &&
          !p.w_kmajor && g.taps == 9 && g.khw == 9 && g.kw == 3 && g.Di == 1 && g.Do == 1 && g.sd == 1 && g.sh == 1 && g.sw == 1 && g.pd == 0 &&
          g.ph == 1 && g.pw == 1 && g.Hi == g.Ho && g.Wi == g.Wo && g.pow2 && (g.Wo & 15) == 0 && p.Kc == 8 && p.a_sc == 1 && (p.Nout & 15) == 0 &&
          p.Nout <= 64 && (p.a_coff & 7) == 0 && ((p.a_sn | p.a_sh | p.a_sw) & 7) == 0 && p.ldw >= 72 && (p.ldw & 7) == 0 &&
@@ -2832,15 +2817,14 @@ static int launch_conv3x3_k8(NtParams& p, hipStream_t s) {
 }
 
 static bool k64_applicable(const NtParams& p) {
-  static const int on = getenv("IPOKE_K64") ? atoi(getenv("IPOKE_K64")) : 1;      // developer A/B: 0 keeps the implicit GEMM
   const GeomDev& g = p.g;
-  return on && kLdsK64 <= device_max_lds() && !p.c_scatter && !p.a_f32 && !p.row_scale && g.taps == 9 && g.khw == 9 && g.kw == 3 && g.Di == 1 && g.Hi == 8 &&
+  return kLdsK64 <= device_max_lds() && !p.c_scatter && !p.a_f32 && !p.row_scale && g.taps == 9 && g.khw == 9 && g.kw == 3 && g.Di == 1 && g.Hi == 8 &&
          g.Wi == 8 && g.lDo == 0 && g.lHo == 3 && g.lWo == 3 && g.sd == 1 && g.sh == 1 && g.sw == 1 && g.pd == 0 && g.ph == 1 && g.pw == 1 &&
          p.Kc <= 64 && (p.Kc & 7) == 0 && p.Kc_real == p.Kc && p.Nout >= 256 && p.splitk == 1 && !p.c_acc && (p.a_coff & 7) == 0 &&
          p.ldw >= p.Ktot && ((p.a_sn | p.a_sh | p.a_sw) & 7) == 0 && (long)(g.M >> 6) * p.a_sn + 7 * p.a_sh + 7 * p.a_sw + p.Kc < (1L << 31) &&
          (long)p.Nout * p.ldw < (1L << 31) && 128 * (128 * 4 + 16) <= (int)kLdsK64 &&
          // one workgroup per CU (115 KB of LDS): a second round loses to the implicit GEMM (B = 40: 14.9 against 13.4 us; B = 20 / 32: 8.2 / 8.5
-         // against 9.9 / 11.0 isolated, scripts/r6/probe_k64.py)
+         // against 9.9 / 11.0 isolated)
          (long)ceil_div(g.M, 128) * ceil_div(p.Nout, 128) <= 256;
 }
 static int launch_conv3x3_k64(NtParams& p, hipStream_t s) {
@@ -2853,15 +2837,10 @@ static int launch_conv3x3_k64(NtParams& p, hipStream_t s) {
   return IPOKE_OK;
 }
 
-static int s8_samples_per_tile() {
-  static const int ts = getenv("IPOKE_S8") ? (atoi(getenv("IPOKE_S8")) ? 2 : 0) : 2;      // developer A/B: IPOKE_S8=0 turns the kernel off
-  return ts;
-}
+static constexpr int kS8SamplesPerTile = 2;      // 8x8 maps per 128-row tile of conv3x3_s8
 static bool s8_applicable(const NtParams& p) {
   const GeomDev& g = p.g;
-  static const int dgrad_on = getenv("IPOKE_S8_DGRAD") ? atoi(getenv("IPOKE_S8_DGRAD")) : 1;      // developer A/B: 0 sends the conv1 data gradient to the implicit GEMM
-  if (!dgrad_on && g.transposed) return false;
-  return s8_samples_per_tile() > 0 && kLdsS8 <= device_max_lds() && !p.c_scatter && !p.a_f32 && g.taps == 9 && g.khw == 9 && g.kw == 3 && g.Di == 1 && g.Hi == 8 && g.Wi == 8 &&
+  return kLdsS8 <= device_max_lds() && !p.c_scatter && !p.a_f32 && g.taps == 9 && g.khw == 9 && g.kw == 3 && g.Di == 1 && g.Hi == 8 && g.Wi == 8 &&
          g.lDo == 0 && g.lHo == 3 && g.lWo == 3 && g.sd == 1 && g.sh == 1 && g.sw == 1 && g.pd == 0 && g.ph == 1 && g.pw == 1 &&
          p.Kc % 64 == 0 && p.Kc_real == p.Kc && p.Kc >= 256 && p.Nout <= 64 && (p.a_coff & 7) == 0 && p.ldw >= p.Ktot &&
          ((p.a_sn | p.a_sh | p.a_sw) & 7) == 0 && (long)(g.M >> 6) * p.a_sn + 7 * p.a_sh + 7 * p.a_sw + p.Kc < (1L << 31) &&
@@ -2872,9 +2851,8 @@ static int launch_conv3x3_s8(NtParams& p, hipStream_t s) {
   p.tiles_m = ceil_div(p.g.M, BM); p.tiles_n = 1; p.xa = p.xb = 0;
   p.kb_per_split = ceil_div(p.Kc / 64, p.splitk);
   dim3 grid((unsigned)p.tiles_m, (unsigned)p.splitk);
-  static const int n32 = getenv("IPOKE_S8_N32") ? atoi(getenv("IPOKE_S8_N32")) : 1;      // developer A/B: 0 keeps the 64-column kernel for narrow outputs
-  { int rc = acc_scratch_fits(p, BM, n32 && p.Nout <= 32 ? 32 : 64, true); if (rc) return rc; }
-  if (n32 && p.Nout <= 32) {
+  { int rc = acc_scratch_fits(p, BM, p.Nout <= 32 ? 32 : 64, true); if (rc) return rc; }
+  if (p.Nout <= 32) {
     const size_t lds = 2 * BM * 128 + 256 + 12 * 32 * 128 + 512 * 16;
     auto kern = conv3x3_s8n32_kernel;
     IPK_SET_LDS_ONCE(kern, lds);
@@ -2892,9 +2870,8 @@ static int launch_conv3x3_s8(NtParams& p, hipStream_t s) {
 // Split count for the skinny 3x3 convolutions of the coupling nets (conv3 forward, conv1 data gradient) at M output rows
 // and Kc input channels: callers size their partial-sum slabs with it.  0: the kernel does not apply (caller's choice).
 extern "C" int ipoke_conv3x3_skinny_splitk(int M, int Kc, int dtype) {
-  const int ts = s8_samples_per_tile();
-  if (dtype != IPOKE_BF16 || ts <= 0 || Kc % 64 != 0 || Kc < 256 || M % 64 != 0) return 0;
-  return conv3x3_s8_splits(M, Kc, ts);
+  if (dtype != IPOKE_BF16 || Kc % 64 != 0 || Kc < 256 || M % 64 != 0) return 0;
+  return conv3x3_s8_splits(M, Kc, kS8SamplesPerTile);
 }
 
 static thread_local int g_last_kernel = IPOKE_KERNEL_NONE;     // (see ipoke_last_conv_kernel)
@@ -2911,8 +2888,7 @@ static int coupling_splits(int M, int Kc) {
   return ns;
 }
 extern "C" int ipoke_conv3x3_coupling_splitk(int M, int Kc, int dtype) {
-  static const int on = getenv("IPOKE_COUPLING_FUSE") ? atoi(getenv("IPOKE_COUPLING_FUSE")) : 1;
-  if (!on || dtype != IPOKE_BF16 || s8_samples_per_tile() <= 0 || Kc % 64 != 0 || Kc < 256 || M % 64 != 0 || M < 64) return 0;
+  if (dtype != IPOKE_BF16 || Kc % 64 != 0 || Kc < 256 || M % 64 != 0 || M < 64) return 0;
   return coupling_splits(M, Kc);
 }
 extern "C" int64_t ipoke_conv3x3_coupling_xchg_bytes(void) { return kCplHeader + 256L * 128 * 256; }     // tiles x splits <= 256 slots of 128 rows x 64 floats
@@ -2964,10 +2940,7 @@ extern "C" int ipoke_conv3x3_coupling(const ipoke_conv_desc* conv, const ipoke_a
   e.ext_ld = ep->ext_ld; e.ext_bf16 = 1;
   auto log2_or = [](int v) { int sh = 0; while ((1 << sh) < v) ++sh; return (1 << sh) == v ? sh : -1; };
   e.ld_sh = log2_or(a->ld); e.cp_sh = log2_or(a->Cp); e.ts_sh = log2_or(a->t_stride);
-  {
-    static const int prio = getenv("IPOKE_NT_PRIO") ? atoi(getenv("IPOKE_NT_PRIO")) : 2;
-    p.prio = prio;
-  }
+  p.prio = 2;
 #ifdef IPOKE_GEMM_STAMPS
   p.stamps = g_gemm_stamps;
   if (g_gemm_stamps) g_gemm_stamps += 16 * 4096;               // one slab of 4096 workgroups x 16 stamps per fused launch
@@ -2998,28 +2971,8 @@ static int dispatch_nt(NtParams& p, hipStream_t s) {
     if (halo16_applicable(p)) { g_last_kernel = IPOKE_KERNEL_HALO16; return launch_conv3x3_halo16(p, s); }
     if (halo_applicable(p)) { g_last_kernel = IPOKE_KERNEL_HALO; return launch_conv3x3_halo(p, s); }
   }
-  static const int forced = getenv("IPOKE_NT_TILE") ? atoi(getenv("IPOKE_NT_TILE")) : 0;     // developer override
-  switch (forced) {
-    case 1: return launch_nt<T, 4, 1, 1, 4>(p, s);
-    case 2: return launch_nt<T, 2, 2, 2, 4>(p, s);
-    case 3: return launch_nt<T, 2, 2, 4, 4>(p, s);
-    case 4: return launch_nt<T, 1, 4, 5, 2>(p, s);
-    case 5: return launch_nt<T, 2, 2, 5, 4>(p, s);
-    case 6: return launch_nt<T, 2, 2, 2, 2>(p, s);
-    default: break;
-  }
-  static const int glds_mode = getenv("IPOKE_NT_GLDS") ? atoi(getenv("IPOKE_NT_GLDS")) : 1;
-  if (glds_mode && !p.a_f32 && forced == 0) {
-    if (N <= 64) {
-      static const int skinny = getenv("IPOKE_NT_SKINNY") ? atoi(getenv("IPOKE_NT_SKINNY")) : 0;
-      if (skinny == 1 && M % 128 == 0) return launch_nt_glds<T, 4, 2, 2, 2, 4, 1>(p, s);   // 128 x 64, 8 waves: half the weight re-reads
-      if (skinny == 2 && M % 128 == 0) return launch_nt_glds<T, 4, 2, 2, 2, 3, 2>(p, s);
-      return launch_nt_glds<T, 4, 1, 1, 4, 4>(p, s);                     // 64 x 64, skinny N
-    }
-    if (glds_mode == 16) return launch_nt_glds<T, 1, 8, 5, 1, 3, 1>(p, s);         // developer A/B: 80 x 128, 8 waves of 80 x 16, 3 slots
-    if (glds_mode == 17) return launch_nt_glds<T, 1, 4, 5, 2, 2, 2, 2>(p, s);      // developer A/B: 2 K-halves x 4 waves of 80 x 32, 2 slots x 2
-    if (glds_mode == 18 && M % 80 == 0) return launch_nt_glds<T, 1, 4, 5, 2, 4, 1, 2>(p, s);      // developer A/B: the default 80 x 128 tile with 4 ring slots
-    if (glds_mode == 19 && M % 80 == 0) return launch_nt_glds<T, 1, 4, 5, 2, 5, 1, 2>(p, s);      // ... 5 slots
+  if (!p.a_f32) {
+    if (N <= 64) return launch_nt_glds<T, 4, 1, 1, 4, 4>(p, s);         // 64 x 64, skinny N
     {
       // Row-tile height: the flow's GEMMs have M = 64*B rows (1280 at B = 20) and N = 2048, i.e. 160 tiles of 128 x 128 on
       // 256 CUs.  80- or 160-row tiles give exactly 256 workgroups at B = 20 / 40; pick the height with the least
@@ -3294,9 +3247,6 @@ static int dispatch_nn(NtParams& p, hipStream_t s) {
   int best = 128; long best_cost = ((long)ceil_div(M, 128) * tn128 + 255) / 256 * 128;
   if (M % 160 == 0) { const long c = ((long)(M / 160) * tn128 + 255) / 256 * 160; if (c <= best_cost) { best = 160; best_cost = c; } }
   if (M % 80 == 0) { const long c = ((long)(M / 80) * tn128 + 255) / 256 * 80; if (c < best_cost) { best = 80; best_cost = c; } }
-  static const int nn_stages = getenv("IPOKE_NN_STAGES") ? atoi(getenv("IPOKE_NN_STAGES")) : 3;      // developer A/B: ring depth of the 80 x 128 tile
-  if (best == 80 && nn_stages == 4) return launch_nn_glds<1, 4, 5, 4, 2>(p, s);
-  if (best == 80 && nn_stages == 5) return launch_nn_glds<1, 4, 5, 5, 2>(p, s);
   if (best == 80) return launch_nn_glds<1, 4, 5, 3, 2>(p, s);       // 80 x 128: two K halves x 4 waves of 80 x 32 (the c2 shape: 256 workgroups)
   if (best == 160) return launch_nn_glds<2, 4, 5, 3, 1>(p, s);      // 160 x 128, 8 waves of 80 x 32
   return launch_nn_glds<2, 4, 4, 3, 1>(p, s);                       // 128 x 128
@@ -4038,10 +3988,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 static constexpr size_t kLdsHaloWg = 2 * (256 * 128 + 328 * 128) + 8 * 1024;
 static bool halo_wgrad_applicable(const TnParams& p) {
-  static const int on = getenv("IPOKE_WGRAD_HALO") ? atoi(getenv("IPOKE_WGRAD_HALO")) : 1;      // developer A/B: 0 keeps the implicit GEMM
   const GeomDev& g = p.g;
   const int kd = g.taps / 9;
-  return on && !p.batch && !p.a_f32 && p.a_sc == 1 && (g.taps == 9 || g.taps == 27) && g.khw == 9 && g.kw == 3 && !g.transposed &&
+  return !p.batch && !p.a_f32 && p.a_sc == 1 && (g.taps == 9 || g.taps == 27) && g.khw == 9 && g.kw == 3 && !g.transposed &&
          g.sd == 1 && g.sh == 1 && g.sw == 1 && g.ph == 1 && g.pw == 1 && g.pd == kd / 2 && g.Di == g.Do && g.Hi == g.Ho && g.Wi == g.Wo &&
          g.Ho % 16 == 0 && g.Wo % 16 == 0 && (g.taps == 27 || g.Di == 1) &&
          (p.a_coff & 7) == 0 && (p.Kc & 7) == 0 && p.Kc == p.Kc_real && ((p.a_sn | p.a_sd | p.a_sh | p.a_sw) & 7) == 0 &&
@@ -4078,9 +4027,8 @@ static int halo_wgrad_splits(const TnParams& p, int target_wgs) {
 }
 
 static bool lat8_applicable(const TnParams& p, int nbatch) {
-  static const int on = getenv("IPOKE_WGRAD_LAT8") ? atoi(getenv("IPOKE_WGRAD_LAT8")) : 1;      // developer A/B: 0 keeps the implicit-GEMM kernels
   const GeomDev& g = p.g;
-  return on && p.batch && nbatch >= 1 && !p.a_f32 && p.a_sc == 1 && g.taps == 9 && g.khw == 9 && g.kw == 3 && g.Di == 1 && g.Hi == 8 && g.Wi == 8 &&
+  return p.batch && nbatch >= 1 && !p.a_f32 && p.a_sc == 1 && g.taps == 9 && g.khw == 9 && g.kw == 3 && g.Di == 1 && g.Hi == 8 && g.Wi == 8 &&
          g.Do == 1 && g.Ho == 8 && g.Wo == 8 && g.sd == 1 && g.sh == 1 && g.sw == 1 && g.pd == 0 && g.ph == 1 && g.pw == 1 && !g.transposed &&
          p.a_sh == 8 * p.a_sw && p.a_sn == 64 * p.a_sw && (p.a_sw & 7) == 0 && (p.a_coff & 7) == 0 && (p.Kc & 7) == 0 && p.Kc == p.Kc_real &&
          (p.ldy & 7) == 0 && (p.y_coff & 7) == 0 && p.splitm == 1 && !p.accumulate && p.split_stride == 0 && p.w_sc == 9 && p.w_st == 1 &&
@@ -4094,18 +4042,10 @@ static int launch_lat8(const TnParams& t, hipStream_t s, int nbatch) {
   p.M = t.g.M; p.lda = (int)t.a_sw; p.a_coff = t.a_coff; p.Kc = t.Kc; p.Kc_store = t.Kc_store;
   p.ldy = t.ldy; p.y_coff = t.y_coff; p.Nout = t.Nout; p.w_sn = t.w_sn;
   p.tiles_n = ceil_div(t.Nout, 64); p.tiles_c = ceil_div(t.Kc, 64); p.z0 = 0;
-  static const int nst = getenv("IPOKE_LAT8_STAGES") ? atoi(getenv("IPOKE_LAT8_STAGES")) : 3;      // developer A/B: ring slots (2 samples each)
   const dim3 grid((unsigned)(p.tiles_n * p.tiles_c), 1, (unsigned)nbatch);
-  if (nst == 4) {
-    constexpr size_t lds4 = 4 * 2 * 128 * 128 + 256;
-    auto kern = wgrad3x3_lat8_kernel<4>;
-    IPK_SET_LDS_ONCE(kern, lds4);
-    hipLaunchKernelGGL(kern, grid, dim3(512), lds4, s, p);
-  } else {
-    auto kern = wgrad3x3_lat8_kernel<3>;
-    IPK_SET_LDS_ONCE(kern, kLdsLat8);
-    hipLaunchKernelGGL(kern, grid, dim3(512), kLdsLat8, s, p);
-  }
+  auto kern = wgrad3x3_lat8_kernel<3>;
+  IPK_SET_LDS_ONCE(kern, kLdsLat8);
+  hipLaunchKernelGGL(kern, grid, dim3(512), kLdsLat8, s, p);
   IPK_LAUNCH_CHECK();
   return IPOKE_OK;
 }
@@ -4133,40 +4073,31 @@ static int launch_tn(TnParams& p, hipStream_t s, int nbatch = 1) {
   }
   const size_t lds = 4 * 128 * kPitch + 256 * sizeof(int);
   // LDS-DMA + transposed-read kernel: bf16, dense operands with 16-byte aligned rows
-  static const int glds = getenv("IPOKE_TN_GLDS") ? atoi(getenv("IPOKE_TN_GLDS")) : 1;
   // (batched launches: the engine's workspace offsets are 256-byte aligned)
-  if (glds && sizeof(T) == 2 && !p.a_f32 && p.a_sc == 1 && (p.a_coff & 7) == 0 && (p.Kc & 7) == 0 &&
+  if (sizeof(T) == 2 && !p.a_f32 && p.a_sc == 1 && (p.a_coff & 7) == 0 && (p.Kc & 7) == 0 &&
       (p.ldy & 7) == 0 && (p.y_coff & 7) == 0 && ((p.a_sn | p.a_sd | p.a_sh | p.a_sw) & 7) == 0 &&
       (p.batch ? ((reinterpret_cast<uintptr_t>(p.a_base) | reinterpret_cast<uintptr_t>(p.y_base)) & 15) == 0
                : ((reinterpret_cast<uintptr_t>(p.A) | reinterpret_cast<uintptr_t>(p.dY)) & 15) == 0)) {
     // ring depth: 2 slots (64 KB of LDS) let a weight-gradient workgroup share a CU with a chain GEMM workgroup (89 KB): the
-    // same 29 us alone, 39 instead of 55 us inside the train step
-    // IPOKE_TN_STAGES (developer A/B): 2 (default) or 3 ring slots.  (Four slots of 32 rows in the same 64 KB -- three stages in
-    // flight, twice the barriers -- measured 35.5 against 29.7 us alone and 63.3 against 62.0 ms per step in round 3; removed.)
-    static const int nst = getenv("IPOKE_TN_STAGES") ? atoi(getenv("IPOKE_TN_STAGES")) : 2;
-    const int NST = nst == 3 ? 3 : 2;
+    // same 29 us alone, 39 instead of 55 us inside the train step; three slots measure the same alone.  (Four slots of 32 rows in the
+    // same 64 KB -- three stages in flight, twice the barriers -- measured 35.5 against 29.7 us alone and 63.3 against 62.0 ms per step
+    // in round 3; removed.)
+    constexpr int NST = 2;
     // narrow outputs of the flow engine's batched launches (conv3 of the coupling nets): 64 x 256 tiles (see the kernel)
-    static const int narrow_on = getenv("IPOKE_TN_NARROW") ? atoi(getenv("IPOKE_TN_NARROW")) : 1;      // developer A/B
-    const bool narrow = narrow_on && NST == 2 && p.batch != nullptr && p.Nout <= 64 && p.Ktot >= 512 && p.max_wgs <= 0;
+    const bool narrow = p.batch != nullptr && p.Nout <= 64 && p.Ktot >= 512 && p.max_wgs <= 0;
     if (narrow) p.tiles_k = ceil_div(p.Ktot, 256);
     g_last_wgrad_kernel = narrow ? IPOKE_WGRAD_KERNEL_TN_NARROW : IPOKE_WGRAD_KERNEL_TN_GLDS;
-    const int nst_n = narrow_on == 3 ? 3 : 2;                  // (developer A/B: IPOKE_TN_NARROW=3 = three ring slots, 144 KB)
-    const size_t lds2 = narrow ? (size_t)nst_n * 3 * 64 * 256 + 256 * sizeof(int) : (size_t)NST * 2 * 64 * 256 + 256 * sizeof(int);
+    const size_t lds2 = narrow ? (size_t)NST * 3 * 64 * 256 + 256 * sizeof(int) : (size_t)NST * 2 * 64 * 256 + 256 * sizeof(int);
     const bool adam = p.ad_p != nullptr;
     if (adam) IPK_REQUIRE(!narrow && p.batch && p.g.taps == 1 && p.w_sc == 1 && p.w_sn == p.Ktot && p.Nout % 128 == 0 && p.Ktot % 128 == 0 &&
                           p.splitm == 1 && !p.accumulate && p.Kc == p.Kc_real && (p.Kc_store == 0 || p.Kc_store == p.Kc) && (p.w_sn & 3) == 0,
                           "Adam in the weight-gradient epilogue: batched dense 1x1 problems in whole 128 x 128 tiles, one reduction split");
-    auto kern = adam ? (NST == 2 ? igemm_tn_glds_kernel<2, 64, false, true> : igemm_tn_glds_kernel<3, 64, false, true>)
-                : narrow ? (nst_n == 3 ? igemm_tn_glds_kernel<3, 64, true> : igemm_tn_glds_kernel<2, 64, true>)
-                       : NST == 2 ? igemm_tn_glds_kernel<2, 64> : igemm_tn_glds_kernel<3, 64>;
-    if (adam && NST == 2) { IPK_SET_LDS_ONCE(kern, lds2); } else if (adam) { IPK_SET_LDS_ONCE(kern, lds2); }
-    else if (narrow && nst_n == 3) { IPK_SET_LDS_ONCE(kern, lds2); } else if (narrow) { IPK_SET_LDS_ONCE(kern, lds2); }
-    else if (NST == 2) { IPK_SET_LDS_ONCE(kern, lds2); } else { IPK_SET_LDS_ONCE(kern, lds2); }      // one flag per instantiation
+    auto kern = adam ? igemm_tn_glds_kernel<NST, 64, false, true> : narrow ? igemm_tn_glds_kernel<NST, 64, true> : igemm_tn_glds_kernel<NST, 64>;
+    if (adam) { IPK_SET_LDS_ONCE(kern, lds2); } else if (narrow) { IPK_SET_LDS_ONCE(kern, lds2); } else { IPK_SET_LDS_ONCE(kern, lds2); }      // one flag per kernel
     const int ntiles = p.tiles_n * p.tiles_k;
     const int cap = p.max_wgs > 0 ? p.max_wgs : ntiles;
     p.xa = p.xb = 0;
-    static const bool xcd_map = !(getenv("IPOKE_TN_XCD") && atoi(getenv("IPOKE_TN_XCD")) == 0);      // developer A/B
-    if (xcd_map && cap >= ntiles && ntiles % 8 == 0) {     // whole problem in one launch, blockIdx.x % 8 = XCD for every (y, z)
+    if (cap >= ntiles && ntiles % 8 == 0) {     // whole problem in one launch, blockIdx.x % 8 = XCD for every (y, z)
       double best = -1;
       for (int xa = 1; xa <= 8; xa *= 2) {
         const int xb = 8 / xa;
@@ -4190,17 +4121,10 @@ static int launch_tn(TnParams& p, hipStream_t s, int nbatch = 1) {
     return IPOKE_OK;
   }
   IPK_REQUIRE(p.ad_p == nullptr, "Adam in the weight-gradient epilogue needs the LDS-DMA kernel (bf16, dense 16-byte aligned operands)");
-  static const int nr = getenv("IPOKE_TN_NR") ? atoi(getenv("IPOKE_TN_NR")) : 2;   // measured: 2 stages in flight beat 4 (54 vs 61 us at the NICE conv2 shape)
   dim3 grid((unsigned)(p.tiles_n * p.tiles_k), (unsigned)p.splitm, (unsigned)nbatch);
-  if (nr == 2) {
-    auto kern = igemm_tn_kernel<T, 2>;
-    IPK_SET_LDS_ONCE(kern, lds);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, p);
-  } else {
-    auto kern = igemm_tn_kernel<T, 4>;
-    IPK_SET_LDS_ONCE(kern, lds);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, p);
-  }
+  auto kern = igemm_tn_kernel<T, 2>;      // measured: 2 stages in flight beat 4 (54 vs 61 us at the NICE conv2 shape)
+  IPK_SET_LDS_ONCE(kern, lds);
+  hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, p);
   IPK_LAUNCH_CHECK();
   return IPOKE_OK;
 }
@@ -4214,12 +4138,12 @@ extern "C" void ipoke_gemm_set_stamps(long long* base) { g_gemm_stamps = base; }
 #endif
 
 /* Test hook: moves a kernel-dispatch switch at run time ("c64" / "halo16": 0 off, 1 default rule, 2 wherever the kernel can run;
- * value < 0 re-reads the environment default at the next launch). */
+ * value < 0 goes back to the default rule 1). */
 extern "C" int ipoke_set_dispatch_override(const char* name, int value) {
   IPK_REQUIRE(name != nullptr && value <= 2, "bad arguments");
   std::atomic<int>* slot = !strcmp(name, "c64") ? &g_c64_mode : (!strcmp(name, "halo16") ? &g_halo16_mode : nullptr);
   IPK_REQUIRE(slot != nullptr, "unknown dispatch switch (c64 | halo16)");
-  slot->store(value < 0 ? -1 : value, std::memory_order_relaxed);
+  slot->store(value < 0 ? 1 : value, std::memory_order_relaxed);
   return IPOKE_OK;
 }
 
@@ -4286,12 +4210,9 @@ extern "C" int ipoke_conv_forward(const ipoke_conv_desc* d, int dtype, void* str
   int rc = conv_params(p, d, dtype); if (rc) return rc;
   const int esz = dtype == IPOKE_BF16 ? 2 : 4;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  {
-    // s_setprio(2) in the chain's GEMMs: their waves win the issue arbitration against the co-resident weight-gradient /
-    // optimizer waves of the side streams (64.6 -> 63.3 ms per step; levels 1 / 2 / 3 measure the same)
-    static const int prio = getenv("IPOKE_NT_PRIO") ? atoi(getenv("IPOKE_NT_PRIO")) : 2;
-    p.prio = prio;
-  }
+  // s_setprio(2) in the chain's GEMMs: their waves win the issue arbitration against the co-resident weight-gradient /
+  // optimizer waves of the side streams (64.6 -> 63.3 ms per step; levels 1 / 2 / 3 measure the same)
+  p.prio = 2;
 #ifdef IPOKE_GEMM_STAMPS
   p.stamps = g_gemm_stamps;
   if (g_gemm_stamps) g_gemm_stamps += 4 * 4096;                // one slab of 4096 workgroups per launch

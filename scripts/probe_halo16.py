@@ -1,5 +1,5 @@
 """Developer probe: the wide halo-staged 3x3(x3) convolution (conv3x3_halo16_kernel) against the kernels the dispatcher used before
-(IPOKE_HALO16=0), at the shapes of the 3-D encoder (B = 20) and of the decoder / discriminator stacks."""
+(dispatch switch "halo16" at 0), at the shapes of the 3-D encoder (B = 20) and of the decoder / discriminator stacks."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -30,8 +30,8 @@ def run(shape, n=20):
     return us, gf / us * 1e-3, y
 for shape in SHAPES:
     res = {}
-    for mode in ("0", "2"):
-        os.environ["IPOKE_HALO16"] = mode
-        res[mode] = run(shape)
-    d = (res["0"][2].t.float() - res["2"][2].t.float()).abs().max().item()
-    print(f"{shape}: before {res['0'][0]:7.1f} us ({res['0'][1]:5.0f} TF/s)   halo16 {res['2'][0]:7.1f} us ({res['2'][1]:5.0f} TF/s)   max diff {d:.3g}")
+    for mode in (0, 2):
+        with _lib.dispatch_override("halo16", mode):
+            res[mode] = run(shape)
+    d = (res[0][2].t.float() - res[2][2].t.float()).abs().max().item()
+    print(f"{shape}: before {res[0][0]:7.1f} us ({res[0][1]:5.0f} TF/s)   halo16 {res[2][0]:7.1f} us ({res[2][1]:5.0f} TF/s)   max diff {d:.3g}")

@@ -20,8 +20,8 @@ DEV = "cuda"
                                                (20, 2048, 64, 3, 2), (20, 32, 2048, 3, 2), (7, 320, 136, 3, 1), (1, 64, 64, 3, 1)])
 def test_batched_weight_gradient_matches_torch(B, Cin, Cout, k, nb):
     """(the 3 x 3 cases run the stationary-input kernel wgrad3x3_lat8 of round 6 -- incl. the benchmarked conv3 / conv1 shapes of a
-    coupling net at B = 20, odd batches (a half-empty last stage), ragged output and input widths; IPOKE_WGRAD_LAT8=0 sends them through
-    the implicit-GEMM kernels again)"""
+    coupling net at B = 20, odd batches (a half-empty last stage), ragged output and input widths; the 1 x 1 case runs the
+    implicit-GEMM kernels)"""
     lib = _lib.lib()
     M = B * 64
     gen = torch.Generator().manual_seed(B * 100 + Cout + k)

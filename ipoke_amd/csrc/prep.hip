@@ -54,12 +54,14 @@ __device__ __forceinline__ void relayout_tile(const RelayoutJob& j, const float*
       const int n = n0 + nl, k = k0 + kl;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
       if (n < j.n_real && k < j.k_real) {
+        const float sc = j.scale_off >= 0 ? wn_scale[j.scale_off + n] : 1.f;      // x * 1.f == x bit for bit
+        const float* src = params + j.src_off + (long)n * j.s_n + k;
         if (k + 3 < j.k_real) {
-          v = *reinterpret_cast<const f32x4*>(params + j.src_off + (long)n * j.s_n + k);
+          v = *reinterpret_cast<const f32x4*>(src);
+          v[0] *= sc; v[1] *= sc; v[2] *= sc; v[3] *= sc;
         } else {
-          for (int q = 0; q < 4; ++q) if (k + q < j.k_real) v[q] = params[j.src_off + (long)n * j.s_n + k + q];
+          for (int q = 0; q < 4; ++q) if (k + q < j.k_real) v[q] = src[q] * sc;    // columns past k_real stay +0, unscaled
         }
-        if (j.scale_off >= 0) { const float sc = wn_scale[j.scale_off + n]; v[0] *= sc; v[1] *= sc; v[2] *= sc; v[3] *= sc; }
       }
 #pragma unroll
       for (int q = 0; q < 4; ++q) tile[nl * TP + kl + q] = v[q];

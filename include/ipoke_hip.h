@@ -808,6 +808,44 @@ int ipoke_pool_rows_weighted(const void* x, int ldx, void* y, int ldy, int64_t G
 int ipoke_activation_moments(const float* act, int n, int D, double* mu, double* sigma, int* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Reductions of the test loop (reference models/second_stage_video.py:665-752, 1037-1155).  Every sum is taken in a fixed order
+ * (double where the metric kernels above use double), there are no float atomics, no host synchronisation, and the caller owns
+ * every buffer: results are bit-reproducible run to run.
+ * --------------------------------------------------------------------------------------------- */
+/* utils/metrics.py:169-189 (SampleMetric.update with measure = ssim(reduction='none'), then .mean(dim=[1,2,3])): out[bs][ns][s] = the
+ * per-frame mean over C and the SSIM map of pred fp32 [bs][ns][s][C][H][W] against target fp32 [bs][1][s][C][H][W], which is read in place
+ * for every sample.  Same map as ipoke_psnr_ssim; the data range is per example: max(range of its ns * s predicted frames, range of its
+ * s target frames), as the reference's per-example call on [ns * s, C, H, W] gives.  H, W >= 11, ns * s * C <= 65535.
+ * workspace: ipoke_sample_ssim_workspace_bytes(...) bytes. */
+int64_t ipoke_sample_ssim_workspace_bytes(int bs, int ns, int s, int C, int H, int W);
+int ipoke_sample_ssim(const float* pred, const float* target, int bs, int ns, int s, int C, int H, int W, void* workspace, float* out,
+                      void* stream);
+/* utils/metrics.py:193-204: vals fp32 [bs][ns][s] -> per frame [bs][s]: nn = the values of the sample with the smallest mean over the
+ * frames (argmin also for SSIM, as the reference; the first index wins a tie), sd = unbiased standard deviation over the samples,
+ * mean = mean over the samples; index[bs] = the chosen sample.  The per-sample means are formed and compared in double (the reference's
+ * torch.argmin sees fp32 means): samples whose means differ by less than an fp32 rounding may resolve to the other index of the two. */
+int ipoke_sample_stats(const float* vals, int bs, int ns, int s, float* nn, float* sd, float* mean, int* index, void* stream);
+/* utils/metrics.py:104-124 (compute_div_score_mse): D fp32 [n_ex][ns][ns], D[e][j][k] = mean((v_j - v_k)^2) over the L elements of the
+ * videos x fp32 [n_ex][ns][L]; each element is read once per example, all ns (ns - 1) / 2 sums are formed together in double.
+ * 2 <= ns <= 64.  workspace: ipoke_pair_mse_workspace_bytes(n_ex, ns, L) bytes. */
+int64_t ipoke_pair_mse_workspace_bytes(int n_ex, int ns, int64_t L);
+int ipoke_pair_mse(const float* x, int n_ex, int ns, int64_t L, void* workspace, float* D, void* stream);
+/* utils/metrics.py:60-62, 88-94 (inner loops of compute_div_score) on one feature map of the ns * s frames of an example, channels-last
+ * rows fmap[(frame * HW + pos) * ld + c] of `dtype` (frame = j * s + t): per location (pos, c) the vector over the s frames of sample j is
+ * divided by (its L2 norm + 1e-10) -- normalize_activation normalizes over dim 0 of f[j], the TIME axis -- and CosineSimilarity(dim=0,
+ * eps=1e-8) contracts time again (each operand divided by max(its norm, eps)).  D fp32 [ns][ns] = the mean over the HW * C locations;
+ * all-zero locations contribute 0; the diagonal is written as 0.  The map is read once.  2 <= ns <= 64; ns <= 8 runs in registers
+ * (s <= 16), larger ns through LDS tiles.  workspace: ipoke_time_cosine_workspace_bytes(ns, s, C, HW) bytes. */
+int64_t ipoke_time_cosine_workspace_bytes(int ns, int s, int C, int64_t HW);
+int ipoke_time_cosine(const void* fmap, int ld, int C, int64_t HW, int ns, int s, int dtype, void* workspace, float* D, void* stream);
+/* models/second_stage_video.py:673-675 (_test_step_fvd): y uint8 [frames][H][W][3] = trunc((x + 1) * 127.5) of x fp32 [frames][3][H][W];
+ * the add and the multiply are two fp32 operations, so the result is bit-equal to numpy's astype(np.uint8) for x in [-1, 1].  Values
+ * outside that range -- where the numpy cast is undefined -- are clamped to [0, 255]. */
+int ipoke_video_to_u8(const float* x, uint8_t* y, int64_t frames, int H, int W, void* stream);
+/* utils/metrics.py:64-72 (normalize_input_vgg): y = ((x + 1) / 2 - mean[c]) / std[c] on fp32 [N][3][H][W], ImageNet mean / std. */
+int ipoke_vgg_normalize(const float* x, float* y, int64_t N, int H, int W, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Input pipeline on the device (reference data/base_dataset.py; host side in ipoke_amd/data.py).
  * ------------------------------------------------------------------------------------------- */
 /* _get_flow (:651-693): dst [B][C][Ho][Wo] = bilinear, align_corners=True, of src [B][C][Hi][Wi] / divide_by (the division is applied

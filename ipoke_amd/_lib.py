@@ -272,6 +272,15 @@ SIGNATURES = {
     "ipoke_pool3d_same": (c_int, [_P, _P, c_int, _P, c_int, c_int, _P]),
     "ipoke_pool_rows_weighted": (c_int, [_P, c_int, _P, c_int, c_int64, c_int, c_int, _P, c_int, _P]),
     "ipoke_activation_moments": (c_int, [_P, c_int, c_int, _P, _P, _P, _P]),
+    "ipoke_sample_ssim_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "ipoke_sample_ssim": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "ipoke_sample_stats": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    "ipoke_pair_mse_workspace_bytes": (c_int64, [c_int, c_int, c_int64]),
+    "ipoke_pair_mse": (c_int, [_P, c_int, c_int, c_int64, _P, _P, _P]),
+    "ipoke_time_cosine_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int64]),
+    "ipoke_time_cosine": (c_int, [_P, c_int, c_int, c_int64, c_int, c_int, c_int, _P, _P, _P]),
+    "ipoke_video_to_u8": (c_int, [_P, _P, c_int64, c_int, c_int, _P]),
+    "ipoke_vgg_normalize": (c_int, [_P, _P, c_int64, c_int, c_int, _P]),
     "ipoke_flow_resize": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P]),
     "ipoke_poke_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "ipoke_poke_simulate": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -185,19 +185,15 @@ __global__ void psnr_final_kernel(const float* __restrict__ mm, const double* __
 }
 // SSIM map of one plane tile: 32 x 32 output positions whose 11 x 11 windows lie inside the image (the reference pads by reflection and
 // crops the padded border away again, functional/ssim.py), separable Gaussian of the five moments, per-block partial sum in double.
-__global__ __launch_bounds__(256) void ssim_kernel(const float* __restrict__ a, const float* __restrict__ b, int H, int W, const float* __restrict__ mm,
-                                                   double* __restrict__ part) {
+// The tile body is shared by ssim_kernel (one data range for the whole call) and sample_ssim_kernel (one per example): thread 0 returns
+// the sum of the tile's SSIM values, every other thread an unspecified value.  256 threads.
+__device__ __forceinline__ double ssim_tile_sum(const float* __restrict__ pa, const float* __restrict__ pb, int H, int W, int y0, int x0, float range) {
   constexpr int TS = 32, K = 11, IN = TS + K - 1;           // 42 x 42 inputs per tile
   __shared__ float sa[IN][IN + 1], sb[IN][IN + 1];
   __shared__ float hz[5][IN][TS + 1];                       // horizontally filtered moments
   __shared__ float gw[K];
   __shared__ double red[4];
   const int Ho = H - (K - 1), Wo = W - (K - 1);
-  const int tiles_x = (Wo + TS - 1) / TS;
-  const int plane = blockIdx.y, ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-  const int y0 = ty * TS, x0 = tx * TS;
-  const float* pa = a + (long)plane * H * W;
-  const float* pb = b + (long)plane * H * W;
   if (threadIdx.x < K) {
     float sum = 0.f, mine = 0.f;
     for (int i = 0; i < K; ++i) {
@@ -225,7 +221,6 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float* __restrict__ a, 
     hz[0][r][c] = m0; hz[1][r][c] = m1; hz[2][r][c] = m2; hz[3][r][c] = m3; hz[4][r][c] = m4;
   }
   __syncthreads();
-  const float range = fmaxf(mm[1] + mm[0], mm[3] + mm[2]);   // max(preds.max() - preds.min(), target.max() - target.min())
   const float c1 = (0.01f * range) * (0.01f * range), c2 = (0.03f * range) * (0.03f * range);
   double acc = 0.0;
   for (int i = threadIdx.x; i < TS * TS; i += 256) {
@@ -245,7 +240,15 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float* __restrict__ a, 
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) part[(long)plane * gridDim.x + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  return red[0] + red[1] + red[2] + red[3];
+}
+__global__ __launch_bounds__(256) void ssim_kernel(const float* __restrict__ a, const float* __restrict__ b, int H, int W, const float* __restrict__ mm,
+                                                   double* __restrict__ part) {
+  const int tiles_x = (W - 10 + 31) / 32;
+  const int plane = blockIdx.y, ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const float range = fmaxf(mm[1] + mm[0], mm[3] + mm[2]);   // max(preds.max() - preds.min(), target.max() - target.min())
+  const double sum = ssim_tile_sum(a + (long)plane * H * W, b + (long)plane * H * W, H, W, ty * 32, tx * 32, range);
+  if (threadIdx.x == 0) part[(long)plane * gridDim.x + blockIdx.x] = sum;
 }
 __global__ void ssim_final_kernel(const double* __restrict__ part, long nparts, double count, float* __restrict__ out) {
   __shared__ double red[256];
@@ -255,6 +258,320 @@ __global__ void ssim_final_kernel(const double* __restrict__ part, long nparts, 
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
   if (threadIdx.x == 0) out[0] = (float)(red[0] / count);
+}
+
+// ---------------------------------------------------------------------------------------------- test loop: sample metrics
+// Reductions of the test loop (reference second_stage_video.py:665-752, 1037-1155, utils/metrics.py:60-124, 149-217).  Every sum below is
+// taken in a fixed order (per-block partials in caller-owned workspace, then one ordered pass over them); minima / maxima go through the
+// integer atomics above, whose result does not depend on arrival order.  No float atomic adds: results are bit-reproducible.
+
+// pair index p of the upper triangle (row-major: (0,1), (0,2), ..., (ns-2,ns-1)) -> (j, k), j < k
+__device__ __forceinline__ void pair_decode(int p, int ns, int& j, int& k) {
+  j = 0;
+  while (p >= ns - 1 - j) { p -= ns - 1 - j; ++j; }
+  k = j + 1 + p;
+}
+
+// mm[e][0..3] = {-min, max} of the ns * s predicted frames of example e and of its s target frames (SampleMetric.update calls the measure
+// per example on [ns * s, C, H, W], metrics.py:182-188, so ssim's data range is per example)
+__global__ void sample_range_kernel(const float* __restrict__ pred, long n_pred, const float* __restrict__ target, long n_tgt, float* __restrict__ mm) {
+  const int e = blockIdx.y;
+  const float* a = pred + (long)e * n_pred;
+  const float* b = target + (long)e * n_tgt;
+  float amin = INFINITY, amax = -INFINITY, bmin = INFINITY, bmax = -INFINITY;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_pred; i += (long)gridDim.x * blockDim.x) {
+    const float x = a[i];
+    amin = fminf(amin, x); amax = fmaxf(amax, x);
+  }
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_tgt; i += (long)gridDim.x * blockDim.x) {
+    const float y = b[i];
+    bmin = fminf(bmin, y); bmax = fmaxf(bmax, y);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    amin = fminf(amin, __shfl_xor(amin, o, 64)); amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    bmin = fminf(bmin, __shfl_xor(bmin, o, 64)); bmax = fmaxf(bmax, __shfl_xor(bmax, o, 64));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    float* m = mm + 4 * e;
+    if (amin <= amax) { atomic_max_f32(m + 0, -amin); atomic_max_f32(m + 1, amax); }      // (a block beyond the data saw nothing)
+    if (bmin <= bmax) { atomic_max_f32(m + 2, -bmin); atomic_max_f32(m + 3, bmax); }
+  }
+}
+// grid (tiles, ns * s * C, bs): plane q = (j * s + f) * C + c of example e against plane f * C + c of the example's target -- the target is
+// read in place for every sample, never replicated
+__global__ __launch_bounds__(256) void sample_ssim_kernel(const float* __restrict__ pred, const float* __restrict__ target, int ns, int sC, int H, int W,
+                                                          const float* __restrict__ mm, double* __restrict__ part) {
+  const int tiles_x = (W - 10 + 31) / 32;
+  const int e = blockIdx.z, q = blockIdx.y, ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int rem = q % sC;
+  const long hw = (long)H * W;
+  const float* m = mm + 4 * e;
+  const float range = fmaxf(m[1] + m[0], m[3] + m[2]);
+  const double sum = ssim_tile_sum(pred + ((long)e * ns * sC + q) * hw, target + ((long)e * sC + rem) * hw, H, W, ty * 32, tx * 32, range);
+  if (threadIdx.x == 0) part[((long)e * ns * sC + q) * gridDim.x + blockIdx.x] = sum;
+}
+// one block per frame: the C * tiles partials of a frame are adjacent
+__global__ void sample_ssim_final_kernel(const double* __restrict__ part, int per_frame, double count, float* __restrict__ out) {
+  __shared__ double red[64];
+  const double* p = part + (long)blockIdx.x * per_frame;
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < per_frame; i += 64) acc += p[i];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = 32; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+  if (threadIdx.x == 0) out[blockIdx.x] = (float)(red[0] / count);
+}
+
+// metrics.py:193-204: one block (one wave) per example over vals[ns][s].  The sample with the smallest mean over the frames is chosen
+// (argmin for SSIM too, as the reference; the first index wins a tie, as torch.argmin), then per frame: that sample's value, the unbiased
+// standard deviation over the samples (ns == 1: NaN, as torch.std) and the mean over the samples.  Sums in double, serial: fixed order.
+// The per-sample means are formed AND COMPARED in double, the reference's torch.argmin sees fp32 means: two samples whose means differ by
+// less than an fp32 rounding (an exact fp32 tie that is none in double, or the reverse) may give the other of the two indices.
+__global__ __launch_bounds__(64) void sample_stats_kernel(const float* __restrict__ vals, int ns, int s, float* __restrict__ nn, float* __restrict__ sd,
+                                                          float* __restrict__ mean, int* __restrict__ index) {
+  extern __shared__ double smean[];
+  __shared__ int best;
+  const float* v = vals + (long)blockIdx.x * ns * s;
+  for (int j = threadIdx.x; j < ns; j += 64) {
+    double acc = 0.0;
+    for (int f = 0; f < s; ++f) acc += (double)v[j * s + f];
+    smean[j] = acc / (double)s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int b = 0;
+    for (int j = 1; j < ns; ++j) if (smean[j] < smean[b]) b = j;
+    best = b;
+    index[blockIdx.x] = b;
+  }
+  __syncthreads();
+  for (int f = threadIdx.x; f < s; f += 64) {
+    double acc = 0.0;
+    for (int j = 0; j < ns; ++j) acc += (double)v[j * s + f];
+    const double mu = acc / (double)ns;
+    double sq = 0.0;
+    for (int j = 0; j < ns; ++j) { const double d = (double)v[j * s + f] - mu; sq += d * d; }
+    const long o = (long)blockIdx.x * s + f;
+    nn[o] = v[best * s + f];
+    sd[o] = (float)sqrt(sq / (double)(ns - 1));
+    mean[o] = (float)mu;
+  }
+}
+
+// metrics.py:104-124: D[e][j][k] = mean((v_j - v_k)^2) for all pairs of the ns samples of an example.  A block stages 64 elements of all
+// ns videos in LDS -- every element is read from memory once per example -- and each thread keeps the running sums of its (up to 8) pairs
+// in double registers across the tiles it visits; per-block partials, then one ordered pass.
+constexpr int PM_TILE = 64, PM_MAXNS = 64, PM_PP = 8;         // 64 * 63 / 2 = 2016 pairs <= 8 * 256
+__global__ __launch_bounds__(256) void pair_mse_kernel(const float* __restrict__ x, int ns, long L, double* __restrict__ part) {
+  __shared__ float tile[PM_MAXNS][PM_TILE + 1];
+  const int P = ns * (ns - 1) / 2;
+  const float* xe = x + (long)blockIdx.y * ns * L;
+  int pj[PM_PP], pk[PM_PP];
+  double acc[PM_PP];
+#pragma unroll
+  for (int i = 0; i < PM_PP; ++i) {
+    const int p = threadIdx.x + 256 * i;
+    pj[i] = 0; pk[i] = 0; acc[i] = 0.0;
+    if (p < P) pair_decode(p, ns, pj[i], pk[i]);
+  }
+  const long ntiles = (L + PM_TILE - 1) / PM_TILE;
+  const int col = threadIdx.x & 63;
+  for (long ti = blockIdx.x; ti < ntiles; ti += gridDim.x) {
+    const long idx = ti * PM_TILE + col;
+    for (int r = threadIdx.x >> 6; r < ns; r += 4) tile[r][col] = idx < L ? xe[(long)r * L + idx] : 0.f;     // a zero tail adds 0 to every pair
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < PM_PP; ++i) {
+      if ((int)threadIdx.x + 256 * i < P) {
+        const float* a = tile[pj[i]];
+        const float* b = tile[pk[i]];
+        double t = acc[i];
+#pragma unroll 8
+        for (int c = 0; c < PM_TILE; ++c) { const double d = (double)a[c] - (double)b[c]; t = fma(d, d, t); }
+        acc[i] = t;
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < PM_PP; ++i) {
+    const int p = threadIdx.x + 256 * i;
+    if (p < P) part[((long)blockIdx.y * gridDim.x + blockIdx.x) * P + p] = acc[i];
+  }
+}
+// D[g] = (sum over the nblk partials of group g) / count, written to both triangles; the diagonal is 0.  One block per group (example / map).
+__global__ void pair_final_kernel(const double* __restrict__ part, int nblk, int ns, double count, float* __restrict__ D) {
+  const int P = ns * (ns - 1) / 2;
+  const double* pg = part + (long)blockIdx.x * nblk * P;
+  float* Dg = D + (long)blockIdx.x * ns * ns;
+  for (int p = threadIdx.x; p < P; p += blockDim.x) {
+    double acc = 0.0;
+    for (int b = 0; b < nblk; ++b) acc += pg[(long)b * P + p];
+    int j, k;
+    pair_decode(p, ns, j, k);
+    const float v = (float)(acc / count);
+    Dg[j * ns + k] = v; Dg[k * ns + j] = v;
+  }
+  for (int j = threadIdx.x; j < ns; j += blockDim.x) Dg[j * ns + j] = 0.f;
+}
+
+// metrics.py:60-62, 88-94 on one feature map of the ns * s frames of an example, channels-last rows x[(frame * HW + pos) * ld + c]:
+// per location (pos, c) the s values of sample j form a vector over TIME; normalize_activation divides it by (its L2 norm + 1e-10), and
+// CosineSimilarity(dim=0, eps=1e-8) (ATen: each operand divided by max(its norm, eps), then the dot product) contracts time again.  A
+// location that is zero in every frame gives 0 / 1e-10 = 0 and contributes 0.  Output: the mean over locations of the ns x ns cosines.
+// u[t] <- x[t] / (|x| + 1e-10), then u[t] / max(|u|, 1e-8): the reference's two divisions, in its order
+template <int S_MAX>
+__device__ __forceinline__ void time_normalize(float (&a)[S_MAX]) {
+  float n2 = 0.f;
+#pragma unroll
+  for (int t = 0; t < S_MAX; ++t) n2 += a[t] * a[t];
+  const float d1 = sqrtf(n2) + 1e-10f;
+  float m2 = 0.f;
+#pragma unroll
+  for (int t = 0; t < S_MAX; ++t) { a[t] = a[t] / d1; m2 += a[t] * a[t]; }
+  const float d2 = fmaxf(sqrtf(m2), 1e-8f);
+#pragma unroll
+  for (int t = 0; t < S_MAX; ++t) a[t] = a[t] / d2;
+}
+// Small ns: one thread per location, the NS x s values in registers (lanes run along the channels: coalesced rows), the pair sums of
+// the locations a thread visits in double registers, one block reduction at the end.  s <= 16.
+template <typename T, int NS>
+__global__ __launch_bounds__(256) void time_cos_reg_kernel(const T* __restrict__ x, int ld, int C, long HW, int s, double* __restrict__ part) {
+  constexpr int P = NS * (NS - 1) / 2, S_MAX = 16;
+  __shared__ double red[4][P];
+  double acc[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) acc[p] = 0.0;
+  const long total = HW * C;
+  for (long l = (long)blockIdx.x * 256 + threadIdx.x; l < total; l += (long)gridDim.x * 256) {
+    const long pos = l / C; const int c = (int)(l - pos * C);
+    float a[NS][S_MAX];
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+#pragma unroll
+      for (int t = 0; t < S_MAX; ++t) a[j][t] = t < s ? ET<T>::to_f32(x[((long)(j * s + t) * HW + pos) * ld + c]) : 0.f;
+      time_normalize<S_MAX>(a[j]);
+    }
+    int p = 0;
+#pragma unroll
+    for (int j = 0; j < NS; ++j)
+#pragma unroll
+      for (int k = j + 1; k < NS; ++k, ++p) {
+        float dot = 0.f;
+#pragma unroll
+        for (int t = 0; t < S_MAX; ++t) dot += a[j][t] * a[k][t];
+        acc[p] += (double)dot;
+      }
+  }
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    double v = acc[p];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][p] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < P) part[(long)blockIdx.x * P + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+// Larger ns (up to 64): a block stages LOC consecutive locations of all ns * s frames in LDS as u[j][t * LOC + lo] (row pitch s * LOC + 1:
+// the threads of a wave read different samples j at one offset, the odd pitch spreads them over the banks), normalizes them in place, and
+// each thread adds the products of its (up to 8) pairs over the tile to double registers.
+template <typename T>
+__global__ __launch_bounds__(256) void time_cos_lds_kernel(const T* __restrict__ x, int ld, int C, long HW, int ns, int s, int LOC, double* __restrict__ part) {
+  extern __shared__ float u[];
+  const int P = ns * (ns - 1) / 2, row = s * LOC, pitch = row + 1;
+  int pj[PM_PP], pk[PM_PP];
+  double acc[PM_PP];
+#pragma unroll
+  for (int i = 0; i < PM_PP; ++i) {
+    const int p = threadIdx.x + 256 * i;
+    pj[i] = 0; pk[i] = 0; acc[i] = 0.0;
+    if (p < P) pair_decode(p, ns, pj[i], pk[i]);
+  }
+  const long total = HW * C, nchunks = (total + LOC - 1) / LOC;
+  for (long ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+    for (int i = threadIdx.x; i < ns * row; i += 256) {
+      const int fr = i / LOC, lo = i - fr * LOC;                   // fr = j * s + t
+      const long l = ch * LOC + lo;
+      float v = 0.f;                                               // locations beyond the map: zero vectors, contribute 0
+      if (l < total) { const long pos = l / C; v = ET<T>::to_f32(x[((long)fr * HW + pos) * ld + (l - pos * C)]); }
+      const int j = fr / s, t = fr - j * s;
+      u[j * pitch + t * LOC + lo] = v;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < ns * LOC; i += 256) {
+      const int j = i / LOC, lo = i - j * LOC;
+      float* q = u + j * pitch + lo;
+      float n2 = 0.f;
+      for (int t = 0; t < s; ++t) n2 += q[t * LOC] * q[t * LOC];
+      const float d1 = sqrtf(n2) + 1e-10f;
+      float m2 = 0.f;
+      for (int t = 0; t < s; ++t) { const float w = q[t * LOC] / d1; q[t * LOC] = w; m2 += w * w; }
+      const float d2 = fmaxf(sqrtf(m2), 1e-8f);
+      for (int t = 0; t < s; ++t) q[t * LOC] = q[t * LOC] / d2;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < PM_PP; ++i) {
+      if ((int)threadIdx.x + 256 * i < P) {
+        const float* a = u + pj[i] * pitch;
+        const float* b = u + pk[i] * pitch;
+        double t = acc[i];
+#pragma unroll 4
+        for (int c = 0; c < row; ++c) t += (double)(a[c] * b[c]);
+        acc[i] = t;
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < PM_PP; ++i) {
+    const int p = threadIdx.x + 256 * i;
+    if (p < P) part[(long)blockIdx.x * P + p] = acc[i];
+  }
+}
+
+// second_stage_video.py:673-675: ((x + 1) * 127.5) truncated to uint8, [B, T, 3, H, W] -> [B, T, H, W, 3].  The add and the multiply are two
+// rounded fp32 operations (never one fma), as numpy / torch evaluate them; for x in [-1, 1] the product lies in [0, 255] and the
+// truncation equals numpy's astype(np.uint8).  Outside that range numpy's cast is undefined behaviour: here the value is clamped to
+// [0, 255] (NaN -> 0).  One thread = four pixels of a frame (12 output bytes, three aligned words) when hw % 4 == 0, else one pixel.
+__device__ __forceinline__ unsigned u8_of(float x) {
+  const float v = __fmul_rn(__fadd_rn(x, 1.0f), 127.5f);
+  return (unsigned)fminf(fmaxf(v, 0.f), 255.f);                 // fmaxf(NaN, 0) = 0
+}
+__global__ void video_to_u8_kernel(const float* __restrict__ x, unsigned char* __restrict__ y, long frames, long hw, int vec) {
+  if (vec) {
+    const long q4 = hw / 4, total = frames * q4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+      const long fr = i / q4, px = (i - fr * q4) * 4;
+      const float* p = x + fr * 3 * hw + px;
+      const f32x4 r = *reinterpret_cast<const f32x4*>(p), g = *reinterpret_cast<const f32x4*>(p + hw), b = *reinterpret_cast<const f32x4*>(p + 2 * hw);
+      unsigned o[12];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { o[3 * k] = u8_of(r[k]); o[3 * k + 1] = u8_of(g[k]); o[3 * k + 2] = u8_of(b[k]); }
+      unsigned* w = reinterpret_cast<unsigned*>(y + (fr * hw + px) * 3);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) w[k] = o[4 * k] | (o[4 * k + 1] << 8) | (o[4 * k + 2] << 16) | (o[4 * k + 3] << 24);
+    }
+  } else {
+    const long total = frames * hw;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+      const long fr = i / hw, px = i - fr * hw;
+      const float* p = x + fr * 3 * hw + px;
+      unsigned char* w = y + i * 3;
+      w[0] = (unsigned char)u8_of(p[0]); w[1] = (unsigned char)u8_of(p[hw]); w[2] = (unsigned char)u8_of(p[2 * hw]);
+    }
+  }
+}
+// metrics.py:64-72 normalize_input_vgg: ((x + 1) / 2 - mean[c]) / std[c] on [N, 3, H, W] (ImageNet statistics), one element-wise pass
+__global__ void vgg_normalize_kernel(const float* __restrict__ x, float* __restrict__ y, long n, long hw) {
+  const float mean[3] = {0.485f, 0.456f, 0.406f}, sd[3] = {0.229f, 0.224f, 0.225f};
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)((i / hw) % 3);
+    const float m = c == 0 ? mean[0] : c == 1 ? mean[1] : mean[2], d = c == 0 ? sd[0] : c == 1 ? sd[1] : sd[2];
+    y[i] = __fsub_rn(__fadd_rn(x[i], 1.0f) / 2.0f, m) / d;
+  }
 }
 
 
@@ -350,6 +667,121 @@ extern "C" int ipoke_psnr_ssim(const float* preds, const float* target, int64_t 
   hipLaunchKernelGGL(ssim_kernel, dim3(tiles, (unsigned)planes), dim3(256), 0, s, preds, target, H, W, mm, part);
   IPK_LAUNCH_CHECK();
   hipLaunchKernelGGL(ssim_final_kernel, dim3(1), dim3(256), 0, s, part, (long)planes * tiles, (double)planes * Ho * Wo, out + 1);
+  IPK_LAUNCH_CHECK();
+  return IPOKE_OK;
+}
+
+/* ---- test loop reductions (declared in include/ipoke_hip.h) ---- */
+static long sample_ssim_tiles(int H, int W) { return (long)((H - 10 + 31) / 32) * ((W - 10 + 31) / 32); }
+extern "C" int64_t ipoke_sample_ssim_workspace_bytes(int bs, int ns, int s, int C, int H, int W) {
+  if (bs < 1 || ns < 1 || s < 1 || C < 1 || H < 11 || W < 11) return 0;
+  return (((int64_t)bs * 16 + 63) / 64) * 64 + 8 * (int64_t)bs * ns * s * C * sample_ssim_tiles(H, W);
+}
+extern "C" int ipoke_sample_ssim(const float* pred, const float* target, int bs, int ns, int s, int C, int H, int W, void* workspace, float* out,
+                                 void* stream) {
+  IPK_REQUIRE(pred && target && workspace && out && bs >= 1 && ns >= 1 && s >= 1 && C >= 1 && H >= 11 && W >= 11,
+              "bad arguments (images must be at least 11 x 11)");
+  IPK_REQUIRE((long)ns * s * C <= 65535 && bs <= 65535, "ns * s * C and bs must fit a grid dimension");
+  hipStream_t st = STREAM(stream);
+  float* mm = reinterpret_cast<float*>(workspace);
+  double* part = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(workspace) + (((int64_t)bs * 16 + 63) / 64) * 64);
+  const long hw = (long)H * W, n_tgt = (long)s * C * hw, n_pred = n_tgt * ns;
+  const int tiles = (int)sample_ssim_tiles(H, W), Ho = H - 10, Wo = W - 10;
+  IPK_HIP(hipMemsetAsync(mm, 0xff, (size_t)bs * 4 * sizeof(float), st));       // below every float in the order of atomic_max_f32
+  hipLaunchKernelGGL(sample_range_kernel, dim3(grid1(n_pred, 256), bs), dim3(256), 0, st, pred, n_pred, target, n_tgt, mm);
+  IPK_LAUNCH_CHECK();
+  hipLaunchKernelGGL(sample_ssim_kernel, dim3(tiles, ns * s * C, bs), dim3(256), 0, st, pred, target, ns, s * C, H, W, mm, part);
+  IPK_LAUNCH_CHECK();
+  hipLaunchKernelGGL(sample_ssim_final_kernel, dim3(bs * ns * s), dim3(64), 0, st, part, C * tiles, (double)C * Ho * Wo, out);
+  IPK_LAUNCH_CHECK();
+  return IPOKE_OK;
+}
+extern "C" int ipoke_sample_stats(const float* vals, int bs, int ns, int s, float* nn, float* sd, float* mean, int* index, void* stream) {
+  IPK_REQUIRE(vals && nn && sd && mean && index && bs >= 1 && ns >= 1 && s >= 1 && ns <= 4096, "bad arguments");
+  hipLaunchKernelGGL(sample_stats_kernel, dim3(bs), dim3(64), (size_t)ns * sizeof(double), STREAM(stream), vals, ns, s, nn, sd, mean, index);
+  IPK_LAUNCH_CHECK();
+  return IPOKE_OK;
+}
+static int pair_mse_blocks(int n_ex, int64_t L) {
+  const int64_t tiles = (L + PM_TILE - 1) / PM_TILE;
+  int64_t b = 2048 / (n_ex > 0 ? n_ex : 1);
+  if (b < 1) b = 1;
+  return (int)(tiles < b ? tiles : b);
+}
+extern "C" int64_t ipoke_pair_mse_workspace_bytes(int n_ex, int ns, int64_t L) {
+  if (n_ex < 1 || ns < 2 || L < 1) return 0;
+  return 8 * (int64_t)n_ex * pair_mse_blocks(n_ex, L) * (ns * (ns - 1) / 2);
+}
+extern "C" int ipoke_pair_mse(const float* x, int n_ex, int ns, int64_t L, void* workspace, float* D, void* stream) {
+  IPK_REQUIRE(x && workspace && D && n_ex >= 1 && n_ex <= 65535 && L >= 1, "bad arguments");
+  IPK_REQUIRE(ns >= 2 && ns <= PM_MAXNS, "2 <= ns <= 64 samples per example");
+  const int nblk = pair_mse_blocks(n_ex, L);
+  double* part = reinterpret_cast<double*>(workspace);
+  hipLaunchKernelGGL(pair_mse_kernel, dim3(nblk, n_ex), dim3(256), 0, STREAM(stream), x, ns, (long)L, part);
+  IPK_LAUNCH_CHECK();
+  hipLaunchKernelGGL(pair_final_kernel, dim3(n_ex), dim3(256), 0, STREAM(stream), part, nblk, ns, (double)L, D);
+  IPK_LAUNCH_CHECK();
+  return IPOKE_OK;
+}
+constexpr int TC_REG_MAX_NS = 8, TC_LDS_BYTES = 64 * 1024;
+static int time_cos_loc(int ns, int s) {       // locations per LDS tile: the largest of 64, 32, ..., 4 whose tile fits 64 KiB; 0: none does
+  for (int loc = 64; loc >= 4; loc >>= 1)
+    if ((int64_t)ns * (s * loc + 1) * 4 <= TC_LDS_BYTES) return loc;
+  return 0;
+}
+static int time_cos_blocks(int ns, int s, int64_t total) {
+  // work units of a launch: 256 locations per block on the register path, one LDS tile of `loc` locations otherwise
+  int64_t per_unit = 256;
+  if (ns > TC_REG_MAX_NS) {
+    const int loc = time_cos_loc(ns, s);
+    per_unit = loc > 0 ? loc : 1;
+  }
+  const int64_t units = (total + per_unit - 1) / per_unit;
+  return (int)(units < 1 ? 1 : units > 1024 ? 1024 : units);
+}
+extern "C" int64_t ipoke_time_cosine_workspace_bytes(int ns, int s, int C, int64_t HW) {
+  if (ns < 2 || s < 1 || C < 1 || HW < 1) return 0;
+  return 8 * (int64_t)time_cos_blocks(ns, s, HW * C) * (ns * (ns - 1) / 2);
+}
+template <typename T>
+static int time_cos_launch(const T* x, int ld, int C, long HW, int ns, int s, double* part, int nblk, hipStream_t st) {
+  switch (ns) {
+#define TC_CASE(N) case N: hipLaunchKernelGGL((time_cos_reg_kernel<T, N>), dim3(nblk), dim3(256), 0, st, x, ld, C, HW, s, part); break;
+    TC_CASE(2) TC_CASE(3) TC_CASE(4) TC_CASE(5) TC_CASE(6) TC_CASE(7) TC_CASE(8)
+#undef TC_CASE
+    default: {
+      const int loc = time_cos_loc(ns, s);
+      hipLaunchKernelGGL(time_cos_lds_kernel<T>, dim3(nblk), dim3(256), (size_t)ns * (s * loc + 1) * sizeof(float), st, x, ld, C, HW, ns, s, loc, part);
+    }
+  }
+  return 0;
+}
+extern "C" int ipoke_time_cosine(const void* fmap, int ld, int C, int64_t HW, int ns, int s, int dtype, void* workspace, float* D, void* stream) {
+  IPK_REQUIRE(fmap && workspace && D && C >= 1 && HW >= 1 && ld >= C && s >= 1, "bad arguments");
+  IPK_REQUIRE(dtype == IPOKE_BF16 || dtype == IPOKE_F32, "bad dtype");
+  IPK_REQUIRE(ns >= 2 && ns <= PM_MAXNS, "2 <= ns <= 64 samples per example");
+  IPK_REQUIRE(ns <= TC_REG_MAX_NS ? s <= 16 : time_cos_loc(ns, s) > 0, "sequence too long (register path: s <= 16; LDS path: ns * (4 s + 1) floats <= 64 KiB)");
+  const int nblk = time_cos_blocks(ns, s, HW * C);
+  double* part = reinterpret_cast<double*>(workspace);
+  if (dtype == IPOKE_BF16) time_cos_launch<bf16_t>((const bf16_t*)fmap, ld, C, (long)HW, ns, s, part, nblk, STREAM(stream));
+  else time_cos_launch<float>((const float*)fmap, ld, C, (long)HW, ns, s, part, nblk, STREAM(stream));
+  IPK_LAUNCH_CHECK();
+  hipLaunchKernelGGL(pair_final_kernel, dim3(1), dim3(256), 0, STREAM(stream), part, nblk, ns, (double)HW * C, D);
+  IPK_LAUNCH_CHECK();
+  return IPOKE_OK;
+}
+extern "C" int ipoke_video_to_u8(const float* x, uint8_t* y, int64_t frames, int H, int W, void* stream) {
+  IPK_REQUIRE(x && y && frames >= 1 && H >= 1 && W >= 1, "bad arguments");
+  const long hw = (long)H * W;
+  const int vec = hw % 4 == 0 && (reinterpret_cast<uintptr_t>(x) % 16) == 0 && (reinterpret_cast<uintptr_t>(y) % 4) == 0;
+  hipLaunchKernelGGL(video_to_u8_kernel, dim3(grid1(vec ? frames * (hw / 4) : frames * hw, 2048)), dim3(256), 0, STREAM(stream), x, y, (long)frames, hw, vec);
+  IPK_LAUNCH_CHECK();
+  return IPOKE_OK;
+}
+extern "C" int ipoke_vgg_normalize(const float* x, float* y, int64_t N, int H, int W, void* stream) {
+  IPK_REQUIRE(x && y && N >= 1 && H >= 1 && W >= 1, "bad arguments");
+  const long hw = (long)H * W, n = (long)N * 3 * hw;
+  hipLaunchKernelGGL(vgg_normalize_kernel, dim3(grid1(n, 2048)), dim3(256), 0, STREAM(stream), x, y, n, hw);
   IPK_LAUNCH_CHECK();
   return IPOKE_OK;
 }

@@ -46,6 +46,11 @@ class PokeMotionModel(nn.Module):
         self.global_step = 0
         self.current_epoch = 0
         self._optimizer = None
+        # state of the test loop (second_stage_video.py:150-180); the metric objects are built on first use
+        self.metrics_dict = {"KPS": {}, "LPIPS": {}, "SSIM": {}, "PSNR": {}}
+        self.div_scores = []
+        self.vggm = None
+        self._test_state = None
         self.device_ = torch.device(device) if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
         lr = tr["lr"]
@@ -572,6 +577,170 @@ class PokeMotionModel(nn.Module):
         for lst in (self._fvd_fake, self._fvd_true, self._fvd_fake_x0, self._fvd_true_x0):
             lst.clear()
         return fvd_score, fvd_x0
+
+    # ---- test loop (second_stage_video.py:665-752, 1037-1155) ------------------------------------------------
+    _TEST_MODES_MISSING = {
+        "samples": "the sample grids are written with the cv2 video writer (utils/logging.py save_video), which is not part of this package",
+        "kps_acc": "the targeted keypoint error needs the HRNet pose estimator (utils/posenet_wrapper.py) and its checkpoint",
+        "control_sensitivity": "the control-sensitivity study needs the HRNet pose estimator and the cv2 video writer",
+        "transfer": "the transfer grids are written with the cv2 video writer (utils/logging.py save_video)",
+    }
+
+    def sample_videos_device(self, batch, n_samples=1, n_logged_vids=1, add_first_frame=False, use_keypoint_pokes=False):
+        """``torch.stack(forward_sample(...), dim=1)`` without the ``.cpu()`` round trip: fp32 [B', n_samples, T, 3, H, W] on the device.
+        The latents are drawn from the CPU generator in the reference's order, one ``torch.randn`` per sample, so a seeded call equals
+        ``forward_sample`` bit for bit (the same kernels on the same data; tested)."""
+        self.first_stage_model.eval(); self.poke_embedder.eval()
+        if self.use_cond:
+            self.conditioner.eval()
+        out = None
+        with torch.no_grad():
+            X = batch["images"]
+            poke = self._poke_of(batch, use_keypoint_pokes)
+            spatial = self.first_stage_config["architecture"]["min_spatial_size"]
+            for i in range(n_samples):
+                z = torch.randn((X.size(0), self.config["architecture"]["flow_in_channels"], spatial, spatial)).type_as(X).detach()
+                if getattr(self, "_graph_sampling", False):
+                    video = self._sample_graphed(X, poke, z)
+                else:
+                    video = self._sample_device(X, poke, z)
+                if add_first_frame:
+                    video = torch.cat([X[:, 0].unsqueeze(1), video], dim=1)
+                video = video[:n_logged_vids]
+                if out is None:
+                    out = torch.empty((video.shape[0], n_samples) + tuple(video.shape[1:]), dtype=video.dtype, device=video.device)
+                out[:, i].copy_(video)                 # (a graph replay hands out its static buffer: copied before the next replay)
+        return out
+
+    def attach_metric_vgg(self, vgg=None, dtype="f32"):
+        """The reference builds ``self.vggm = metric_vgg16()`` with torchvision's ImageNet weights (:155); here the extractor is attached
+        explicitly (``ipoke_amd.vgg.metric_vgg16`` + ``load_torchvision_features``)."""
+        from .vgg import metric_vgg16
+        self.vggm = (metric_vgg16(dtype=dtype) if vgg is None else vgg).to(self.device_)
+        return self.vggm
+
+    def _test(self):
+        if self._test_state is None:
+            from . import metrics
+            self._test_state = {"real_u8": [], "fake_u8": [], "real": [], "fake": [], "ssim": metrics.SSIM_custom(), "psnr": metrics.PSNR_custom(),
+                                "sample_ssim": metrics.SampleSSIM(self.n_test_samples)}
+        return self._test_state
+
+    def _test_batch_size(self, X):
+        return self.config["testing"].get("test_batch_size", X.size(0))
+
+    def _test_step_fvd(self, batch):
+        """:665-678 -- one sample per clip; uint8 [B, T, H, W, 3] real and generated-with-x0 clips (converted on the device)."""
+        from . import metrics
+        st = self._test()
+        X = batch["images"]
+        sample = self.sample_videos_device(batch, 1, n_logged_vids=X.size(0))[:, 0]
+        gen = torch.cat([X[:, 0].unsqueeze(1), sample.type_as(X)], dim=1)
+        st["real_u8"].append(metrics.video_to_uint8(X))
+        st["fake_u8"].append(metrics.video_to_uint8(gen))
+        if getattr(self, "FVD", None) is not None:
+            st["real"].append(X); st["fake"].append(gen)
+
+    def _test_step_metrics(self, batch, batch_id):
+        """:681-743 without the keypoint and LPIPS terms."""
+        if "keypoints_rel" in batch and "keypoints_abs" in batch:
+            raise NotImplementedError("test mode 'accuracy' with keypoints in the batch: the keypoint term needs the HRNet pose estimator "
+                                      "(utils/posenet_wrapper.py) and its checkpoint; drop 'keypoints_rel' / 'keypoints_abs' from the data keys")
+        if self.config["testing"].get("lpips", False):
+            raise NotImplementedError("testing.lpips: the LPIPS term needs the lpips package's pretrained network, which is not available")
+        st = self._test()
+        imgs = batch["images"]
+        samples = self.sample_videos_device(batch, self.n_test_samples, n_logged_vids=self._test_batch_size(imgs), add_first_frame=True)
+        target_vid = imgs[:samples.shape[0], 1:].unsqueeze(1)
+        target_act = target_vid.reshape(-1, *target_vid.shape[3:])
+        for n_sample in range(samples.shape[1]):
+            samples_act = samples[:, n_sample, 1:].reshape(-1, *samples.shape[3:]).type_as(target_vid)
+            both = self._psnr_ssim(samples_act, target_act)
+            st["ssim"].update_value(both[1]); st["psnr"].update_value(both[0])
+        st["sample_ssim"].update(samples[:, :, 1:], target_vid)
+
+    @staticmethod
+    def _psnr_ssim(a, b):
+        from . import metrics
+        return metrics.psnr_ssim(a, b)
+
+    def _test_step_diversity(self, batch, batch_id):
+        """:746-752 -- the samples stay on the device."""
+        if self.config["testing"].get("div_kp", False):
+            raise NotImplementedError("testing.div_kp: the keypoint diversity score needs the HRNet pose estimator (utils/posenet_wrapper.py)")
+        if self.config["testing"].get("lpips", False):
+            raise NotImplementedError("testing.lpips: the LPIPS diversity term needs the lpips package's pretrained network, which is not available")
+        return self.sample_videos_device(batch, self.n_test_samples, n_logged_vids=self._test_batch_size(batch["images"]))
+
+    def test_step(self, batch, batch_id):
+        self.eval()
+        with torch.no_grad():
+            if self.test_mode == "fvd":
+                self._test_step_fvd(batch)
+            elif self.test_mode == "accuracy":
+                self._test_step_metrics(batch, batch_id)
+            elif self.test_mode in self._TEST_MODES_MISSING:
+                raise NotImplementedError(f"test mode '{self.test_mode}': {self._TEST_MODES_MISSING[self.test_mode]}")
+            elif self.test_mode == "diversity":
+                return self._test_step_diversity(batch, batch_id)
+            else:
+                raise ValueError(f'The specified test_mode is "{self.test_mode}", which is invalid...')
+
+    def test_step_end(self, out_step):
+        return out_step
+
+    def _n_pokes(self):
+        return self.config["testing"].get("n_pokes", self.config.get("data", {}).get("n_pokes", 1))
+
+    def test_epoch_end(self, outputs=None):
+        st = self._test()
+        if self.test_mode == "fvd":
+            savedir = os.path.join(self.dirs["generated"], "samples_fvd")
+            os.makedirs(savedir, exist_ok=True)
+            # np.stack over the per-batch arrays, as :1071-1072: [n_batches, B, T, H, W, 3] (the mp4 examples of :1075-1084 are not written)
+            real_samples = torch.stack(st["real_u8"], dim=0).cpu().numpy()
+            fake_samples = torch.stack(st["fake_u8"], dim=0).cpu().numpy()
+            np.save(os.path.join(savedir, "real_samples.npy"), real_samples)
+            np.save(os.path.join(savedir, "fake_samples.npy"), fake_samples)
+            score = None
+            if getattr(self, "FVD", None) is not None:
+                from .fvd import calculate_FVD
+                score = calculate_FVD(self.FVD.i3d, torch.cat(st["fake"]), torch.cat(st["real"]), batch_size=self.first_stage_config["logging"]["bs_i3d"])
+                self.log("FVD-test-x0", score)
+            for k in ("real_u8", "fake_u8", "real", "fake"):
+                st[k].clear()
+            return score
+        if self.test_mode == "accuracy":
+            n_pokes = self._n_pokes()
+            ssim_normal = st["ssim"].compute().cpu().numpy()
+            self.metrics_dict["SSIM"] = ssim_normal
+            self.metrics_dict["PSNR"] = st["psnr"].compute().cpu().numpy()
+            ssim_nn, ssim_dict = st["sample_ssim"].compute(n_pokes=n_pokes)
+            self.metrics_dict["SSIM NN"] = ssim_dict
+            self.log("ssim-test", ssim_normal); self.log("ssim-nn-test", ssim_nn)
+            st["sample_ssim"].reset(); st["ssim"].reset(); st["psnr"].reset()
+            return ssim_normal
+        if self.test_mode == "diversity":
+            from . import metrics
+            if self.vggm is None:
+                raise RuntimeError("test mode 'diversity' needs the VGG-16 feature extractor: call attach_metric_vgg() first")
+            n_pokes = self._n_pokes()
+            exmpls = torch.cat(outputs, dim=0)
+            div_score = metrics.compute_div_score(exmpls, self.vggm, device=self.device_)
+            div_score_mse = metrics.compute_div_score_mse(exmpls, device=self.device_)
+            self.div_scores.append(div_score)
+            savepath = os.path.join(self.dirs["generated"], "diversity")
+            metrics_dir = os.path.join(self.dirs["generated"], "metrics")
+            os.makedirs(savepath, exist_ok=True); os.makedirs(metrics_dir, exist_ok=True)
+            # the reference's line (:1145); its third term needs the lpips package and is reported as not computed
+            text = f"Similarity measure_vgg: {div_score}; similarity measure mse: {div_score_mse}; similarity measure lpips: {None}\n"
+            np.save(os.path.join(savepath, f"samples_diversity_{n_pokes}_pokes.npy"), exmpls.cpu().numpy())
+            with open(os.path.join(metrics_dir, "divscore.txt"), "a+") as f:
+                f.writelines(text)
+            return div_score
+        if self.test_mode in self._TEST_MODES_MISSING:
+            raise NotImplementedError(f"test mode '{self.test_mode}': {self._TEST_MODES_MISSING[self.test_mode]}")
+        raise ValueError(f'The specified test_mode is "{self.test_mode}", which is invalid...')
 
     def configure_optimizers(self):
         tr = self.config["training"]

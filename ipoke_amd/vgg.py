@@ -16,9 +16,15 @@ from .discriminator import _L1MeanFn, max_pool3d
 CFG_E = (64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512, 512, 512, 512, "M", 512)     # features[:30]
 SLICE_OF = lambda idx: 1 if idx < 2 else 2 if idx < 7 else 3 if idx < 12 else 4 if idx < 21 else 5
 TAPS = (1, 6, 11, 20, 29)                                       # relu1_1, relu2_1, relu3_1, relu4_1, relu5_1
+# torchvision configuration D: the 13 convolutions of vgg16().features[:30] (reference utils/metrics.py:20-58, slices [0,4) [4,9) [9,16) [16,23) [23,30))
+CFG_D = (64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512)
+SLICE_OF_D = lambda idx: 1 if idx < 4 else 2 if idx < 9 else 3 if idx < 16 else 4 if idx < 23 else 5
+TAPS_D = (3, 8, 15, 22, 29)                                     # relu1_2, relu2_2, relu3_3, relu4_3, relu5_3
 
 
 class VGG(nn.Module):
+    CFG, SLICE, TAP_IDX = CFG_E, staticmethod(SLICE_OF), TAPS     # the feature stack a subclass runs (``metric_vgg16``: configuration D)
+
     def __init__(self, requires_grad=False, dtype="bf16"):
         super().__init__()
         self.dtype = dtype
@@ -27,13 +33,13 @@ class VGG(nn.Module):
             setattr(self, f"slice{i}", nn.ModuleDict())
         self.program = []                                       # ("conv", slice, idx) | ("pool",) | ("tap",)
         idx, cin = 0, 3
-        for v in CFG_E:
+        for v in self.CFG:
             if v == "M":
                 self.program.append(("pool",)); idx += 1
                 continue
-            getattr(self, f"slice{SLICE_OF(idx)}")[str(idx)] = FS._Conv(cin, v, 3, 1, 1, bias=True, dims=2)
-            self.program.append(("conv", SLICE_OF(idx), str(idx)))
-            if idx + 1 in TAPS:
+            getattr(self, f"slice{self.SLICE(idx)}")[str(idx)] = FS._Conv(cin, v, 3, 1, 1, bias=True, dims=2)
+            self.program.append(("conv", self.SLICE(idx), str(idx)))
+            if idx + 1 in self.TAP_IDX:
                 self.program.append(("tap",))
             idx += 2; cin = v
         if not requires_grad:
@@ -41,14 +47,14 @@ class VGG(nn.Module):
                 p.requires_grad = False
 
     def load_torchvision_features(self, sd):
-        """``torchvision.models.vgg19().state_dict()`` (or its ``features`` part) -> this module."""
+        """``torchvision.models.vgg19().state_dict()`` (``vgg16`` for ``metric_vgg16``; or its ``features`` part) -> this module."""
         own = {}
         for k, v in sd.items():
             parts = k.split(".")
             if parts[0] == "features":
                 parts = parts[1:]
             if len(parts) == 2 and parts[0].isdigit() and int(parts[0]) < 30:
-                own[f"slice{SLICE_OF(int(parts[0]))}.{parts[0]}.{parts[1]}"] = v
+                own[f"slice{self.SLICE(int(parts[0]))}.{parts[0]}.{parts[1]}"] = v
         return self.load_state_dict(own, strict=True)
 
     def forward(self, X):
@@ -73,6 +79,21 @@ class VGG(nn.Module):
             else:
                 out.append(h)
         return out
+
+
+class metric_vgg16(VGG):
+    """Feature extractor of the diversity score (reference utils/metrics.py:20-58): ``torchvision.models.vgg16().features[:30]`` in five
+    slices, state-dict names ``slice{1..5}.{idx}.{weight,bias}``, taps after relu1_2, relu2_2, relu3_3, relu4_3 and relu5_3.
+    ``forward`` returns the five maps as channels-last records for ``metrics.time_cosine``.  ``pretrained`` is kept for the reference's
+    signature: the ImageNet weights cannot be fetched here, load them with ``load_torchvision_features``."""
+    CFG, SLICE, TAP_IDX = CFG_D, staticmethod(SLICE_OF_D), TAPS_D
+
+    def __init__(self, requires_grad=False, pretrained=False, dtype="f32"):
+        if pretrained:
+            raise NotImplementedError("metric_vgg16(pretrained=True) needs torchvision's ImageNet checkpoint, which is not bundled: build it with "
+                                      "pretrained=False and call load_torchvision_features(torchvision.models.vgg16(...).state_dict())")
+        super().__init__(requires_grad=requires_grad, dtype=dtype)
+        self.N_slices = 5
 
 
 class VGGLoss(nn.Module):

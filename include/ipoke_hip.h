@@ -742,7 +742,9 @@ int ipoke_avgpool_rows_bwd(const void* dy, int ldy, void* dx, int ldx, int64_t G
 /* GroupNorm tangent for the discriminators' gradient penalty (patchgan_3d.py:285-294), evaluated forward-over-reverse (see
  * vae_train.hip): ydot = act'(y) (gamma r (xdot - <xdot> - xhat <xhat xdot>) + resdot) per (sample, group); the backward
  * returns the gradients on xdot, on the PRIMAL input x (the second-order term, through the statistics), on resdot and on
- * gamma (fp32 [C], atomically accumulated).  x, xdot, y, q, ... are channels-last rows of the compute dtype. */
+ * gamma (fp32 [C], atomically accumulated).  x, xdot, y, q, ... are channels-last rows of the compute dtype, read and written in
+ * 16-byte pieces: C, every pitch and every base address of a tensor that is passed are multiples of 16 bytes (y counts only with an
+ * activation), C / G divides or is a multiple of the elements in 16 bytes, G <= 512. */
 int ipoke_groupnorm_jvp(const void* x, int ldx, const void* xdot, int ldxd, const void* y, int ldy, const void* resdot, int ldres,
                         void* ydot, int ldyd, const float* gamma, int N, int S, int C, int G, int act, float eps, float* workspace, int dtype,
                         void* stream);

@@ -531,6 +531,10 @@ struct GnJvp {
 // of column group cg over rows rr, rr + rp, ...): (1) per-channel sums over the chunk -> per-group sums, added atomically
 // into gsum[n][g][.]: sum x, x^2, u, x u (+ w, w x, w u in the backward); (2) the element-wise pass with the group scalars
 // derived from those sums (xhat sums follow from raw ones: <xhat u> = r (<x u> - mu <u>)).
+// Every x in those sums is taken relative to a pivot, the first element of its (sample, group): E[x^2] - mu^2 on raw values loses
+// (mu / sigma)^2 ulp of the variance, which at a shifted mean is orders of magnitude more than the primal norm's merged (count, mean, M2)
+// statistics lose; relative to a value of the group itself the cancellation is of order one.  Both kernels read the same pivot, so
+// the apply pass normalises (x - pivot) - mean(x - pivot) and never forms the rounded mean of x.
 constexpr int kGjPos = 128;          // positions per block
 constexpr int kGjMaxG = 512;         // groups per sample the block-level sums hold (host-checked)
 template <typename T, bool BWD>
@@ -543,7 +547,9 @@ __global__ __launch_bounds__(256) void gn_jvp_sums_kernel(const GnJvp a, float* 
   // partial sums straight into gsum[n][g][.] (2 560 addresses for 14 M atomics at the discriminator's 12 x 64 x 64 maps) a launch
   // took 1.0 ms for 0.1 ms of memory traffic
   __shared__ float bsum[NK][kGjMaxG];
+  __shared__ float piv[kGjMaxG];
   for (int i = threadIdx.x; i < NK * kGjMaxG; i += 256) (&bsum[0][0])[i] = 0.f;
+  for (int g = threadIdx.x; g < a.G; g += 256) piv[g] = ET<T>::to_f32(reinterpret_cast<const T*>(a.x)[(long)n * a.S * a.ldx + g * cpg]);
   __syncthreads();
   for (int g0 = 0; g0 < cvec; g0 += 256) {
     const int groups = cvec - g0 < 256 ? cvec - g0 : 256;
@@ -554,6 +560,9 @@ __global__ __launch_bounds__(256) void gn_jvp_sums_kernel(const GnJvp a, float* 
     for (int k = 0; k < NK; ++k)
 #pragma unroll
       for (int e = 0; e < E16; ++e) acc[k][e] = 0.f;
+    float pv[E16];
+#pragma unroll
+    for (int e = 0; e < E16; ++e) pv[e] = piv[(cg * E16 + e) / cpg];
     if (rr < rp) {
       for (int p = p0 + rr; p < p1; p += rp) {
         const long m = (long)n * a.S + p;
@@ -566,7 +575,7 @@ __global__ __launch_bounds__(256) void gn_jvp_sums_kernel(const GnJvp a, float* 
         }
 #pragma unroll
         for (int e = 0; e < E16; ++e) {
-          const float x = ET<T>::to_f32(xv[e]), u = ET<T>::to_f32(uv[e]);
+          const float x = ET<T>::to_f32(xv[e]) - pv[e], u = ET<T>::to_f32(uv[e]);
           acc[0][e] += x; acc[1][e] += x * x; acc[2][e] += u; acc[3][e] += x * u;
           if constexpr (BWD) {
             float w = ET<T>::to_f32(qv[e]) * (a.gamma ? a.gamma[cg * E16 + e] : 1.f);
@@ -605,7 +614,7 @@ template <typename T, bool BWD>
 __global__ __launch_bounds__(256) void gn_jvp_apply_kernel(const GnJvp a, const float* __restrict__ gsum) {
   constexpr int E16 = ET<T>::E16;
   typedef typename ET<T>::frag frag_t;
-  extern __shared__ float lds[];            // [8][G]: mu, r, ub, mm, aa, bb, k0, -  per group of this sample; then [C] dgamma partials
+  extern __shared__ float lds[];            // [8][G]: mu, r, ub, mm, aa, bb, k0, pivot  per group of this sample (mu: mean of x - pivot); then [C] dgamma partials
   const int n = blockIdx.y, p0 = blockIdx.x * kGjPos, p1 = min(a.S, p0 + kGjPos);
   const int cpg = a.C / a.G, cvec = a.C / E16, G = a.G;
   const float inv = 1.f / ((float)a.S * cpg);
@@ -614,6 +623,7 @@ __global__ __launch_bounds__(256) void gn_jvp_apply_kernel(const GnJvp a, const 
     const float mu = s[0] * inv, var = fmaxf(s[1] * inv - mu * mu, 0.f), r = rsqrtf(var + a.eps);
     const float ub = s[2] * inv, mm = r * (s[3] * inv - mu * ub);
     lds[g] = mu; lds[G + g] = r; lds[2 * G + g] = ub; lds[3 * G + g] = mm;
+    lds[7 * G + g] = ET<T>::to_f32(reinterpret_cast<const T*>(a.x)[(long)n * a.S * a.ldx + g * cpg]);      // the pivot of gn_jvp_sums_kernel
     if (BWD) {
       const float aa = s[4] * inv, bb = r * (s[5] * inv - mu * aa), cc = s[6] * inv;
       lds[4 * G + g] = aa; lds[5 * G + g] = bb; lds[6 * G + g] = cc - aa * ub - 3.f * bb * mm;
@@ -642,7 +652,7 @@ __global__ __launch_bounds__(256) void gn_jvp_apply_kernel(const GnJvp a, const 
         for (int e = 0; e < E16; ++e) {
           const int c = cg * E16 + e, g = c / cpg;
           const float mu = lds[g], r = lds[G + g], ub = lds[2 * G + g], mm = lds[3 * G + g];
-          const float xh = (ET<T>::to_f32(xv[e]) - mu) * r, u = ET<T>::to_f32(uv[e]);
+          const float xh = ((ET<T>::to_f32(xv[e]) - lds[7 * G + g]) - mu) * r, u = ET<T>::to_f32(uv[e]);
           const float gm = a.gamma ? a.gamma[c] : 1.f;
           const float da = a.act != IPOKE_ACT_NONE ? act_grad_from_out(a.act, ET<T>::to_f32(yv[e])) : 1.f;
           const float proj = r * (u - ub - xh * mm);
@@ -957,6 +967,7 @@ static int pool_geom(PoolGeom& g, const int* dims) {
 extern "C" int ipoke_maxpool3d_fwd(const int* dims, const void* x, int ldx, void* y, int ldy, int* idx, int dtype, void* stream) {
   IPK_REQUIRE(dims && x && y && idx, "null argument");
   PoolGeom g; int rc = pool_geom(g, dims); if (rc) return rc;
+  IPK_REQUIRE(ldx >= g.C && ldy >= g.C, "row pitches must cover the channel count");
   const long total = (long)g.N * g.Do * g.Ho * g.Wo * g.C;
   if (dtype == IPOKE_BF16)
     hipLaunchKernelGGL(maxpool3d_fwd_kernel<bf16_t>, dim3(grid1(total, 4096)), dim3(256), 0, STREAM(stream), g, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, idx);
@@ -968,6 +979,7 @@ extern "C" int ipoke_maxpool3d_fwd(const int* dims, const void* x, int ldx, void
 extern "C" int ipoke_maxpool3d_bwd(const int* dims, const void* dy, int ldy, const int* idx, void* dx, int ldx, int dtype, void* stream) {
   IPK_REQUIRE(dims && dy && dx && idx, "null argument");
   PoolGeom g; int rc = pool_geom(g, dims); if (rc) return rc;
+  IPK_REQUIRE(ldx >= g.C && ldy >= g.C, "row pitches must cover the channel count");
   const long total = (long)g.N * g.Di * g.Hi * g.Wi * ldx;
   if (dtype == IPOKE_BF16 && g.C % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && (((uintptr_t)dy | (uintptr_t)dx | (uintptr_t)idx) & 15) == 0)
     hipLaunchKernelGGL(maxpool3d_bwd_vec8_kernel, dim3(grid1(total / 8, 8192)), dim3(256), 0, STREAM(stream), g, (const bf16_t*)dy, ldy, idx, (bf16_t*)dx, ldx);
@@ -1012,6 +1024,16 @@ template <bool BWD>
 static int gn_jvp_launch(const GnJvp& a, float* gsum, int dtype, void* stream) {
   const int e16 = dtype == IPOKE_BF16 ? 8 : 4, cpg = a.C / a.G;
   IPK_REQUIRE(a.C % e16 == 0 && (cpg % e16 == 0 || e16 % cpg == 0) && a.ldx % e16 == 0 && a.ldxd % e16 == 0, "channels / pitches: multiples of 16 bytes");
+  // every tensor the kernels touch is read or written in 16-byte pieces: its pitch and base address count as much as x's
+  const bool use_y = a.y && a.act != IPOKE_ACT_NONE;
+  IPK_REQUIRE(!use_y || a.ldy % e16 == 0, "channels / pitches: multiples of 16 bytes");
+  if (!BWD) {
+    IPK_REQUIRE((!a.resd || a.ldres % e16 == 0) && a.ldyd % e16 == 0, "channels / pitches: multiples of 16 bytes");
+  } else {
+    IPK_REQUIRE(a.ldq % e16 == 0 && a.lddxd % e16 == 0 && a.lddx % e16 == 0 && (!a.dresd || a.lddresd % e16 == 0), "channels / pitches: multiples of 16 bytes");
+  }
+  IPK_REQUIRE((((uintptr_t)a.x | (uintptr_t)a.xd | (uintptr_t)(use_y ? a.y : nullptr) | (uintptr_t)a.resd | (uintptr_t)a.yd | (uintptr_t)a.q |
+                (uintptr_t)a.dxd | (uintptr_t)a.dx | (uintptr_t)a.dresd) & 15) == 0, "base addresses: multiples of 16 bytes");
   IPK_REQUIRE(a.G <= kGjMaxG, "GroupNorm tangent: at most 512 groups");
   const int nch = (a.S + kGjPos - 1) / kGjPos;
   const size_t lds = ((size_t)8 * a.G + a.C) * sizeof(float);

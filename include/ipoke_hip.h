@@ -275,6 +275,10 @@ int ipoke_reduce_rows_multi(const float* src, float* dst, const void* entries_de
 
 int ipoke_logdet_finalize(const float* slots, int nslots, int B, int slot_w, float const_term, const float* const_dev,
                           float* logdet, void* stream);
+/* out_scalar[0] = P * sum over the n referenced ActNorm layers of sum_c log_scale[c] (the batch-independent log-det, macow2.py:512).
+ * refs_dev[l] = {int64 off (floats into params: the layer's log_scale), int32 C (its channel count, any width >= 0), int32 pad}:
+ * ipoke_actnorm_logdet_ref_size() = 16 bytes per entry.  n == 0 writes 0. */
+int ipoke_actnorm_logdet_ref_size(void);
 int ipoke_actnorm_logdet(const float* params, const void* refs_dev, int n, int P, float* out_scalar, void* stream);
 /* FlowLoss (loss.py:6-31,75-79): scalars3 = (loss, nll, nlogdet); optional gradients in state layout */
 int ipoke_flow_nll(const float* z_state, const float* logdet, int B, int P, int C, int ld, float logdet_weight,
@@ -401,7 +405,11 @@ int ipoke_wn_bwd_multi_range(const float* params, float* grads, const float* inv
  * [W | W^-1 | wl | wu] (C*C floats each) per job in the workspace; apply: out[:, :C] = in[:, :C] mat^T (or mat), rest copied,
  * over 64 * B rows (the 1x1 convolution is row-wise: one workgroup per block of 64 rows = one sample of the 8x8 latent; B counts
  * those blocks, so any row count that is a multiple of 64 is valid);
- * wgrad writes dl, du, dlog_s of one layer into the flat gradient buffer (B samples of P8 positions each). */
+ * wgrad writes dl, du, dlog_s of one layer into the flat gradient buffer (B samples of P8 positions each).
+ * jobs_dev[i] = {int64 p_l, p_u, p_logs (floats into params); int64 b_perm, b_sign, b_lmask, b_umask, b_eye (floats into fbuf);
+ * int64 w_off (floats into the workspace); int32 C; int32 pad}: ipoke_lu_job_size() bytes per job.  Every job's C must be in
+ * 1 .. 64: prepare and wgrad read C from the DEVICE table and keep C x C tiles in fixed 64 x 65 LDS arrays, so this is the one limit
+ * the entry points cannot check -- the caller that builds the table must (ipoke_lu_apply, which is handed C, rejects C > 64). */
 int ipoke_lu_job_size(void);
 int ipoke_lu_prepare(const float* params, const float* fbuf, float* workspace, const void* jobs_dev, int njobs, void* stream);
 /* out[m][:C] = mat (or mat^T) in[m][:C] on M state rows of pitch ld (M = B * positions per sample); columns >= C are copied */

@@ -181,6 +181,7 @@ SIGNATURES = {
     "ipoke_reduce_rows": (c_int, [_P, _P, c_int, c_int, _P]),
     "ipoke_spin_delay": (c_int, [c_int, _P]),
     "ipoke_logdet_finalize": (c_int, [_P, c_int, c_int, c_int, c_float, _P, _P, _P]),
+    "ipoke_actnorm_logdet_ref_size": (c_int, []),
     "ipoke_actnorm_logdet": (c_int, [_P, _P, c_int, c_int, _P, _P]),
     "ipoke_flow_nll": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, _P]),
     "ipoke_adam_amsgrad_step": (c_int, [_P, _P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float, c_int,

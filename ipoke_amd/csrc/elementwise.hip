@@ -688,7 +688,7 @@ __global__ void logdet_finalize_kernel(const float* __restrict__ slots, int nslo
   if (threadIdx.x == 0) logdet[b] = tot + const_term + (const_dev ? const_dev[0] : 0.f);
 }
 // out_scalar[0] = P * sum over `n` ActNorm layers of sum_c log_scale  (batch independent, macow2.py:512)
-struct LsRef { long off; int C; };
+struct LsRef { long off; int C; };                  // 16 bytes with the tail padding (ipoke_actnorm_logdet_ref_size)
 __global__ void actnorm_logdet_kernel(const float* __restrict__ params, const LsRef* __restrict__ refs, int n, int P,
                                       float* __restrict__ out_scalar) {
   __shared__ float red[16];
@@ -1041,6 +1041,7 @@ extern "C" int ipoke_logdet_finalize(const float* slots, int nslots, int B, int 
   IPK_LAUNCH_CHECK();
   return IPOKE_OK;
 }
+extern "C" int ipoke_actnorm_logdet_ref_size(void) { return (int)sizeof(LsRef); }
 extern "C" int ipoke_actnorm_logdet(const float* params, const void* refs_dev, int n, int P, float* out_scalar, void* stream) {
   IPK_REQUIRE(params && refs_dev && out_scalar, "null tensor");
   hipLaunchKernelGGL(actnorm_logdet_kernel, dim3(1), dim3(1024), 0, STREAM(stream), params, (const LsRef*)refs_dev, n, P,

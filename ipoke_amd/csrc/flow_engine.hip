@@ -870,6 +870,7 @@ static int ensure_device(ipoke_flow* f) {
     IPK_HIP(hipMalloc(&f->d_lujobs, f->lujobs.size() * sizeof(LuJobH)));
     IPK_HIP(hipMemcpy(f->d_lujobs, f->lujobs.data(), f->lujobs.size() * sizeof(LuJobH), hipMemcpyHostToDevice));
   }
+  IPK_REQUIRE((int)sizeof(LsRefH) == ipoke_actnorm_logdet_ref_size(), "ActNorm log-det reference table layout mismatch");
   IPK_HIP(hipMalloc(&f->d_lsrefs, f->lsrefs.size() * sizeof(LsRefH)));
   IPK_HIP(hipMemcpy(f->d_lsrefs, f->lsrefs.data(), f->lsrefs.size() * sizeof(LsRefH), hipMemcpyHostToDevice));
   {   // weight gradients are off the critical path: lowest priority so that chain kernels get the CUs first

@@ -873,6 +873,30 @@ int64_t ipoke_poke_workspace_bytes(int B, int H, int W, int poke_size, int n_pok
 int ipoke_poke_simulate(const float* flow, int B, int H, int W, int poke_size, int n_pokes, int fix_n_pokes, int equal_poke_val,
                         const int* zero_poke, const float* u, float* poke, int64_t* centers, float* flow_out, int* status, void* workspace,
                         void* stream);
+/* Poke editing.  Both entry points write squares with the semantics of the reference's slice assignment
+ *     p[:, r - half : r + half + 1, c - half : c + half + 1] = v
+ * under Python's slice rules: a start (or stop) below zero wraps once by the extent and then clamps at 0, one above the extent clamps at
+ * the extent, an empty range writes nothing -- a centre at (0, 0) with half = 2 on a 64-row map is the slice 62:3, which is empty.
+ *
+ * ipoke_poke_stamp (second_stage_video.py:959-966; testing/gui.py:120-150): poke [B][2][H][W] = zeros with the squares of the pokes
+ * 0 .. n-1 written in that order (where squares overlap the later poke wins).  centers int64 [B][n][2] = (row, col); the value of poke j
+ * is values[b][j][0..1] (fp32 [B][n][2]) or, when values is NULL, flow[b][:][row][col] of flow fp32 [B][2][H][W] -- in that mode a centre
+ * outside the map has no value and is left out.  skip_negative != 0 leaves out every centre with a negative coordinate (the -1 padding
+ * rows of poke_centers, which :963 drops).  Every element of poke is written; values are copied, never computed. */
+int ipoke_poke_stamp(const int64_t* centers, const float* values, const float* flow, int B, int H, int W, int n, int half,
+                     int skip_negative, float* poke, void* stream);
+/* _control_sensitivity (second_stage_video.py:798-833) for all samples and all n_s sampled pokes: per sample the amplitude
+ * sqrt(fx^2 + fy^2) of flow [B][2][H][W], its mean (summed in double in a fixed order), the candidate pixels with amplitude > mean in
+ * row-major order (the reference normalises by (a - min) / max first, which leaves the set as it is), and from u fp32 [B][n_s][2] in [0, 1)
+ * for sampled poke j: candidate min(floor(u[b][j][0] * n_valid), n_valid - 1) -- the mapping of a uniform to randint that
+ * ipoke_poke_simulate uses --, phase = the amplitude there, angle = pi * u[b][j][1] (the upper half plane only, as the reference), value
+ * (cos(angle) * phase, sin(angle) * phase), stamped under the slice rules above around the sample's FIRST centre centers[b][0] only
+ * (int64 [B][n_c][2]), on zeros.  Outputs: pokes [n_s][B][2][H][W], picked int64 [B][n_s][2] = the chosen (row, col), status int32 [B]:
+ * 0, 1 = no candidate (a constant map; the reference's randint(0) raises), 2 = negative first centre; flagged samples get zero pokes and
+ * picked = -1.  No atomics: two runs are bit-identical.  1 <= n_s <= 64.  workspace: ipoke_poke_randomize_workspace_bytes. */
+int64_t ipoke_poke_randomize_workspace_bytes(int B, int H, int W, int n_s);
+int ipoke_poke_randomize(const float* flow, const int64_t* centers, const float* u, int B, int H, int W, int n_c, int n_s, int half,
+                         float* pokes, int64_t* picked, int* status, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -255,3 +255,147 @@ extern "C" int ipoke_poke_simulate(const float* flow, int B, int H, int W, int p
   IPK_LAUNCH_CHECK();
   return IPOKE_OK;
 }
+
+// ---------------------------------------------------------------------------------------------- poke editing
+// Python's slice a:b on an axis of `extent` elements for a = c - half, b = c + half + 1: an index below zero wraps ONCE by the extent and
+// then clamps at 0, one above the extent clamps at the extent; lo >= hi is the empty slice.
+__device__ __forceinline__ void slice_range(long long c, int half, int extent, int* lo, int* hi) {
+  long long a = c - half, b = c + half + 1;
+  if (a < 0) { a += extent; if (a < 0) a = 0; } else if (a > extent) a = extent;
+  if (b < 0) { b += extent; if (b < 0) b = 0; } else if (b > extent) b = extent;
+  *lo = (int)a; *hi = (int)b;
+}
+__device__ __forceinline__ bool square_covers(long long r, long long c, int half, int H, int W, int y, int x) {
+  int y0, y1, x0, x1;
+  slice_range(r, half, H, &y0, &y1); slice_range(c, half, W, &x0, &x1);
+  return y >= y0 && y < y1 && x >= x0 && x < x1;
+}
+
+// poke[b][:][y][x] = the value of the LAST poke whose square covers (y, x), else 0.  values [B][n][2], or (values == nullptr) the flow at
+// the poke's centre: a centre outside the map has no flow value and is left out in that mode.
+__global__ void poke_stamp_kernel(const long long* __restrict__ centers, const float* __restrict__ values, const float* __restrict__ flow,
+                                  float* __restrict__ poke, int B, int H, int W, int n, int half, int skip_negative) {
+  const long total = (long)B * H * W, HW = (long)H * W;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int x = (int)(i % W); long t = i / W;
+    const int y = (int)(t % H); const int b = (int)(t / H);
+    float v0 = 0.f, v1 = 0.f;
+    for (int j = n - 1; j >= 0; --j) {
+      const long long r = centers[((long)b * n + j) * 2], c = centers[((long)b * n + j) * 2 + 1];
+      if (skip_negative && (r < 0 || c < 0)) continue;
+      if (!values && (r < 0 || r >= H || c < 0 || c >= W)) continue;
+      if (!square_covers(r, c, half, H, W, y, x)) continue;
+      if (values) { v0 = values[((long)b * n + j) * 2]; v1 = values[((long)b * n + j) * 2 + 1]; }
+      else { const float* f = flow + (long)b * 2 * HW + r * W + c; v0 = f[0]; v1 = f[HW]; }
+      break;
+    }
+    float* o = poke + (long)b * 2 * HW + (long)y * W + x;
+    o[0] = v0; o[HW] = v1;
+  }
+}
+
+// _control_sensitivity (second_stage_video.py:798-833), one workgroup per sample: amplitude map -> mean (double, fixed order) -> the
+// candidates above it in row-major order -> n_s picks and their re-aimed values.  The map lives in LDS when it fits (amp_ws == nullptr).
+constexpr int kMaxRandomPokes = 64;
+constexpr long kRandomizeLdsFloats = 16384;          // 128 x 128: 64 KB of the CU's 160 KB, beside ~1.5 KB of reduction scratch
+struct RandomizeArgs {
+  const float* flow; const long long* centers; const float* u; float* amp_ws; float* val; long long* picked; int* status;
+  int B, H, W, n_c, n_s;
+};
+
+__global__ __launch_bounds__(kPokeThreads) void poke_randomize_select_kernel(RandomizeArgs p) {
+  extern __shared__ float amp_lds[];
+  __shared__ double red_d[16];
+  __shared__ int sh_i[256];
+  __shared__ int picks[kMaxRandomPokes], pos[kMaxRandomPokes];
+  const int b = blockIdx.x, tid = threadIdx.x, n = p.H * p.W;
+  const float* fx = p.flow + (long)b * 2 * n;
+  const float* fy = fx + n;
+  float* a = p.amp_ws ? p.amp_ws + (long)b * n : amp_lds;
+  double s = 0.0;
+  for (int i = tid; i < n; i += blockDim.x) {
+    const float vx = fx[i], vy = fy[i];
+    const float v = __fsqrt_rn(__fadd_rn(__fmul_rn(vx, vx), __fmul_rn(vy, vy)));
+    a[i] = v; s += (double)v;
+  }
+  const double mean_d = block_sum_d(s, red_d) / (double)n;
+  // a > mean_d for an fp32 a  <=>  a > (mean_d rounded DOWN to fp32)
+  const float thr = __double2float_rd(mean_d);
+  int cnt = 0;
+  for (int i = tid; i < n; i += blockDim.x) cnt += a[i] > thr;
+  int n_valid;
+  block_scan(cnt, sh_i, &n_valid);
+  const long long r0 = p.centers[(long)b * p.n_c * 2], c0 = p.centers[(long)b * p.n_c * 2 + 1];
+  // no candidate (a constant map: the reference's randint(0) raises) comes first, as in the reference; then the padded first centre
+  const int status = n_valid == 0 ? 1 : (r0 < 0 || c0 < 0) ? 2 : 0;
+  if (tid == 0) p.status[b] = status;
+  long long* picked = p.picked + (long)b * p.n_s * 2;
+  float* val = p.val + (long)b * p.n_s * 2;
+  if (status != 0) {
+    for (int i = tid; i < 2 * p.n_s; i += blockDim.x) { picked[i] = -1; val[i] = 0.f; }
+    return;
+  }
+  const float* u = p.u + (long)b * p.n_s * 2;
+  if (tid < p.n_s) { picks[tid] = min((int)floor((double)u[2 * tid] * (double)n_valid), n_valid - 1); pos[tid] = 0; }
+  __syncthreads();
+  pick_positions(a, n, SEL_GT0, thr, picks, p.n_s, pos, sh_i);
+  if (tid < p.n_s) {
+    const int q = pos[tid];
+    const float phase = a[q], angle = __fmul_rn(3.14159265358979323846f, u[2 * tid + 1]);
+    picked[2 * tid] = q / p.W; picked[2 * tid + 1] = q % p.W;
+    val[2 * tid] = __fmul_rn(cosf(angle), phase); val[2 * tid + 1] = __fmul_rn(sinf(angle), phase);
+  }
+}
+
+// pokes[j][b][:][y][x] = val[b][j] inside the square around the sample's FIRST centre, 0 elsewhere and for flagged samples
+__global__ void poke_randomize_fill_kernel(const long long* __restrict__ centers, const float* __restrict__ val, const int* __restrict__ status,
+                                           float* __restrict__ pokes, int B, int H, int W, int n_c, int n_s, int half) {
+  const long HW = (long)H * W, total = (long)n_s * B * HW;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int x = (int)(i % W); long t = i / W;
+    const int y = (int)(t % H); t /= H;
+    const int b = (int)(t % B), j = (int)(t / B);
+    const bool on = status[b] == 0 && square_covers(centers[(long)b * n_c * 2], centers[(long)b * n_c * 2 + 1], half, H, W, y, x);
+    float* o = pokes + ((long)j * B + b) * 2 * HW + (long)y * W + x;
+    o[0] = on ? val[((long)b * n_s + j) * 2] : 0.f;
+    o[HW] = on ? val[((long)b * n_s + j) * 2 + 1] : 0.f;
+  }
+}
+
+extern "C" int ipoke_poke_stamp(const int64_t* centers, const float* values, const float* flow, int B, int H, int W, int n, int half,
+                                int skip_negative, float* poke, void* stream) {
+  IPK_REQUIRE(centers && poke && (values || flow), "null argument (values or flow must be given)");
+  IPK_REQUIRE(B >= 1 && H >= 1 && W >= 1 && n >= 0 && half >= 0, "bad poke configuration");
+  hipLaunchKernelGGL(poke_stamp_kernel, dim3(grid1((long)B * H * W)), dim3(256), 0, STREAM(stream), reinterpret_cast<const long long*>(centers),
+                     values, flow, poke, B, H, W, n, half, skip_negative);
+  IPK_LAUNCH_CHECK();
+  return IPOKE_OK;
+}
+
+extern "C" int64_t ipoke_poke_randomize_workspace_bytes(int B, int H, int W, int n_s) {
+  const long n = (long)H * W;
+  return (int64_t)B * ((long)n_s * 2 + (n > kRandomizeLdsFloats ? n : 0)) * (long)sizeof(float);
+}
+
+extern "C" int ipoke_poke_randomize(const float* flow, const int64_t* centers, const float* u, int B, int H, int W, int n_c, int n_s, int half,
+                                    float* pokes, int64_t* picked, int* status, void* workspace, void* stream) {
+  IPK_REQUIRE(flow && centers && u && pokes && picked && status && workspace, "null argument");
+  IPK_REQUIRE(B >= 1 && H >= 1 && W >= 1 && (long)H * W < (1L << 30) && n_c >= 1 && half >= 0, "bad poke configuration");
+  IPK_REQUIRE(n_s >= 1 && n_s <= kMaxRandomPokes, "1 <= n_s <= 64 sampled pokes per launch");
+  const long n = (long)H * W;
+  const bool in_lds = n <= kRandomizeLdsFloats;
+  RandomizeArgs a;
+  a.flow = flow; a.centers = reinterpret_cast<const long long*>(centers); a.u = u;
+  a.val = reinterpret_cast<float*>(workspace); a.amp_ws = in_lds ? nullptr : a.val + (long)B * n_s * 2;
+  a.picked = reinterpret_cast<long long*>(picked); a.status = status;
+  a.B = B; a.H = H; a.W = W; a.n_c = n_c; a.n_s = n_s;
+  const size_t lds = in_lds ? (size_t)n * sizeof(float) : 0;
+  // the 128 x 128 map and the static scratch together pass the 64 KB a kernel may use without asking
+  IPK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(poke_randomize_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)(kRandomizeLdsFloats * sizeof(float))));
+  hipLaunchKernelGGL(poke_randomize_select_kernel, dim3(B), dim3(kPokeThreads), lds, STREAM(stream), a);
+  hipLaunchKernelGGL(poke_randomize_fill_kernel, dim3(grid1((long)n_s * B * n)), dim3(256), 0, STREAM(stream), a.centers, a.val, status, pokes, B, H,
+                     W, n_c, n_s, half);
+  IPK_LAUNCH_CHECK();
+  return IPOKE_OK;
+}

@@ -582,8 +582,10 @@ class PokeMotionModel(nn.Module):
     _TEST_MODES_MISSING = {
         "samples": "the sample grids are written with the cv2 video writer (utils/logging.py save_video), which is not part of this package",
         "kps_acc": "the targeted keypoint error needs the HRNet pose estimator (utils/posenet_wrapper.py) and its checkpoint",
-        "control_sensitivity": "the control-sensitivity study needs the HRNet pose estimator and the cv2 video writer",
-        "transfer": "the transfer grids are written with the cv2 video writer (utils/logging.py save_video)",
+        "control_sensitivity": "the control-sensitivity study needs the HRNet pose estimator and the cv2 video writer; its pokes and samples, "
+                               "without the files, come from control_sensitivity_samples()",
+        "transfer": "the transfer grids are written with the cv2 video writer (utils/logging.py save_video); the transferred and sampled "
+                    "videos, without the files, come from transfer_motion()",
     }
 
     def sample_videos_device(self, batch, n_samples=1, n_logged_vids=1, add_first_frame=False, use_keypoint_pokes=False):
@@ -611,6 +613,95 @@ class PokeMotionModel(nn.Module):
                     out = torch.empty((video.shape[0], n_samples) + tuple(video.shape[1:]), dtype=video.dtype, device=video.device)
                 out[:, i].copy_(video)                 # (a graph replay hands out its static buffer: copied before the next replay)
         return out
+
+    # ---- applications (second_stage_video.py:786-852, 948-1015): the tensors; writing mp4 / png files is left to the caller ------------
+    def _sample_video(self, X, poke, z):
+        if getattr(self, "_graph_sampling", False):
+            return self._sample_graphed(X, poke, z)
+        return self._sample_device(X, poke, z)
+
+    def _cut_augmentation(self, motion):
+        if self.augment_input:
+            motion = motion[:, :-self.config["architecture"]["augment_channels"]].contiguous()
+        return motion
+
+    def poke_simulator(self):
+        """The ``PokeSimulator`` of ``config['data']`` (the reference reads ``poke_size`` from its test data set, :794, :951)."""
+        if getattr(self, "_poke_simulator", None) is None:
+            from .data import PokeSimulator
+            self._poke_simulator = PokeSimulator(self.config["data"])
+        return self._poke_simulator
+
+    def transfer_motion(self, batch):
+        """Motion transfer, ``_test_transfer`` (second_stage_video.py:948-1015) up to the video writer: the residual r1 of clip 1 (``batch``)
+        under its own conditioning, replayed under the conditioning of clip 2 -- ``batch['nn'] = (X_2, flow_2, sample_ids2)`` -- whose
+        start frame takes the place of clip 1's while the poke stays clip 1's: cond_2 = conditioner(X_2[:, 0]) (through ``_adapt_cond`` when
+        configured) ++ poke_embedder(poke1 ++ X_2[:, 0]).  Returns device tensors: ``r1``, ``z_r1_cond2`` (r1 reversed under cond_2),
+        ``z_random_cond2`` (a fresh residual reversed under cond_2), ``vid_r1_c2`` and ``vid_random_cond2`` (both decoded on X_2[:, 0]).
+
+        Not computed, although the reference does: ``poke_2`` / ``poke_emb_2`` (:959-966, 980: clip 2's flow re-read at clip 1's centres,
+        ``PokeSimulator.stamp(centers, flow=flow_2)`` here), which never reach ``cond_2``, and ``r2`` (:1004), which only commented-out code
+        uses.  The random residual is ``torch.randn(r1.shape).type_as(r1)`` from the CPU generator, drawn after the forward pass -- the
+        convention of ``forward_sample``; the reference's ``randn_like`` on the device is not reproducible across devices.  With
+        ``augmented_input`` the noise channels are cut off before decoding, as in sampling."""
+        from . import _lib
+        _lib.require_gpu()
+        if not self.embed_poke_and_image:
+            # :975-981: poke1_src2 is only assigned under `if self.embed_poke_and_image` and read unconditionally
+            raise NotImplementedError("transfer_motion without poke_and_image: the reference's own _test_transfer fails with a NameError "
+                                      "(poke1_src2 is only defined when the poke embedder takes the poke AND the image, "
+                                      "second_stage_video.py:975-981): no behaviour to reproduce")
+        self.eval()
+        with torch.no_grad():
+            X_2 = batch["nn"][0]
+            poke1 = self._poke_of(batch)
+            z_1, cond_1 = self.make_flow_input(batch)
+            poke_emb_1, *_ = self.poke_embedder.encoder(torch.cat([poke1, X_2[:, 0]], dim=1))
+            if self.use_cond:
+                cond_2, *_ = self.conditioner.encoder(X_2[:, 0])
+                if self.adapt_cond_ssize:
+                    cond_2 = self._adapt_cond(cond_2)
+                cond_2 = torch.cat([cond_2, poke_emb_1], dim=1)
+            else:
+                cond_2 = poke_emb_1
+            r1, _ = self.flow(z_1, cond_1, reverse=False)
+            z_r1_cond2 = self.flow(r1, cond_2, reverse=True)
+            residual_sample = torch.randn(r1.shape).type_as(r1)
+            z_random_cond2 = self.flow(residual_sample, cond_2, reverse=True)
+            vid_r1_c2 = self.decode_first_stage(self._cut_augmentation(z_r1_cond2), X_2)
+            vid_random_cond2 = self.decode_first_stage(self._cut_augmentation(z_random_cond2), X_2)
+        return {"r1": r1, "z_r1_cond2": z_r1_cond2, "z_random_cond2": z_random_cond2, "vid_r1_c2": vid_r1_c2,
+                "vid_random_cond2": vid_random_cond2}
+
+    def control_sensitivity_samples(self, batch, n_pokes=None, u=None):
+        """The control-sensitivity study, ``_control_sensitivity`` (second_stage_video.py:786-852) up to the video writer: the batch's start
+        frames sampled under the batch's own poke (slot 0) and under ``n`` pokes at each sample's first centre that are re-aimed at a random
+        angle of the upper half plane, with the magnitude the flow has at a randomly chosen pixel above its mean amplitude
+        (``PokeSimulator.randomize_pokes``).  n defaults to ``testing.n_control_sensitivity_pokes``; u: fp32 [B, n, 2] uniforms, drawn on the
+        device when not given.  Returns ``(pokes [n + 1, B, 2, H, W], samples [B, n + 1, T, 3, H, W], picked int64 [B, n, 2], status)`` on the
+        device; sample k is ``forward_sample`` of the batch with ``batch['poke'] = pokes[k]``.  Draw order: the uniforms, then one latent
+        per poke (CPU generator).  ``batch`` is not modified (the reference overwrites ``batch['poke']``); samples without a candidate pixel
+        raise ``FlowError`` before anything is sampled."""
+        from . import _lib
+        _lib.require_gpu()
+        n = int(self.config["testing"]["n_control_sensitivity_pokes"] if n_pokes is None else n_pokes)
+        self.eval()
+        with torch.no_grad():
+            X = batch["images"]
+            poke0, centers = batch["poke"]
+            randomized, picked, status = self.poke_simulator().randomize_pokes(batch["flow"], centers, n, u=u, strict=True)
+            pokes = torch.cat([poke0.float()[None], randomized])
+            spatial = self.first_stage_config["architecture"]["min_spatial_size"]
+            samples = None
+            step = dict(batch)
+            for k in range(n + 1):
+                step["poke"] = pokes[k]
+                z = torch.randn((X.size(0), self.config["architecture"]["flow_in_channels"], spatial, spatial)).type_as(X).detach()
+                video = self._sample_video(X, self._poke_of(step), z)
+                if samples is None:
+                    samples = torch.empty((video.shape[0], n + 1) + tuple(video.shape[1:]), dtype=video.dtype, device=video.device)
+                samples[:, k].copy_(video)                 # (a graph replay hands out its static buffer: copied before the next replay)
+        return pokes, samples, picked, status
 
     def attach_metric_vgg(self, vgg=None, dtype="f32"):
         """The reference builds ``self.vggm = metric_vgg16()`` with torchvision's ImageNet weights (:155); here the extractor is attached

@@ -127,6 +127,22 @@ int ipoke_conv_acc_scratch_init(void* scratch, void* stream);
  * 3x3, padding 1, on the 8x8 latent). */
 int ipoke_conv3x3_skinny_splitk(int M, int Kc, int dtype);
 
+/* The conv2 and conv1 data gradients of a coupling net (NICEConvBlock, macow_utils.py:270-281) as ONE launch:
+ *   dp1 = (dp2 @ W2) * ELU'(h1)            `conv2`: the 1x1 convolution on dense rows with its weight read K-major (w_kmajor = 1, dact = h1,
+ *                                          C = dp1 in dtype), exactly the descriptor ipoke_conv_forward takes for it;
+ *   C1 += conv3x3^T(dp1, W1)               `conv1`: the 3x3 (padding 1) convolution on the 8x8 latent whose input A is conv2's C (same pointer,
+ *                                          row stride and column offset), Nout = cin <= 32 output columns, c_f32 = c_accumulate = 1 with
+ *                                          ldc / c_coff / c_cstride, and acc_scratch (required; ipoke_conv_acc_scratch_bytes).
+ * conv1->splitk is ignored: the hidden channels are always reduced in slices of 128 (one column tile of the GEMM each), summed in a
+ * fixed order by the workgroup that reaches a row tile last -- bit-reproducible, and bit-identical to the two ipoke_conv_forward
+ * launches when the second runs with splitk = hidden / 128.  Shapes the kernel does not take (ipoke_conv_pair_dgrad_applicable) are
+ * rejected with IPOKE_ERR_INVALID; callers issue the two launches there. */
+int ipoke_conv_pair_dgrad(const ipoke_conv_desc* conv2, const ipoke_conv_desc* conv1, int dtype, void* stream);
+/* Host-only: 1 when ipoke_conv_pair_dgrad takes M = 64*B rows, `hidden` channels, cin conditioning channels in `dtype` with an
+ * accumulation scratch of acc_scratch_bytes bytes: bf16, M a multiple of 64, hidden a multiple of 128 (>= 256), cin <= 32, one round of
+ * workgroups (ceil(M / 128) * hidden / 128 <= 256) and room for ceil(M / 128) * hidden / 128 slabs of 128 x 32 floats.  Else 0. */
+int ipoke_conv_pair_dgrad_applicable(int M, int hidden, int cin, int dtype, int64_t acc_scratch_bytes);
+
 /* Weight gradient: dW[n][tap*Kc + c] (+)= sum_m dY[m][n] * A[src(m,tap)][c].
  * dY is dtype [M][ldy]; A as in ipoke_conv_desc (fp32 or dtype).  Output fp32, written through a
  * (n, c, tap) stride triple so PyTorch's [out][in][k...] layout is produced directly. */

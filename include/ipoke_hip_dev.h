@@ -15,9 +15,10 @@ extern "C" {
 /* n back-to-back native launches of the same convolution (kernel timing without host round trips) */
 int ipoke_conv_forward_repeat(const ipoke_conv_desc* d, int dtype, int n, void* stream);
 /* Test hook: kernel-dispatch switch `name` ("c64": conv3x3_c64, "halo16": conv3x3_halo16) <- value (0 off, 1 the measured default
- * rule, 2 wherever the kernel can run; < 0: back to the default rule 1). */
+ * rule, 2 wherever the kernel can run; < 0: back to the default rule 1).  "nn128" (scripts/probe_pair_dgrad.py): 2 = the K-major GEMM
+ * (ipoke_conv_desc.w_kmajor) on its 128 x 128 tile whatever M, instead of the 80- / 160-row tiles the cost rule picks. */
 int ipoke_set_dispatch_override(const char* name, int value);
-/* Test hook: the kernel family the calling thread's last ipoke_conv_forward was dispatched to */
+/* Test hook: the kernel family the calling thread's last ipoke_conv_forward was dispatched to (ipoke_conv_pair_dgrad reports IPOKE_KERNEL_IGEMM) */
 enum { IPOKE_KERNEL_NONE = 0, IPOKE_KERNEL_IGEMM = 1, IPOKE_KERNEL_S8 = 2, IPOKE_KERNEL_HALO = 3, IPOKE_KERNEL_HALO16 = 4, IPOKE_KERNEL_C64 = 5, IPOKE_KERNEL_K8 = 6 };
 int ipoke_last_conv_kernel(void);
 /* Test hook: the weight-gradient kernel the calling thread's last ipoke_conv_wgrad / ipoke_conv_wgrad_batched was dispatched to
@@ -60,6 +61,11 @@ int ipoke_desc_sizes(int32_t* out, int n);
 /* Test hook: make the flow's next polled pass report a hand-off time-out (which = 0: the row-split unit scratch, 1: the fused
  * conv3 + coupling scratch) -- exercises the engine's IPOKE_ERR_STATE + scratch re-initialisation path (ipoke_flow_handoff_timeouts) */
 int ipoke_flow_test_inject_timeout(ipoke_flow* f, int which, void* stream);
+
+/* Test hook: on != 0 makes the flow's backward pass issue the conv2 and conv1 data gradients of every coupling net as two launches
+ * even where ipoke_conv_pair_dgrad applies, the second with that kernel's slices (splitk = hidden / 128): every gradient must come out
+ * bit-identical (the parity test of the fused launch); 0: back to the default.  Drops the handle's captured graphs. */
+int ipoke_flow_test_split_pair_dgrad(ipoke_flow* f, int on);
 
 /* Test hook: forward unroll of the ConvGRU as one launch (1), as launches per phase (0), or the IPOKE_GRU_FUSED environment default (< 0) */
 int ipoke_gru_set_fused(int mode);

@@ -129,6 +129,7 @@ struct ipoke_flow {
   // event has completed reads the words: non-zero -> the scratches are re-initialised and the call fails with IPOKE_ERR_STATE.
   // scratch of the deterministic split-K accumulation of the conv1 data gradients (ipoke_conv_desc.acc_scratch; the chain's stream only)
   void* d_acc = nullptr; int64_t acc_bytes = 0;
+  bool split_pair_dgrad = false;      // test hook (ipoke_flow_test_split_pair_dgrad): conv2's and conv1's data gradients as two launches
   unsigned* h_tmo = nullptr; hipEvent_t pass_ev = nullptr; hipStream_t pass_stream = nullptr; bool pass_recorded = false, pass_unchecked = false;
   int64_t xchg_bytes = 0;
   // every masked-conv layer is differentiated inside a fused MaCowUnit launch, which also writes the layer's input in the matrix
@@ -1251,6 +1252,13 @@ extern "C" int ipoke_flow_test_inject_timeout(ipoke_flow* f, int which, void* st
   IPK_LAUNCH_CHECK();
   return IPOKE_OK;
 }
+/* Test hook (include/ipoke_hip_dev.h): the two-launch form of the coupling nets' conv2 + conv1 data gradients */
+extern "C" int ipoke_flow_test_split_pair_dgrad(ipoke_flow* f, int on) {
+  IPK_REQUIRE(f != nullptr, "null flow handle");
+  f->split_pair_dgrad = on != 0;
+  drop_graphs(f);      // captured passes hold the other form
+  return IPOKE_OK;
+}
 /* Synchronising query: waits for the last pass of this flow and writes the hand-off time-out counts since the scratches were last
  * (re-)initialised: out[0] row-split MaCowUnit launches, out[1] fused conv3 + coupling launches.  Returns IPOKE_OK; non-zero counts
  * mean that a pass finished on garbage (the next entry point fails with IPOKE_ERR_STATE and re-initialises the scratches). */
@@ -1882,22 +1890,32 @@ static int run_backward(ipoke_flow* f, const float* params, const int32_t* perm,
         d.W = l.sh(op.sh_c3t); d.ldw = 9 * op.Kc3; d.Nout = hid; d.dact = h2; d.ld_dact = op.hidK; d.dact_act = IPOKE_ACT_ELU;
         d.C = dp2; d.ldc = hid;
         rc = ipoke_conv_forward(&d, l.dtype, l.stream()); if (rc) return rc;
-        // conv2 data gradient, times ELU'(h1)
+        // conv2 data gradient, times ELU'(h1), and conv1 data gradient accumulated into the conditioning channels
+        ipoke_conv_desc d1;
         set_conv8(d, l.B, 1, 0);
         set_a_dense(d, dp2, hid, hid);
         if (f->c2_straight) { d.W = l.sh(op.sh_c2); d.w_kmajor = 1; }      // W2[out][in] read K-major: no transposed copy exists
         else d.W = l.sh(op.sh_c2t);
         d.ldw = hid; d.Nout = hid; d.dact = h1; d.ld_dact = hid; d.dact_act = IPOKE_ACT_ELU;
         d.C = dp1; d.ldc = hid;
-        rc = ipoke_conv_forward(&d, l.dtype, l.stream()); if (rc) return rc;
-        // conv1 data gradient accumulated into the conditioning channels
-        set_conv8(d, l.B, 3, 1); d.transposed = 1;
-        set_a_dense(d, dp1, hid, hid);
-        d.W = l.sh(op.sh_c1t); d.ldw = 9 * hid; d.Nout = op.cin; d.C = gout; d.c_f32 = 1; d.c_accumulate = 1; d.ldc = l.ld;
-        d.c_coff = op.z_off; d.c_cstride = op.z_stride; d.splitk = nice_splitk(l);
+        set_conv8(d1, l.B, 3, 1); d1.transposed = 1;
+        set_a_dense(d1, dp1, hid, hid);
+        d1.W = l.sh(op.sh_c1t); d1.ldw = 9 * hid; d1.Nout = op.cin; d1.C = gout; d1.c_f32 = 1; d1.c_accumulate = 1; d1.ldc = l.ld;
+        d1.c_coff = op.z_off; d1.c_cstride = op.z_stride; d1.splitk = nice_splitk(l);
         // the K slices meet in the engine's scratch and are summed in a fixed order (bit-reproducible steps); sub-batch lanes
         // (developer switch) run several of these launches at once and keep the atomic form
-        if (lanes.size() == 1 && op.cin <= 64) { d.acc_scratch = f->d_acc; d.acc_scratch_bytes = f->acc_bytes; }
+        if (lanes.size() == 1 && op.cin <= 64) { d1.acc_scratch = f->d_acc; d1.acc_scratch_bytes = f->acc_bytes; }
+        // one launch where the pair kernel takes the shape (c2: B <= 32 at hidden 2048, cin <= 32): conv1's slices are the GEMM's column tiles
+        if (lanes.size() == 1 && f->c2_straight && f->d_acc && !f->cfg.condition_nice &&
+            ipoke_conv_pair_dgrad_applicable((int)l.M, hid, op.cin, l.dtype, f->acc_bytes)) {
+          if (!f->split_pair_dgrad) {
+            rc = ipoke_conv_pair_dgrad(&d, &d1, l.dtype, l.stream()); if (rc) return rc;
+            continue;
+          }
+          d1.splitk = hid / 128;      // test hook: the two launches with the pair kernel's slices, i.e. the same sums in the same order
+        }
+        rc = ipoke_conv_forward(&d, l.dtype, l.stream()); if (rc) return rc;
+        d = d1;
         rc = ipoke_conv_forward(&d, l.dtype, l.stream()); if (rc) return rc;
       }
     }

@@ -1203,6 +1203,10 @@ static void pick_xcd_map(NtParams& p) {
 // (two hand-over rounds) before the epilogue.
 // Split-K is over channel chunks (blockIdx.y); the epilogue is nt_epilogue (partials / atomics / dense outputs).
 //
+// igemm_nn_pair_kernel (further down) carries a COPY of this body's K-block loop and of the four K groups' hand-over, with the input
+// image taken from LDS: the two must keep the same K-block order (chunk-major, nine taps inside, group kq takes every fourth block) and
+// the same hand-over sums -- tests/test_pair_dgrad_gpu.py compares them bit for bit and fails when they diverge.
+//
 // NSPLIT > 0 (conv3x3_s8_coupling_kernel): the K splits of a row tile meet INSIDE the launch and the coupling transform the
 // convolution feeds (affine_fwd / affine_actnorm_fwd / affine_inv of elementwise.hip) runs in the same launch -- see the tail
 // of the body.
@@ -2556,7 +2560,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // Dispatch switches of the two persistent / wide 3 x 3 kernels: 0 off, 1 (default) where measured faster, 2 wherever the kernel can run.
 // The parity tests move them at run time through ipoke_set_dispatch_override (atomics because launches on distinct streams may come
 // from distinct threads).
-static std::atomic<int> g_c64_mode{1}, g_halo16_mode{1};
+static std::atomic<int> g_c64_mode{1}, g_halo16_mode{1}, g_nn128_mode{1};
 
 static bool c64_applicable(const NtParams& p) {
   // mode 1 (default): at >= 512 patches (two per CU)
@@ -3247,9 +3251,366 @@ static int dispatch_nn(NtParams& p, hipStream_t s) {
   int best = 128; long best_cost = ((long)ceil_div(M, 128) * tn128 + 255) / 256 * 128;
   if (M % 160 == 0) { const long c = ((long)(M / 160) * tn128 + 255) / 256 * 160; if (c <= best_cost) { best = 160; best_cost = c; } }
   if (M % 80 == 0) { const long c = ((long)(M / 80) * tn128 + 255) / 256 * 80; if (c < best_cost) { best = 80; best_cost = c; } }
+  // developer hook (ipoke_set_dispatch_override "nn128" = 2, scripts/probe_pair_dgrad.py): EVERY K-major GEMM of the process on the 128 x 128 tile
+  if (g_nn128_mode.load(std::memory_order_relaxed) == 2) best = 128;
   if (best == 80) return launch_nn_glds<1, 4, 5, 3, 2>(p, s);       // 80 x 128: two K halves x 4 waves of 80 x 32 (the c2 shape: 256 workgroups)
   if (best == 160) return launch_nn_glds<2, 4, 5, 3, 1>(p, s);      // 160 x 128, 8 waves of 80 x 32
   return launch_nn_glds<2, 4, 4, 3, 1>(p, s);                       // 128 x 128
+}
+
+// =============================================================================================
+// The conv2 AND conv1 data gradients of a coupling net as one launch (ipoke_conv_pair_dgrad).
+// conv1's data gradient -- the skinny transposed 3x3 convolution conv3x3_s8n32_kernel runs as 16 K slices of two 64-channel chunks --
+// is a split-K reduction over the hidden channels, and a slice of 128 channels is exactly one 128-column N tile of conv2's GEMM.  A
+// workgroup that owns the [128 rows (two samples) x 128 columns] tile of dp1 therefore holds, after its epilogue, the whole input
+// image of one slice: it leaves the bf16 values in LDS as the two chunk images of conv3x3_s8_body (same swizzle, same zero row), runs
+// that slice's 18 K-blocks against the matching slab of the conv1 filter operand and accumulates through the deterministic scratch
+// path of nt_epilogue (slab = N tile, last arriver of a row tile sums in the fixed order).  No spin, no flag: the ticket is the only
+// cross-workgroup mechanism.  Per coupling one chain launch, the L2 -> LDS re-read of dp1 and the skinny kernel's ramp disappear.
+// The GEMM main loop is igemm_nn_glds_kernel<2, 4, 4, 3, 1>'s; the K-block loop, the hand-over of the four K groups and the
+// accumulation are conv3x3_s8_body<0, 2>'s (a copy with the input image taken from LDS: the shipped skinny kernels keep their code),
+// in the same order -- the results equal the two launches bit for bit when the skinny one runs hidden / 128 slices.
+struct PairEpi {
+  const void* W1; int ldw1, cin, transposed;      // conv1's filter operand [cin][9 * hidden] (tap-major), its output columns
+  float* C2; long ldc2; int c_coff2, c_cstride2;  // the fp32 accumulation target
+  unsigned* acc_cnt; float* acc_part;             // ipoke_conv_desc.acc_scratch
+};
+// LDS: GEMM ring [0, 96 KB) -- afterwards the fp32 staging tile [0, 66 KB) and the two chunk images + zero row [66 KB, 98.25 KB) --,
+// the filter ring (12 K-blocks of 32 rows) at 100 KB and 1 KB per wave for padding DMAs at 148 KB
+static constexpr int kPairImg = 128 * (128 * 4 + 16), kPairZrow = kPairImg + 2 * 128 * 128, kPairRing = 100 * 1024,
+                     kPairDummy = kPairRing + 12 * 32 * 128;
+static constexpr size_t kLdsPair = kPairDummy + 8 * 1024;
+static_assert(kPairZrow + 256 <= kPairRing && 3 * (128 * 128 + 64 * 256) <= kPairRing, "LDS regions of igemm_nn_pair_kernel overlap");
+
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void igemm_nn_pair_kernel(const NtParams p, const PairEpi e) {
+  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)(sizeof(NtParams) + sizeof(PairEpi)) < 512 ? (int)(sizeof(NtParams) + sizeof(PairEpi)) : 512>();
+  typedef bf16_t T;
+  typedef typename ET<T>::frag frag_t;
+  typedef typename Pack4<T>::type pack_t;
+  typedef __attribute__((address_space(3))) void lds_void;
+  typedef const __attribute__((address_space(1))) void glb_void;
+  constexpr int WM = 2, WN = 4, MREP = 4, NREP = 2, NSTAGE = 3, NTHR = 512, NWAVE = 8, BM = 128, BN = 128;
+  constexpr int A_IT = BM * 8 / NTHR, B_IT = 1024 / NTHR, L = A_IT + B_IT;
+  constexpr int SUB = BM * 128 + 64 * 256;
+  constexpr int EP = BN * 4 + 16;
+  constexpr int R = 12, WSLOT = 32 * 128, WJ = 2, ABUF = BM * 128;      // the filter ring of conv3x3_s8_body<0, 2>
+  constexpr int NKB = 18, NROUNDS = 5;                                  // 2 chunks x 9 taps, four K-blocks per round
+  constexpr unsigned kInvalid = 0xffffffffu;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  unsigned char* img = smem + kPairImg;
+  unsigned char* zrow = smem + kPairZrow;
+  unsigned char* ring = smem + kPairRing;
+  unsigned char* dummy = smem + kPairDummy;
+  if (p.prio == 1) __builtin_amdgcn_s_setprio(1); else if (p.prio == 2) __builtin_amdgcn_s_setprio(2); else if (p.prio == 3) __builtin_amdgcn_s_setprio(3);
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave / WN, wn = wave % WN;
+  const GeomDev& g = p.g;
+  int tm, tn;
+  {
+    const int bid = blockIdx.x;
+    if (p.xa > 0) {
+      const int xcd = bid & 7, q = bid >> 3;
+      const FDiv fxa(p.xa), fxb(p.xb);                   // (powers of two: pick_xcd_map)
+      const int sub_m = fxa.div(p.tiles_m), sub_n = fxb.div(p.tiles_n);
+      const FDiv fsm(sub_m);
+      tm = fxa.mod(xcd) * sub_m + fsm.mod(q);
+      tn = fxa.div(xcd) * sub_n + fsm.div(q);
+    } else {
+      const FDiv ftm(p.tiles_m);
+      tm = ftm.mod(bid); tn = ftm.div(bid);
+    }
+  }
+  const int m0 = tm * BM, n0 = tn * BN;
+  const int hid = p.Nout;                                // conv1's input channels = the GEMM's columns
+  const T* zero = reinterpret_cast<const T*>(g_zero_chunk);
+  if (tid < 16) reinterpret_cast<f32x4*>(zrow)[tid] = f32x4{0.f, 0.f, 0.f, 0.f};      // (outside every ring: first read after many barriers)
+
+  // ---- conv1 filter slab of this slice: wave w brings rows 16 * (w >> 2) .. + 15 (2 instructions of 8 rows) of K-block 4r + (w & 3);
+  // the first two rounds are requested NOW (they are the oldest requests: the GEMM loop's counted waits cover them)
+  const T* W1 = reinterpret_cast<const T*>(e.W1);
+  unsigned w_src[WJ];
+#pragma unroll
+  for (int j = 0; j < WJ; ++j) {
+    const int n = 8 * WJ * (wave >> 2) + 8 * j + (lane >> 3), pos = lane & 7;
+    w_src[j] = n < e.cin ? (unsigned)((long)n * e.ldw1 + n0 + ((pos ^ ((n >> 1) & 7)) * 8)) : kInvalid;
+  }
+  int wi_g = wave & 3, wi_c = 0, wi_t = wave & 3;          // K-block index / (chunk, tap) of this wave's next filter request
+  auto issue_w = [&]() {
+    const bool in = wi_g < NKB;
+#pragma unroll
+    for (int j = 0; j < WJ; ++j) {
+      const bool real = in && w_src[j] != kInvalid;
+      const T* src = real ? W1 + w_src[j] + (long)wi_t * hid + wi_c * 64 : zero;
+      unsigned char* dst = in ? ring + (wi_g % R) * WSLOT + (WJ * (wave >> 2) + j) * 1024 : dummy + wave * 1024;
+      __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)dst, 16, 0, 0);
+    }
+    wi_g += 4; wi_t += 4;
+    if (wi_t >= 9) { wi_t -= 9; ++wi_c; }
+  };
+  issue_w(); issue_w();
+
+  // ---- conv2 data gradient: the main loop of igemm_nn_glds_kernel<2, 4, 4, 3, 1>
+  const int nkb = (p.Ktot + 63) >> 6;
+  unsigned a_off[A_IT];
+#pragma unroll
+  for (int i = 0; i < A_IT; ++i) {
+    const int ch = tid + NTHR * i, row = ch >> 3, pos = ch & 7;
+    a_off[i] = (m0 + row < g.M) ? (unsigned)((long)(m0 + row) * p.a_sw + p.a_coff + ((pos ^ ((row >> 1) & 7)) * 8)) : kInvalid;
+  }
+  unsigned b_off[B_IT]; int b_row[B_IT];
+#pragma unroll
+  for (int i = 0; i < B_IT; ++i) {
+    const int row = 4 * (wave + NWAVE * i) + (lane >> 4), col = n0 + (((lane & 15) ^ tn_swz(row)) * 8);
+    b_row[i] = row;
+    b_off[i] = col < p.Nout ? (unsigned)((long)row * p.ldw + col) : kInvalid;
+  }
+  const T* Abase = reinterpret_cast<const T*>(p.A);
+  const T* Wbase = reinterpret_cast<const T*>(p.W);
+  int kb_issue = 0;
+  auto issue_slot = [&](int slot) {
+    unsigned char* sa = smem + slot * SUB;
+    const bool real = kb_issue < nkb;
+#pragma unroll
+    for (int i = 0; i < A_IT; ++i) {
+      const T* src = (real && a_off[i] != kInvalid) ? Abase + a_off[i] : zero;
+      unsigned char* dst = real ? sa + (wave * 64 + NTHR * i) * 16 : dummy + wave * 1024;
+      __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)dst, 16, 0, 0);
+      if (a_off[i] != kInvalid) a_off[i] += 64;
+    }
+#pragma unroll
+    for (int i = 0; i < B_IT; ++i) {
+      const T* src = (real && b_off[i] != kInvalid && kb_issue * 64 + b_row[i] < p.Ktot) ? Wbase + b_off[i] : zero;
+      unsigned char* dst = real ? sa + BM * 128 + (wave + NWAVE * i) * 1024 : dummy + wave * 1024;
+      __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)dst, 16, 0, 0);
+      if (b_off[i] != kInvalid) b_off[i] += (unsigned)(64 * p.ldw);
+    }
+    ++kb_issue;
+  };
+  f32x4 acc[MREP][NREP];
+#pragma unroll
+  for (int i = 0; i < MREP; ++i)
+#pragma unroll
+    for (int j = 0; j < NREP; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  {
+    int a_rd[MREP][2];
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+      const int q = s2 * 4 + (lane >> 4);
+#pragma unroll
+      for (int i = 0; i < MREP; ++i) {
+        const int row = wm * MREP * 16 + i * 16 + (lane & 15);
+        a_rd[i][s2] = row * 128 + ((q ^ ((row >> 1) & 7)) * 16);
+      }
+    }
+    const int i16 = lane & 15, grp = lane >> 4;
+    const int rrow = 8 * grp + (i16 >> 2);
+    const int hsw = tn_swz(rrow);
+    const unsigned lds0 = (unsigned)(unsigned long)(__attribute__((address_space(3))) unsigned char*)smem;
+    unsigned b_rd[NREP];
+#pragma unroll
+    for (int j = 0; j < NREP; ++j) {
+      const int col = (wn * NREP + j) * 16 + 4 * (i16 & 3);
+      b_rd[j] = lds0 + (unsigned)(BM * 128 + rrow * 256 + (((col >> 3) ^ hsw) * 16) + ((col >> 2) & 1) * 8);
+    }
+    auto read_b = [&](frag_t (&fb)[NREP], unsigned sb, int kstep) {
+#pragma unroll
+      for (int j = 0; j < NREP; ++j) {
+        const unsigned a = b_rd[j] + sb + (unsigned)(kstep * 32 * 256);
+        const tn_tr4_t lo = tn_ds_tr<0>(a), hi = tn_ds_tr<4 * 256>(a);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { fb[j][q] = lo[q]; fb[j][4 + q] = hi[q]; }
+      }
+    };
+    auto wait_b = [&](frag_t (&fb)[NREP]) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fb[0]), "+v"(fb[1])::"memory"); };
+#pragma unroll
+    for (int s2 = 0; s2 < NSTAGE - 1; ++s2) issue_slot(s2);
+    int slot = 0;
+    for (int kb = 0; kb < nkb; ++kb) {
+      wait_vmcnt<(NSTAGE - 2) * L>();
+      __builtin_amdgcn_s_barrier();
+      issue_slot((slot + NSTAGE - 1) % NSTAGE);
+      const unsigned char* base = smem + slot * SUB;
+      const unsigned sb = (unsigned)(slot * SUB);
+      slot = (slot + 1) % NSTAGE;
+      frag_t fa[2][MREP], fb[2][NREP];
+      read_b(fb[0], sb, 0);
+#pragma unroll
+      for (int i = 0; i < MREP; ++i) fa[0][i] = *reinterpret_cast<const frag_t*>(base + a_rd[i][0]);
+      wait_b(fb[0]);
+      read_b(fb[1], sb, 1);
+#pragma unroll
+      for (int i = 0; i < MREP; ++i) fa[1][i] = *reinterpret_cast<const frag_t*>(base + a_rd[i][1]);
+#pragma unroll
+      for (int i = 0; i < MREP; ++i)
+#pragma unroll
+        for (int j = 0; j < NREP; ++j) GEMM_MMA(fa[0][i], fb[0][j], acc[i][j]);
+      wait_b(fb[1]);
+#pragma unroll
+      for (int i = 0; i < MREP; ++i)
+#pragma unroll
+        for (int j = 0; j < NREP; ++j) GEMM_MMA(fa[1][i], fb[1][j], acc[i][j]);
+    }
+  }
+  wait_vmcnt<0>();
+
+  // ---- dp1 = bf16(acc * ELU'(h1)): the arithmetic of nt_epilogue's dense path.  A thread owns one 4-column group in 8 rows; the values
+  // go into the chunk images (column c of the tile = channel c & 63 of chunk c >> 6, 16-byte units swizzled by (row >> 1) & 7) and
+  // stay in registers for the store to C, which is issued behind the convolution's K loop (nothing in that loop waits for it)
+  constexpr int G4F = BN / 4, ITER = BM * G4F / NTHR, RSTEP = NTHR / G4F;
+  const int c4 = tid % G4F, r0 = tid / G4F;
+  const bool mask = p.dact != nullptr;
+  pack_t dy[ITER], o[ITER];
+#pragma unroll
+  for (int k = 0; k < ITER; ++k) dy[k] = pack_t{};
+  if (mask) {      // (rows beyond M: the index is clamped, no branch around a load; their sums are zero)
+#pragma unroll
+    for (int k = 0; k < ITER; ++k) {
+      const int m = min(m0 + r0 + k * RSTEP, g.M - 1);
+      dy[k] = *reinterpret_cast<const pack_t*>(reinterpret_cast<const T*>(p.dact) + (long)m * p.ld_dact + n0 + 4 * c4);
+    }
+  }
+  auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+  lds_barrier();                     // the GEMM ring is dead
+  {
+    unsigned char* base = smem + (wm * MREP * 16 + (lane & 15)) * EP + (wn * NREP * 16 + (lane >> 4) * 4) * 4;
+#pragma unroll
+    for (int i = 0; i < MREP; ++i)
+#pragma unroll
+      for (int j = 0; j < NREP; ++j) *reinterpret_cast<f32x4*>(base + i * 16 * EP + j * 64) = acc[i][j];
+  }
+  __syncthreads();                   // (also: the derivative-mask loads have landed)
+  {
+    const unsigned char* sp = smem + r0 * EP + c4 * 16;
+    const int pos = (c4 & 15) >> 1;
+#pragma unroll
+    for (int k = 0; k < ITER; ++k) {
+      const int row = r0 + k * RSTEP;
+      const f32x4 v = *reinterpret_cast<const f32x4*>(sp + k * RSTEP * EP);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float x = v[r];
+        const float y = ET<T>::to_f32(dy[k][r]);
+        x *= (mask && y <= 0.f) ? y + 1.f : 1.f;
+        o[k][r] = ET<T>::from_f32(m0 + row < g.M ? x : 0.f);
+      }
+      *reinterpret_cast<pack_t*>(img + (c4 >> 4) * ABUF + row * 128 + ((pos ^ ((row >> 1) & 7)) * 16) + (c4 & 1) * 8) = o[k];
+    }
+  }
+
+  // ---- conv1 data gradient of this slice: the K-block loop of conv3x3_s8_body<0, 2> (2 row halves x 4 K groups, chunk-major, nine
+  // taps inside) on the images above
+  constexpr int CREP = 2;            // 32 output columns
+  const int mh = wave & 1, kq = wave >> 1;
+  const int sgn = e.transposed ? -1 : 1;
+  unsigned vmask[MREP];
+#pragma unroll
+  for (int i = 0; i < MREP; ++i) {
+    const int r = i * 16 + (lane & 15);
+    const int y = (r >> 3) & 7, x = r & 7;
+    unsigned vm = 0;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      const int yy = y + sgn * (t / 3 - 1), xx = x + sgn * (t % 3 - 1);
+      if ((unsigned)yy < 8u && (unsigned)xx < 8u) vm |= 1u << t;
+    }
+    vmask[i] = vm;
+  }
+  const int qlo = lane >> 4;
+  int w_rd[CREP];
+#pragma unroll
+  for (int j = 0; j < CREP; ++j) {
+    const int n = j * 16 + (lane & 15);
+    w_rd[j] = n * 128 + ((qlo ^ ((n >> 1) & 7)) * 16);
+  }
+  f32x4 acc2[MREP][CREP];
+#pragma unroll
+  for (int i = 0; i < MREP; ++i)
+#pragma unroll
+    for (int j = 0; j < CREP; ++j) acc2[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  int gk = kq, ci = 0, t = kq;
+  for (int r = 0; r < NROUNDS; ++r) {
+    wait_vmcnt<WJ>();                // everything but this wave's share of round r + 1 has landed
+    lds_barrier();                   // (round 0: the images are complete)
+    issue_w();                       // round r + 2 into the slots of round r - 1
+    if (gk < NKB) {
+      const unsigned char* ab = img + ci * ABUF + mh * 64 * 128;
+      const unsigned char* wb = ring + (gk % R) * WSLOT;
+      const int th = t / 3, tw = t - 3 * th;
+      const int shift = sgn * ((th - 1) * 8 + (tw - 1));
+      const unsigned char* arow[MREP]; int aswz[MREP];
+#pragma unroll
+      for (int i = 0; i < MREP; ++i) {
+        const bool ok = (vmask[i] >> t) & 1u;
+        const int sr = i * 16 + (lane & 15) + shift;
+        arow[i] = ok ? ab + sr * 128 : zrow;
+        aswz[i] = ok ? (sr >> 1) & 7 : 0;
+      }
+      frag_t fa[2][MREP], fb[2][CREP];
+#pragma unroll
+      for (int hs = 0; hs < 2; ++hs) {
+#pragma unroll
+        for (int i = 0; i < MREP; ++i) fa[hs][i] = *reinterpret_cast<const frag_t*>(arow[i] + (((hs * 4 + qlo) ^ aswz[i]) * 16));
+#pragma unroll
+        for (int j = 0; j < CREP; ++j) fb[hs][j] = *reinterpret_cast<const frag_t*>(wb + (w_rd[j] ^ (hs * 64)));
+      }
+#pragma unroll
+      for (int hs = 0; hs < 2; ++hs)
+#pragma unroll
+        for (int i = 0; i < MREP; ++i)
+#pragma unroll
+          for (int j = 0; j < CREP; ++j) GEMM_MMA(fa[hs][i], fb[hs][j], acc2[i][j]);
+      // (issue order as in conv3x3_s8_body: the first half-step's fragments, then one read of the second per MFMA of the first)
+      constexpr int NF = MREP + CREP, NM = MREP * CREP, PER = NM / NF;
+      __builtin_amdgcn_sched_group_barrier(0x100, NF, 0);
+#pragma unroll
+      for (int f = 0; f < NF; ++f) {
+        __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      }
+      __builtin_amdgcn_sched_group_barrier(0x008, 2 * NM - NF * PER, 0);
+    }
+    gk += 4; t += 4;
+    if (t >= 9) { t -= 9; ++ci; }
+  }
+  wait_vmcnt<0>();
+  if (c4 * 4 + n0 < p.Nout) {        // dp1 to C (the conv1 weight gradient reads it)
+    T* Cp = reinterpret_cast<T*>(p.C) + (long)(m0 + r0) * p.ldc + p.c_coff + n0 + 4 * c4;
+#pragma unroll
+    for (int k = 0; k < ITER; ++k)
+      if (m0 + r0 + k * RSTEP < g.M) *reinterpret_cast<pack_t*>(Cp + (long)k * RSTEP * p.ldc) = o[k];
+  }
+  // the four K groups meet: groups 2, 3 hand over to groups 0, 1, then group 1 to group 0 (nt_epilogue's staging layout)
+  constexpr int EP2 = 16 * CREP * 4 + 16;
+  {
+    unsigned char* st = smem + (mh * MREP * 16 + (lane & 15)) * EP2 + (lane >> 4) * 16;
+    lds_barrier();                   // the ring and the images are dead
+#pragma unroll
+    for (int round = 0; round < 2; ++round) {
+      const int give_lo = round == 0 ? 2 : 1, take_hi = round == 0 ? 2 : 1;
+      if (kq >= give_lo && kq < 2 * give_lo) {
+        unsigned char* d = st + (kq - give_lo) * BM * EP2;
+#pragma unroll
+        for (int i = 0; i < MREP; ++i)
+#pragma unroll
+          for (int j = 0; j < CREP; ++j) *reinterpret_cast<f32x4*>(d + i * 16 * EP2 + j * 64) = acc2[i][j];
+      }
+      lds_barrier();
+      if (kq < take_hi) {
+        const unsigned char* d = st + kq * BM * EP2;
+#pragma unroll
+        for (int i = 0; i < MREP; ++i)
+#pragma unroll
+          for (int j = 0; j < CREP; ++j) acc2[i][j] += *reinterpret_cast<const f32x4*>(d + i * 16 * EP2 + j * 64);
+      }
+      if (round == 0) lds_barrier();
+    }
+  }
+  // slab [row tile][N tile], ticket, fixed-order sum by the last arriver, one read-modify-write into C2: nt_epilogue's DET branch
+  NtParams q = p;
+  q.splitk = p.tiles_n; q.tiles_n = 1; q.c_acc = 1; q.c_f32 = 1; q.acc_cnt = e.acc_cnt; q.acc_part = e.acc_part;
+  q.C = e.C2; q.ldc = e.ldc2; q.c_coff = e.c_coff2; q.c_cstride = e.c_cstride2; q.Nout = e.cin;
+  nt_epilogue<T, 2, 1, MREP, CREP, NTHR, true>(q, acc2, smem, m0, 0, mh, 0, tn, kq == 0);
 }
 
 // RM = reduction rows per ring slot (64).
@@ -4138,11 +4499,11 @@ extern "C" void ipoke_gemm_set_stamps(long long* base) { g_gemm_stamps = base; }
 #endif
 
 /* Test hook: moves a kernel-dispatch switch at run time ("c64" / "halo16": 0 off, 1 default rule, 2 wherever the kernel can run;
- * value < 0 goes back to the default rule 1). */
+ * "nn128": 2 = the K-major GEMM on its 128 x 128 tile at any M; value < 0 goes back to the default rule 1). */
 extern "C" int ipoke_set_dispatch_override(const char* name, int value) {
   IPK_REQUIRE(name != nullptr && value <= 2, "bad arguments");
-  std::atomic<int>* slot = !strcmp(name, "c64") ? &g_c64_mode : (!strcmp(name, "halo16") ? &g_halo16_mode : nullptr);
-  IPK_REQUIRE(slot != nullptr, "unknown dispatch switch (c64 | halo16)");
+  std::atomic<int>* slot = !strcmp(name, "c64") ? &g_c64_mode : (!strcmp(name, "halo16") ? &g_halo16_mode : (!strcmp(name, "nn128") ? &g_nn128_mode : nullptr));
+  IPK_REQUIRE(slot != nullptr, "unknown dispatch switch (c64 | halo16 | nn128)");
   slot->store(value < 0 ? 1 : value, std::memory_order_relaxed);
   return IPOKE_OK;
 }
@@ -4250,6 +4611,67 @@ extern "C" int ipoke_conv_forward(const ipoke_conv_desc* d, int dtype, void* str
     ts.annotate(square ? 0 : IPOKE_TAG_CONV_BASE + g_last_kernel, flops, bytes);
   }
   return rc;
+}
+
+extern "C" int ipoke_conv_pair_dgrad_applicable(int M, int hidden, int cin, int dtype, int64_t acc_scratch_bytes) {
+  if (dtype != IPOKE_BF16 || M < 64 || M % 64 != 0 || hidden < 256 || hidden % 128 != 0 || cin < 1 || cin > 32) return 0;
+  const long tiles = (long)ceil_div(M, 128) * (hidden / 128);
+  if (tiles > 256) return 0;                               // one round of workgroups
+  return acc_scratch_bytes >= kAccCounterBytes + tiles * 128 * 32 * 4 ? 1 : 0;
+}
+
+extern "C" int ipoke_conv_pair_dgrad(const ipoke_conv_desc* conv2, const ipoke_conv_desc* conv1, int dtype, void* stream) {
+  IPK_REQUIRE(conv2 != nullptr && conv1 != nullptr, "null descriptor");
+  IPK_REQUIRE(dtype == IPOKE_BF16, "the fused data gradients are bf16 only");
+  NtParams p, p1;
+  int rc = conv_params(p, conv2, dtype); if (rc) return rc;
+  rc = conv_params(p1, conv1, dtype); if (rc) return rc;
+  const GeomDev& g = p.g; const GeomDev& g1 = p1.g;
+  IPK_REQUIRE(conv2->w_kmajor && g.taps == 1 && !g.transposed && g.sd == 1 && g.sh == 1 && g.sw == 1 && g.pd == 0 && g.ph == 0 && g.pw == 0 &&
+              !p.a_f32 && p.Kc == p.Kc_real && p.Kc % 64 == 0 && (p.a_coff & 7) == 0 && (p.a_sw & 7) == 0 && (p.ldw & 7) == 0 &&
+              p.ldw >= p.Nout && p.splitk == 1 && !p.c_scatter && p.a_sh == (long)g.Wi * p.a_sw && p.a_sn == (long)g.Hi * g.Wi * p.a_sw &&
+              (long)g.M * p.a_sw + p.Kc < (1L << 31) && (long)p.Ktot * p.ldw < (1L << 31),
+              "conv2: K-major weights, 1x1 kernel over dense bf16 channels-last rows, K a multiple of 64");
+  IPK_REQUIRE(!p.bias && p.act == IPOKE_ACT_NONE && !p.c_f32 && !p.row_scale && ((p.ldc | p.c_coff) & 3) == 0 && p.ldc >= p.c_coff + p.Nout &&
+              (!p.dact || ((p.ld_dact & 3) == 0 && p.dact_act == IPOKE_ACT_ELU && p.ld_dact >= p.Nout)) &&
+              (long)g.M * p.ldc < (1L << 31) && (long)g.M * p.ld_dact < (1L << 31),
+              "conv2: dense dtype output, no bias / activation, an ELU derivative mask at most");
+  IPK_REQUIRE(!p1.c_scatter && !p1.a_f32 && g1.taps == 9 && g1.khw == 9 && g1.kw == 3 && g1.Di == 1 && g1.Hi == 8 && g1.Wi == 8 &&
+              g1.lDo == 0 && g1.lHo == 3 && g1.lWo == 3 && g1.sd == 1 && g1.sh == 1 && g1.sw == 1 && g1.pd == 0 && g1.ph == 1 && g1.pw == 1 &&
+              g1.M == g.M && p1.Kc == p.Nout && p1.Kc_real == p1.Kc && p1.ldw >= p1.Ktot && (long)p1.Nout * p1.ldw < (1L << 31),
+              "conv1: 3x3 kernel, padding 1, on the 8x8 latent over conv2's output channels");
+  IPK_REQUIRE(p1.A == p.C && p1.a_coff == p.c_coff && p1.a_sw == p.ldc && p1.a_sh == 8 * p.ldc && p1.a_sn == 64 * p.ldc,
+              "conv1 reads conv2's output (same pointer, column offset and row stride)");
+  IPK_REQUIRE(p1.c_f32 && p1.c_acc && !p1.bias && p1.act == IPOKE_ACT_NONE && !p1.dact && !p1.row_scale,
+              "conv1 accumulates raw fp32 sums");
+  IPK_REQUIRE(conv1->acc_scratch != nullptr && ((uintptr_t)conv1->acc_scratch & 15) == 0,
+              "conv1 needs the accumulation scratch (ipoke_conv_acc_scratch_bytes / _init), 16-byte aligned");
+  IPK_REQUIRE(ipoke_conv_pair_dgrad_applicable(g.M, p.Nout, p1.Nout, dtype, conv1->acc_scratch_bytes),
+              "shape not taken by the fused launch (ipoke_conv_pair_dgrad_applicable)");
+  IPK_REQUIRE(kLdsPair <= device_max_lds(), "the fused launch needs 156 KB of LDS per workgroup");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  p.prio = 2;                                              // (as ipoke_conv_forward: the chain's GEMMs win the issue arbitration)
+  p.w_kmajor = 1;
+  g_last_kernel = IPOKE_KERNEL_IGEMM;                      // ipoke_last_conv_kernel: the GEMM family, as for the conv2 launch this replaces
+  PairEpi e;
+  e.W1 = p1.W; e.ldw1 = p1.ldw; e.cin = p1.Nout; e.transposed = g1.transposed;
+  e.C2 = reinterpret_cast<float*>(p1.C); e.ldc2 = p1.ldc; e.c_coff2 = p1.c_coff; e.c_cstride2 = p1.c_cstride;
+  e.acc_cnt = reinterpret_cast<unsigned*>(conv1->acc_scratch);
+  e.acc_part = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(conv1->acc_scratch) + kAccCounterBytes);
+  p.tiles_m = ceil_div(g.M, 128); p.tiles_n = p.Nout / 128;
+  p.splitk = 1; p.kb_per_split = ceil_div(p.Ktot, 64);
+  pick_xcd_map(p);
+  // tagged as ipoke_conv_forward tags the conv2 data gradient: that family's time now includes conv1's data gradient
+  const bool square = p.Nout == p.Ktot && p.Nout >= 1024;
+  TimedScope ts(square ? IPOKE_TAG_NN_SQUARE : IPOKE_TAG_CONV_BASE, s);
+  auto kern = igemm_nn_pair_kernel;
+  IPK_SET_LDS_ONCE(kern, kLdsPair);
+  hipLaunchKernelGGL(kern, dim3((unsigned)((long)p.tiles_m * p.tiles_n)), dim3(512), kLdsPair, s, p, e);
+  IPK_LAUNCH_CHECK();
+  if (ts.slot >= 0)
+    ts.annotate(square ? 0 : IPOKE_TAG_CONV_BASE + IPOKE_KERNEL_IGEMM, 2.0 * g.M * p.Nout * ((double)p.Kc + 9.0 * p1.Nout),
+                2.0 * ((double)g.M * p.Kc + (double)p.Nout * p.Kc + (double)g.M * p.Nout + 9.0 * p1.Nout * p.Nout) + 4.0 * g.M * p1.Nout);
+  return IPOKE_OK;
 }
 
 static int fill_tn(TnParams& p, const ipoke_wgrad_desc* d, int dtype, bool batched) {

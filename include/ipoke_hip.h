@@ -913,6 +913,26 @@ int ipoke_poke_stamp(const int64_t* centers, const float* values, const float* f
 int64_t ipoke_poke_randomize_workspace_bytes(int B, int H, int W, int n_s);
 int ipoke_poke_randomize(const float* flow, const int64_t* centers, const float* u, int B, int H, int W, int n_c, int n_s, int half,
                          float* pokes, int64_t* picked, int* status, void* workspace, void* stream);
+/* Clip augmentation (data/base_dataset.py:695-722 _get_color_transforms / _get_geometric_transforms, applied per frame at :432-440 and to
+ * the flow at :683-691): brightness -> contrast -> hue -> saturation on uint8 values, then pad(S/2, reflect) -> affine(angle, translate,
+ * nearest neighbour, fill 0) -> center_crop(S), bit-equal to what torchvision's PIL backend computes through Pillow.  One sample's parameters
+ * apply to all T frames of its clip (:204-206).  Host side (ipoke_amd/data.py, ClipAugmenter) draws the parameters as the reference does.
+ *   frames  uint8 [B][T][S][S][3] (HWC)            out     fp32 [B][T][3][S][S] = (u / 255) * 2 - 1 (ToTensor and post_T :105 fused in)
+ *   colour  fp32 [B][3] = the brightness, contrast and saturation factors          hue_add int32 [B] in 0..255, added to the HSV hue mod 256
+ *   mean_l  int32 [B][T] = int(mean of convert("L") of the brightness-adjusted frame + 0.5), the grey level the contrast step blends towards
+ *   affine  int32 [B][6] = Pillow's 16.16 fixed-point inverse matrix for the 2S x 2S padded image: (FIX(m0), FIX(m1), FIX(m2 + m0/2 + m1/2),
+ *           FIX(m3), FIX(m4), FIX(m5 + m3/2 + m4/2)), FIX(v) = floor(v * 65536 + 0.5); output pixel (y, x) of the crop reads the padded pixel
+ *           xi = (a2 + a0 X + a1 Y) >> 16, yi = (a5 + a3 X + a4 Y) >> 16 at X = x + S/2, Y = y + S/2, or the fill outside [0, 2S)
+ * Each colour step is Image.blend(degenerate, image, factor): t = deg + f * (x - deg) in fp32 with the product and the sum rounded
+ * separately, truncated for 0 <= f <= 1 and clipped to [0, 255] first otherwise.  The hue step is Pillow's RGB -> HSV -> RGB round trip and
+ * runs for hue_add = 0 too (it is not the identity).  S must be even and at most 4096, so that every fixed-point term fits 32 bits.
+ * ipoke_aug_frame_means fills mean_l (one integer sum per frame, no atomics); ipoke_aug_frames is one gather over the output pixels and
+ * needs no intermediate image; ipoke_aug_flow gathers flow fp32 [B][C][S][S] with the same geometry and no arithmetic on the values (fill
+ * 0; the vectors are not rotated, as in the reference). */
+int ipoke_aug_frame_means(const uint8_t* frames, const float* colour, int B, int T, int S, int* mean_l, void* stream);
+int ipoke_aug_frames(const uint8_t* frames, const float* colour, const int* hue_add, const int* mean_l, const int* affine, int B, int T, int S,
+                     float* out, void* stream);
+int ipoke_aug_flow(const float* flow, const int* affine, int B, int C, int S, float* out, void* stream);
 
 #ifdef __cplusplus
 }

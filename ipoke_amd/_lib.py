@@ -290,6 +290,9 @@ SIGNATURES = {
     "ipoke_poke_stamp": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "ipoke_poke_randomize_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "ipoke_poke_randomize": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    "ipoke_aug_frame_means": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
+    "ipoke_aug_frames": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P]),
+    "ipoke_aug_flow": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
     "ipoke_timing_start": (c_int, []),
     "ipoke_timing_start_all": (c_int, []),
     "ipoke_timing_stop": (c_int, [POINTER(c_int), c_int, POINTER(c_int), POINTER(ctypes.c_double)]),

@@ -225,6 +225,146 @@ __global__ void poke_fill_kernel(const float* __restrict__ flow, const int* __re
   }
 }
 
+// ---------------------------------------------------------------------------------------------- clip augmentation
+// _get_color_transforms / _get_geometric_transforms (:695-722) as the reference applies them per frame through PIL (:432-440) and to the
+// flow (:683-691), restated on integers and floats at Pillow's precisions so that the result is bit-equal.  Products and sums are rounded
+// separately everywhere: an FMA changes results.  Every function with float arithmetic switches contraction off for its body and uses the
+// plain operators: the __f*_rn intrinsics are inline functions compiled under the default, contraction allowed, so hipcc fuses a
+// __fmul_rn into the __fadd_rn that consumes it ((u / 255) * 2 - 1 written with them became one v_fma_f32).  `/` is IEEE division (hipcc's
+// default, correctly rounded divide).
+__device__ __forceinline__ int aug_clip8(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+// Image.blend(degenerate, image, f) on one uint8 value
+__device__ __forceinline__ int aug_blend(int deg, int x, float f) {
+#pragma clang fp contract(off)
+  const float p = f * (float)(x - deg);
+  const float t = (float)deg + p;
+  if (f >= 0.f && f <= 1.f) return (int)t;
+  return t <= 0.f ? 0 : t >= 255.f ? 255 : (int)t;
+}
+// convert("L")
+__device__ __forceinline__ int aug_luma(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16; }
+// convert("HSV"): fp32 ratios, the hue offset and the two scalings in double -- Pillow's mixture, and the only one that reproduces it
+__device__ __forceinline__ void aug_rgb2hsv(int r, int g, int b, int* h, int* s) {
+#pragma clang fp contract(off)
+  const int maxc = max(r, max(g, b)), minc = min(r, min(g, b));
+  if (maxc == minc) { *h = 0; *s = 0; return; }
+  const float cr = (float)(maxc - minc);
+  const float sf = cr / (float)maxc;
+  const float rc = (float)(maxc - r) / cr, gc = (float)(maxc - g) / cr, bc = (float)(maxc - b) / cr;
+  float hf;
+  if (r == maxc) hf = bc - gc;
+  else if (g == maxc) hf = (float)(2.0 + (double)rc - (double)bc);
+  else hf = (float)(4.0 + (double)gc - (double)rc);
+  const double w = (double)hf / 6.0 + 1.0;               // in [5/6, 11/6]: fmod(w, 1) == w - floor(w), exactly
+  hf = (float)(w - floor(w));
+  *h = aug_clip8((int)((double)hf * 255.0));
+  *s = aug_clip8((int)((double)sf * 255.0));
+}
+// round() of a value >= 0: half away from zero
+__device__ __forceinline__ int aug_round(float v) {
+#pragma clang fp contract(off)
+  const float w = v + 0.5f;
+  return aug_clip8((int)floorf(w));
+}
+// convert("RGB") of an HSV pixel, fp32
+__device__ __forceinline__ void aug_hsv2rgb(int h, int s, int v, int* r, int* g, int* b) {
+#pragma clang fp contract(off)
+  if (s == 0) { *r = *g = *b = v; return; }
+  const float h6 = (float)h * 6.f / 255.f;
+  const float fi = floorf(h6), f = h6 - fi, fs = (float)s / 255.f, vf = (float)v;
+  const float fsf = fs * f, fsg = fs * (1.f - f);
+  const float vp = vf * (1.f - fs), vq = vf * (1.f - fsf), vt = vf * (1.f - fsg);
+  const int p = aug_round(vp), q = aug_round(vq), t = aug_round(vt);
+  switch ((int)fi % 6) {
+    case 0: *r = v; *g = t; *b = p; break;
+    case 1: *r = q; *g = v; *b = p; break;
+    case 2: *r = p; *g = v; *b = t; break;
+    case 3: *r = p; *g = q; *b = v; break;
+    case 4: *r = t; *g = p; *b = v; break;
+    default: *r = v; *g = p; *b = q; break;
+  }
+}
+// ToTensor and post_T (:105): (u / 255) * 2 - 1
+__device__ __forceinline__ float aug_to_float(int u) {
+#pragma clang fp contract(off)
+  const float x = (float)u / 255.f;
+  const float y = x * 2.f;
+  return y - 1.f;
+}
+// pad(S/2, reflect) -> Image.transform(AFFINE, NEAREST) -> center_crop(S) for output pixel (y, x): Pillow's 16.16 fixed-point walk, with
+// its 32-bit wrap-around.  Returns false where the padded image has no pixel (fill), else the offset of the source pixel in the S x S frame.
+__device__ __forceinline__ bool aug_source(const int* __restrict__ a, int S, int y, int x, int* src) {
+  const int P = S >> 1;
+  const unsigned X = (unsigned)(x + P), Y = (unsigned)(y + P);
+  const int xi = (int)((unsigned)a[2] + (unsigned)a[0] * X + (unsigned)a[1] * Y) >> 16;
+  const int yi = (int)((unsigned)a[5] + (unsigned)a[3] * X + (unsigned)a[4] * Y) >> 16;
+  if (xi < 0 || xi >= 2 * S || yi < 0 || yi >= 2 * S) return false;
+  const int sx = xi < P ? P - xi : xi >= P + S ? 2 * (S - 1) - (xi - P) : xi - P;      // numpy's "reflect": the edge is not repeated
+  const int sy = yi < P ? P - yi : yi >= P + S ? 2 * (S - 1) - (yi - P) : yi - P;
+  *src = sy * S + sx;
+  return true;
+}
+
+constexpr int kAugMeanThreads = 256;
+// mean_l[frame] = int(sum of L over the brightness-adjusted frame / S^2 + 0.5), one workgroup per frame, integer sums in a fixed order
+__global__ __launch_bounds__(kAugMeanThreads) void aug_frame_means_kernel(const uint8_t* __restrict__ frames, const float* __restrict__ colour, int T,
+                                                                           int S, int* __restrict__ mean_l) {
+#pragma clang fp contract(off)
+  __shared__ unsigned long long red[kAugMeanThreads / 64];
+  const int frame = blockIdx.x, n = S * S;
+  const float fb = colour[(long)(frame / T) * 3];
+  const uint8_t* p = frames + (long)frame * n * 3;
+  unsigned long long sum = 0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x)
+    sum += (unsigned)aug_luma(aug_blend(0, p[3 * (long)i], fb), aug_blend(0, p[3 * (long)i + 1], fb), aug_blend(0, p[3 * (long)i + 2], fb));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t = 0;
+    for (int i = 0; i < kAugMeanThreads / 64; ++i) t += red[i];
+    mean_l[frame] = (int)((double)t / (double)n + 0.5);
+  }
+}
+
+// out[frame][c][y][x] = the colour chain of the source pixel of (y, x), as (u / 255) * 2 - 1; fill pixels are uint8 0, i.e. -1
+__global__ void aug_frames_kernel(const uint8_t* __restrict__ frames, const float* __restrict__ colour, const int* __restrict__ hue_add,
+                                  const int* __restrict__ mean_l, const int* __restrict__ affine, long frames_n, int T, int S, float* __restrict__ out) {
+  const long n = (long)S * S, total = frames_n * n;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int x = (int)(i % S); long t = i / S;
+    const int y = (int)(t % S); const long frame = t / S;
+    const int b = (int)(frame / T);
+    int r = 0, g = 0, bl = 0, src;
+    if (aug_source(affine + (long)b * 6, S, y, x, &src)) {
+      const uint8_t* p = frames + (frame * n + src) * 3;
+      const float fb = colour[(long)b * 3], fc = colour[(long)b * 3 + 1], fs = colour[(long)b * 3 + 2];
+      const int m = mean_l[frame];
+      r = aug_blend(m, aug_blend(0, p[0], fb), fc); g = aug_blend(m, aug_blend(0, p[1], fb), fc); bl = aug_blend(m, aug_blend(0, p[2], fb), fc);
+      int h, s;
+      const int v = max(r, max(g, bl));
+      aug_rgb2hsv(r, g, bl, &h, &s);
+      aug_hsv2rgb((h + hue_add[b]) & 255, s, v, &r, &g, &bl);
+      const int l = aug_luma(r, g, bl);
+      r = aug_blend(l, r, fs); g = aug_blend(l, g, fs); bl = aug_blend(l, bl, fs);
+    }
+    float* o = out + frame * 3 * n + (long)y * S + x;
+    o[0] = aug_to_float(r); o[n] = aug_to_float(g); o[2 * n] = aug_to_float(bl);
+  }
+}
+
+// out[b][c][y][x] = flow[b][c] at the source pixel of (y, x), 0 where the padded image has none; the vectors are not rotated (:683-691)
+__global__ void aug_flow_kernel(const float* __restrict__ flow, const int* __restrict__ affine, long planes, int C, int S, float* __restrict__ out) {
+  const long n = (long)S * S, total = planes * n;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int x = (int)(i % S); long t = i / S;
+    const int y = (int)(t % S); const long plane = t / S;
+    int src;
+    out[i] = aug_source(affine + (plane / C) * 6, S, y, x, &src) ? flow[plane * n + src] : 0.f;
+  }
+}
+
 // ==============================================================================================
 extern "C" int ipoke_flow_resize(const float* src, float* dst, int B, int C, int Hi, int Wi, int Ho, int Wo, float divide_by, void* stream) {
   IPK_REQUIRE(src && dst && B >= 1 && C >= 1 && Hi >= 1 && Wi >= 1 && Ho >= 1 && Wo >= 1 && divide_by != 0.f, "bad arguments");
@@ -396,6 +536,42 @@ extern "C" int ipoke_poke_randomize(const float* flow, const int64_t* centers, c
   hipLaunchKernelGGL(poke_randomize_select_kernel, dim3(B), dim3(kPokeThreads), lds, STREAM(stream), a);
   hipLaunchKernelGGL(poke_randomize_fill_kernel, dim3(grid1((long)n_s * B * n)), dim3(256), 0, STREAM(stream), a.centers, a.val, status, pokes, B, H,
                      W, n_c, n_s, half);
+  IPK_LAUNCH_CHECK();
+  return IPOKE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- clip augmentation
+static int aug_check_size(int S) {
+  IPK_REQUIRE(S >= 2 && S % 2 == 0 && S <= 4096, "the frame size must be even and at most 4096 (16.16 fixed point in 32 bits)");
+  return IPOKE_OK;
+}
+
+extern "C" int ipoke_aug_frame_means(const uint8_t* frames, const float* colour, int B, int T, int S, int* mean_l, void* stream) {
+  IPK_REQUIRE(frames && colour && mean_l, "null argument");
+  IPK_REQUIRE(B >= 1 && T >= 1 && (long)B * T <= 0x7fffffffL, "bad clip shape");
+  if (int rc = aug_check_size(S)) return rc;
+  hipLaunchKernelGGL(aug_frame_means_kernel, dim3(B * T), dim3(kAugMeanThreads), 0, STREAM(stream), frames, colour, T, S, mean_l);
+  IPK_LAUNCH_CHECK();
+  return IPOKE_OK;
+}
+
+extern "C" int ipoke_aug_frames(const uint8_t* frames, const float* colour, const int* hue_add, const int* mean_l, const int* affine, int B, int T,
+                                int S, float* out, void* stream) {
+  IPK_REQUIRE(frames && colour && hue_add && mean_l && affine && out, "null argument");
+  IPK_REQUIRE(B >= 1 && T >= 1, "bad clip shape");
+  if (int rc = aug_check_size(S)) return rc;
+  const long nf = (long)B * T;
+  hipLaunchKernelGGL(aug_frames_kernel, dim3(grid1(nf * S * S)), dim3(256), 0, STREAM(stream), frames, colour, hue_add, mean_l, affine, nf, T, S, out);
+  IPK_LAUNCH_CHECK();
+  return IPOKE_OK;
+}
+
+extern "C" int ipoke_aug_flow(const float* flow, const int* affine, int B, int C, int S, float* out, void* stream) {
+  IPK_REQUIRE(flow && affine && out, "null argument");
+  IPK_REQUIRE(B >= 1 && C >= 1, "bad flow shape");
+  if (int rc = aug_check_size(S)) return rc;
+  const long planes = (long)B * C;
+  hipLaunchKernelGGL(aug_flow_kernel, dim3(grid1(planes * S * S)), dim3(256), 0, STREAM(stream), flow, affine, planes, C, S, out);
   IPK_LAUNCH_CHECK();
   return IPOKE_OK;
 }

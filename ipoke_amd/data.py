@@ -9,10 +9,15 @@ poke_size, n_pokes, fix_n_pokes, equal_poke_val, scale_poke_to_res) and offers
                                   :959-966, testing/gui.py:120-150)
     randomize_pokes(flow, centers, n)  the re-aimed pokes of the control-sensitivity study (models/second_stage_video.py:798-833)
 
-so that a loader only has to deliver raw flows and frames; everything downstream of the file read happens in HBM.  The random
+and ``ClipAugmenter`` the augmentation the shipped training configs switch on (_get_color_transforms / _get_geometric_transforms,
+:695-722: colour jitter on the frames, one reflect-padded affine warp for frames and flow), so that a loader only has to deliver raw flows
+and uint8 frames; everything downstream of the file read happens in HBM.  The random
 draws are uniforms supplied by the caller (or drawn here from a torch generator): see ``ipoke_poke_simulate`` in
 include/ipoke_hip.h for how they map to the reference's ``np.random.randint`` calls.  No CPU path.
 """
+import math
+
+import numpy as np
 import torch
 
 from . import _lib
@@ -21,6 +26,150 @@ from ._lib import check, ptr
 
 class FlowError(RuntimeError):
     """No poke candidate in a sample (the reference raises FlowError and draws another sample, base_dataset.py:588-589)."""
+
+
+class AugmentParams:
+    """One sample's colour and geometry parameters per entry, as ``ClipAugmenter.draw`` / ``params`` build them.  Host arrays [B]:
+    ``brightness``, ``contrast``, ``saturation`` (the factors), ``hue`` (the hue value), ``angle`` (degrees), ``tx``, ``ty`` (pixels).
+    Device tensors, the arguments of the kernels (include/ipoke_hip.h): ``colour`` fp32 [B, 3], ``hue_add`` int32 [B], ``affine`` int32 [B, 6]
+    and ``mean_l`` int32 [B, T], which ``images`` fills for the clip it is given (None before)."""
+
+    def __init__(self, size, brightness, contrast, saturation, hue, angle, tx, ty, device):
+        self.size = int(size)
+        self.brightness, self.contrast, self.saturation, self.hue, self.angle = (
+            np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in (brightness, contrast, saturation, hue, angle))
+        self.tx, self.ty = (np.atleast_1d(np.asarray(v, dtype=np.int64)) for v in (tx, ty))
+        B = len(self.brightness)
+        if any(len(v) != B for v in (self.contrast, self.saturation, self.hue, self.angle, self.tx, self.ty)):
+            raise ValueError("one value per sample for every parameter")
+        if ((self.hue < -0.5) | (self.hue > 0.5)).any():
+            raise ValueError(f"hue_factor is not in [-0.5, 0.5]: {self.hue.tolist()}")           # torchvision's adjust_hue
+        colour = np.stack([self.brightness, self.contrast, self.saturation], 1).astype(np.float32)
+        hue_add = np.array([int(h * 255) % 256 for h in self.hue], dtype=np.int32)               # np.uint8(hue_factor * 255): truncate, wrap
+        affine = np.array([fixed_point_affine(a, x, y, self.size) for a, x, y in zip(self.angle, self.tx, self.ty)], dtype=np.int64)
+        if (np.abs(affine) >= 2 ** 31).any():
+            raise ValueError("the translation does not fit Pillow's 16.16 fixed point")
+        self.colour = torch.from_numpy(colour).to(device)
+        self.hue_add = torch.from_numpy(hue_add).to(device)
+        self.affine = torch.from_numpy(affine.astype(np.int32)).to(device)
+        self.mean_l = None
+
+    def __len__(self):
+        return len(self.brightness)
+
+
+def fixed_point_affine(angle, tx, ty, size):
+    """The inverse matrix FT.affine(angle, (tx, ty), 1.0, 0) computes, in double, for the reflect-padded 2 size x 2 size image (centre
+    (size, size)), as the six 16.16 fixed-point integers Pillow's nearest-neighbour transform steps through."""
+    a = math.radians(float(angle))
+    m = [math.cos(a), math.sin(a), 0.0, -math.sin(a), math.cos(a), 0.0]
+    cx = cy = float(size)
+    m[2] += m[0] * (-cx - tx) + m[1] * (-cy - ty) + cx
+    m[5] += m[3] * (-cx - tx) + m[4] * (-cy - ty) + cy
+
+    def fix(v):
+        return int(math.floor(v * 65536.0 + 0.5))
+
+    return [fix(m[0]), fix(m[1]), fix(m[2] + m[0] * 0.5 + m[1] * 0.5), fix(m[3]), fix(m[4]), fix(m[5] + m[3] * 0.5 + m[4] * 0.5)]
+
+
+def augment_images(frames_u8, params):
+    """uint8 frames [B, T, S, S, 3] (or [B, S, S, 3]) -> fp32 [B, T, 3, S, S] (or [B, 3, S, S]) in [-1, 1]: the colour chain and the warp of
+    ``params`` in one gather (``ipoke_aug_frame_means`` + ``ipoke_aug_frames``).  Current stream, no host synchronisation."""
+    _lib.require_gpu()
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() not in (4, 5):
+        raise ValueError("frames_u8 must be uint8 [B, T, S, S, 3] or [B, S, S, 3]")
+    single = frames_u8.dim() == 4
+    frames = (frames_u8.unsqueeze(1) if single else frames_u8).contiguous()
+    B, T, S, S2, C = frames.shape
+    if (S, S2, C) != (params.size, params.size, 3) or B != len(params):
+        raise ValueError(f"frames {tuple(frames_u8.shape)} do not match {len(params)} parameter sets at size {params.size}")
+    dev = frames.device
+    colour, hue_add, affine = params.colour.to(dev), params.hue_add.to(dev), params.affine.to(dev)
+    mean_l = torch.empty(B, T, dtype=torch.int32, device=dev)
+    out = torch.empty(B, T, 3, S, S, dtype=torch.float32, device=dev)
+    stream = _lib.current_stream()
+    check(_lib.lib().ipoke_aug_frame_means(ptr(frames), ptr(colour), B, T, S, ptr(mean_l), stream))
+    check(_lib.lib().ipoke_aug_frames(ptr(frames), ptr(colour), ptr(hue_add), ptr(mean_l), ptr(affine), B, T, S, ptr(out), stream))
+    params.mean_l = mean_l
+    return out[:, 0] if single else out
+
+
+def augment_flow(flow, params):
+    """flow fp32 [B, C, S, S] under the warp of ``params`` (``ipoke_aug_flow``): values are copied, not rotated, as in the reference
+    (:683-691).  Current stream, no host synchronisation."""
+    _lib.require_gpu()
+    flow = flow.contiguous().float()
+    if flow.dim() != 4 or flow.shape[2:] != (params.size, params.size) or flow.shape[0] != len(params):
+        raise ValueError(f"flow {tuple(flow.shape)} does not match {len(params)} parameter sets at size {params.size}")
+    B, C, S, _ = flow.shape
+    out = torch.empty_like(flow)
+    check(_lib.lib().ipoke_aug_flow(ptr(flow), ptr(params.affine.to(flow.device)), B, C, S, ptr(out), _lib.current_stream()))
+    return out
+
+
+class ClipAugmenter:
+    """The training augmentation of the reference data set (data/base_dataset.py:695-722) on the device, bit-equal to the per-frame PIL chain
+    (:432-440 for the frames, :683-691 for the flow): brightness, contrast, hue and saturation jitter, then pad(size / 2, reflect) ->
+    affine(angle, translate) -> center_crop(size), nearest neighbour.  One parameter set per sample, shared by all frames of its clip and
+    by its flow (:204-206).  ``config`` is the ``data`` section (:86-93): augment, p_col, p_geom, augment_b/c/h/s, aug_deg, aug_trans,
+    spatial_size.
+
+    Out of scope: ``fancy_aug`` (use_fb_aug, :425-442), which blends a second colour draw in through the segmentation masks, and
+    ``_get_flip_transform`` (:724-729), which nothing calls."""
+
+    def __init__(self, config):
+        self.config = config
+        self.spatial_size = tuple(int(v) for v in config["spatial_size"])
+        if self.spatial_size[0] != self.spatial_size[1]:
+            raise ValueError(f"spatial_size {self.spatial_size} is not square (the reference's own reshape at :690 assumes it)")
+        self.size = self.spatial_size[0]
+        self.augment = bool(config.get("augment", False))
+        self.p_col, self.p_geom = float(config.get("p_col", 0)), float(config.get("p_geom", 0))
+        self.ab, self.ac = float(config.get("augment_b", 0)), float(config.get("augment_c", 0))
+        self.ah, self.a_s = float(config.get("augment_h", 0)), float(config.get("augment_s", 0))
+        self.ad = float(config.get("aug_deg", 0))
+        self.at = tuple(config.get("aug_trans", (0, 0)))
+
+    def draw(self, B, rng, device=None):
+        """Parameters for ``B`` samples from ``rng``, a ``numpy.random.RandomState``: per sample the calls of _get_color_transforms
+        (:698-702) and then of _get_geometric_transforms (:714-717), in that order and with those arguments, so that an ``rng`` seeded like
+        ``np.random`` yields the reference's values."""
+        if not self.augment:
+            raise ValueError("augment is off in this config: the reference then applies no transform at all (make_batch(augment=None))")
+        S0, S1 = self.spatial_size
+        rows = []
+        for _ in range(int(B)):
+            make = bool(rng.choice(np.arange(2), size=1, p=[1 - self.p_col, self.p_col])[0])
+            brightness = float(rng.uniform(-self.ab, self.ab, 1)[0]) if self.ab > 0. and make else 0.
+            contrast = float(rng.uniform(-self.ac, self.ac, 1)[0]) if self.ac > 0. and make else 0.
+            hue = float(rng.uniform(-self.ah, 2 * self.ah, 1)[0]) if self.ah > 0. and make else 0.
+            saturation = 1. + (float(rng.uniform(-self.a_s, self.a_s)) if self.a_s > 0. and make else 0)
+            make = bool(rng.choice(np.arange(2), size=1, p=[1 - self.p_geom, self.p_geom])[0])
+            angle = float(rng.uniform(-self.ad, self.ad, 1)[0]) if self.ad > 0. and make else 0.
+            vert = int(rng.randint(int(-self.at[0] * S1 / 2), int(self.at[0] * S1 / 2), 1)[0]) if self.at[0] > 0 and make else 0
+            hor = int(rng.randint(int(-self.at[1] * S0 / 2), int(self.at[1] * S0 / 2), 1)[0]) if self.at[1] > 0 and make else 0
+            rows.append((1. + brightness, 1. + contrast, saturation, hue, angle, hor, vert))          # translate=(tval_hor, tval_vert)
+        return self.params(*zip(*rows), device=device)
+
+    def params(self, brightness, contrast, saturation, hue, angle, tx, ty, device=None):
+        """The parameter object from explicit per-sample values: the three factors, the hue value in [-0.5, 0.5], the angle in degrees and
+        the translation in pixels (tx to the right, ty down)."""
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        return AugmentParams(self.size, brightness, contrast, saturation, hue, angle, tx, ty, device)
+
+    def images(self, frames_u8, params):
+        self._check(params)
+        return augment_images(frames_u8, params)
+
+    def flow(self, flow, params):
+        self._check(params)
+        return augment_flow(flow, params)
+
+    def _check(self, params):
+        if params.size != self.size:
+            raise ValueError(f"parameters built for size {params.size}, augmenter for {self.size}")
 
 
 class PokeSimulator:
@@ -127,10 +276,19 @@ class PokeSimulator:
                             f"(status {status[bad].tolist()})")
         return pokes, picked, status
 
-    def make_batch(self, images, raw_flow, zero_poke=None, u=None, generator=None):
+    def make_batch(self, images, raw_flow, zero_poke=None, u=None, generator=None, augment=None, frames_u8=None):
         """The ``batch`` dict the second stage consumes (images, flow, poke = [poke, poke_centers]) from frames already on the device
-        and raw flows: the part of BaseDataset.__getitem__ that follows the file reads."""
+        and raw flows: the part of BaseDataset.__getitem__ that follows the file reads.  With ``augment`` (the parameters of
+        ``ClipAugmenter.draw`` / ``params``) the order is the reference's: _get_flow -> the warp -> _get_poke, so the pokes are taken from
+        the warped flow, and ``images`` comes from the uint8 clip ``frames_u8`` [B, T, S, S, 3] through the colour chain and the same warp."""
         flow = self.get_flow(raw_flow)
+        if augment is not None:
+            if frames_u8 is None:
+                raise ValueError("make_batch(augment=...) builds the images from frames_u8")
+            if self.spatial_size != (augment.size, augment.size):
+                raise ValueError(f"parameters built for size {augment.size}, simulator for {self.spatial_size}")
+            flow = augment_flow(flow, augment)
+            images = augment_images(frames_u8, augment)
         # no host synchronisation on the loader path: samples without a candidate (the reference's FlowError) are flagged in
         # ``poke_status`` (int32 [B], 1 = resample), for the caller to inspect when it chooses to
         poke, centers, flow_out, status = self.get_poke(flow, zero_poke, u, generator, strict=False)

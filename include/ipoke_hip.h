@@ -680,8 +680,10 @@ typedef struct { int32_t B, T, L, Cx, Ch, H, W; } ipoke_gru_desc;
 int64_t ipoke_gru_workspace_bytes(const ipoke_gru_desc* d, int dtype);
 /* out [T][M][ldo]: the last cell's hidden state after every step.  The workspace keeps every operand for ipoke_gru_unroll_backward. */
 /* The forward unroll runs as ONE launch where it applies (a workgroup per sample runs the T x L recurrence on LDS-resident operands;
- * bf16, 8 x 8 map, Cx = Ch in {32, 64}), otherwise as four launches per cell and step; both forms fill the same workspace for
- * ipoke_gru_unroll_backward (test hook to force either: ipoke_gru_set_fused, ipoke_hip_dev.h). */
+ * bf16, 8 x 8 map, Cx = Ch in {32, 64}, and the states of the L cells small enough for the LDS of the forward AND the backward kernel
+ * to fit a workgroup: L <= 5 at Ch = 64, L <= 15 at Ch = 32 with 160 KiB), otherwise as four launches per cell and step; both forms fill
+ * the same workspace for ipoke_gru_unroll_backward, which runs in the form the forward pass took (test hooks: ipoke_gru_set_fused,
+ * ipoke_gru_fused_applicable, ipoke_gru_workspace_form, ipoke_hip_dev.h). */
 int ipoke_gru_unroll_forward(const ipoke_gru_desc* d, const void* x0, int ldx, const void* h0, int ldh, const float* const* weights,
                              void* workspace, void* out, int ldo, int dtype, void* stream);
 /* d_out [T][M][ldo] -> dweights (the layouts of `weights`, written), d_x0 [M][Cx] and d_h0 [M][Ch] (fp32; d_h0 summed over the cells) */

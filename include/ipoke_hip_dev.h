@@ -69,6 +69,19 @@ int ipoke_flow_test_split_pair_dgrad(ipoke_flow* f, int on);
 
 /* Test hook: forward unroll of the ConvGRU as one launch (1), as launches per phase (0), or the IPOKE_GRU_FUSED environment default (< 0) */
 int ipoke_gru_set_fused(int mode);
+/* Test hook: byte offsets into the ConvGRU unroll's workspace and row widths (in elements) of its per-(cell, step) buffers:
+ * out[2 k], out[2 k + 1] for k = XH, XHR, UR, U, O, DO, DUR (operands [x | h], [x | h r]; pre-activations ur, the update gate u, the
+ * candidate's pre-activation o; the gradients of o and ur); out[14] = ipoke_gru_workspace_bytes; out[15 .. 20] the weight operands:
+ * offset of cell 0's slots, bytes per cell, and within a cell the offsets of the ur, ur^T, o and o^T operands.  Buffer k of (cell l,
+ * step t) starts (l T + t) B H W rows behind its offset.  Needs n >= 21; returns the number of entries.  No device is touched. */
+int ipoke_gru_workspace_layout(const ipoke_gru_desc* d, int dtype, int64_t* out, int n);
+/* Test hook: the form ipoke_gru_unroll_forward takes for these arguments where a workgroup may ask for `lds_limit` bytes of LDS: 1 the
+ * fused form (bf16, 8 x 8 map, Cx = Ch in {32, 64}, ldx, ldh multiples of 8 and ldo of 4, x0 / h0 16-byte and out 8-byte aligned, and the
+ * LDS of BOTH the forward and the backward kernel within the limit), 0 the launch-per-phase form.  The pointers are not dereferenced. */
+int ipoke_gru_fused_applicable(const ipoke_gru_desc* d, int dtype, int ldx, int ldh, int ldo, const void* x0, const void* h0, const void* out,
+                               int64_t lds_limit);
+/* Test hook: the form of the last forward pass on record for `workspace`: 1 fused, 0 launch-per-phase, -1 none on record */
+int ipoke_gru_workspace_form(const void* workspace);
 
 #ifdef __cplusplus
 }

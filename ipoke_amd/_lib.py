@@ -143,6 +143,9 @@ SIGNATURES = {
     "ipoke_last_wgrad_kernel": (c_int, []),
     "ipoke_gru_set_fused": (c_int, [c_int]),
     "ipoke_gru_workspace_bytes": (c_int64, [POINTER(GruDesc), c_int]),
+    "ipoke_gru_workspace_layout": (c_int, [POINTER(GruDesc), c_int, POINTER(c_int64), c_int]),
+    "ipoke_gru_fused_applicable": (c_int, [POINTER(GruDesc), c_int, c_int, c_int, c_int, _P, _P, _P, c_int64]),
+    "ipoke_gru_workspace_form": (c_int, [_P]),
     "ipoke_gru_unroll_forward": (c_int, [POINTER(GruDesc), _P, c_int, _P, c_int, POINTER(c_void_p), _P, _P, c_int, c_int, _P]),
     "ipoke_gru_unroll_backward": (c_int, [POINTER(GruDesc), _P, c_int, _P, POINTER(c_void_p), _P, _P, c_int, _P]),
     "ipoke_rowscale_bwd_workspace_floats": (c_int64, [c_int64, c_int, c_int64]),

@@ -3,6 +3,15 @@ namespace ipoke {
 static thread_local std::string g_last_error;
 void set_error(const std::string& msg) { g_last_error = msg; }
 int fail(int code, const std::string& msg) { g_last_error = msg; return code; }
+size_t device_max_lds() {
+  static std::once_flag once; static size_t bytes = 0;
+  std::call_once(once, []() {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && v > 0) bytes = (size_t)v;
+    else bytes = 64 * 1024;
+  });
+  return bytes;
+}
 }  // namespace ipoke
 extern "C" const char* ipoke_last_error(void) { return ipoke::g_last_error.c_str(); }
 extern "C" int ipoke_version(void) { return 100; }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <mutex>
 #include <string>
 
 #include "../../include/ipoke_hip.h"
@@ -31,6 +32,23 @@ int fail(int code, const std::string& msg);
   } while (0)
 
 #define IPK_LAUNCH_CHECK() IPK_HIP(hipGetLastError())
+
+// ---- dynamic LDS ------------------------------------------------------------------------------------------------------
+// Dynamic LDS a workgroup may ask for on this device (queried once, common.cpp): the kernels that keep their operands in LDS are only
+// dispatched when their buffers fit, so that a smaller part falls back to the generic kernels instead of failing in hipFuncSetAttribute.
+size_t device_max_lds();
+template <typename KernelT>
+static int set_lds(KernelT k, size_t bytes) {
+  IPK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  return IPOKE_OK;
+}
+// The dynamic-LDS attribute of a kernel is set once per process, race-free (the header promises thread safety for launches on
+// distinct streams): one std::once_flag + result per expansion site, i.e. per kernel (template instantiation).
+#define IPK_SET_LDS_ONCE(kern, bytes) do {                                              \
+    static std::once_flag ipk_once; static int ipk_rc = IPOKE_OK;                       \
+    std::call_once(ipk_once, [&]() { ipk_rc = ::ipoke::set_lds(kern, bytes); });        \
+    if (ipk_rc) return ipk_rc;                                                          \
+  } while (0)
 
 // ---- in-situ timing of tagged launches (common.cpp; bench.py's roofline objects) ---------------------------------
 bool timing_active(int tag = 1);      // tags >= IPOKE_TAG_CONV_BASE are recorded only at level 2 (ipoke_timing_start_all)

@@ -1119,33 +1119,10 @@ static int make_geom(GeomDev& g, int NB, int Di, int Hi, int Wi, int Do, int Ho,
   return IPOKE_OK;
 }
 
-template <typename KernelT>
-static int set_lds(KernelT k, size_t bytes) {
-  IPK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  return IPOKE_OK;
-}
-// Dynamic LDS a workgroup may ask for on this device (queried once): the stationary-input kernels are only dispatched when their buffers
-// fit, so that a smaller part falls back to the generic kernels instead of failing in hipFuncSetAttribute.
-static size_t device_max_lds() {
-  static std::once_flag once; static size_t bytes = 0;
-  std::call_once(once, []() {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && v > 0) bytes = (size_t)v;
-    else bytes = 64 * 1024;
-  });
-  return bytes;
-}
+// set_lds / device_max_lds: common.h (shared with gru.hip)
 constexpr size_t kLdsC64 = 9 * 64 * 128 + 2 * 41 * 1024 + 1024, kLdsHalo16 = 2 * 41 * 1024 + 4 * 128 * 128 + 8 * 1024,
                  kLdsHalo = 2 * 24 * 1024 + 12 * 64 * 128 + 8 * 1024, kLdsS8 = 2 * 128 * 128 + 256 + 12 * 64 * 128 + 512 * 16,
                  kLdsLat8 = 3 * 2 * 128 * 128 + 256, kLdsK64 = 128 * 128 + 256 + 6 * 128 * 128;
-
-// The dynamic-LDS attribute of a kernel is set once per process, race-free (the header promises thread safety for launches on
-// distinct streams): one std::once_flag + result per expansion site, i.e. per kernel (template instantiation).
-#define IPK_SET_LDS_ONCE(kern, bytes) do {                                              \
-    static std::once_flag ipk_once; static int ipk_rc = IPOKE_OK;                       \
-    std::call_once(ipk_once, [&]() { ipk_rc = set_lds(kern, bytes); });                 \
-    if (ipk_rc) return ipk_rc;                                                          \
-  } while (0)
 
 // Scratch of the deterministic split-K accumulation (ipoke_conv_desc.acc_scratch): 4096 tile counters, then the slabs.
 static constexpr long kAccCounterBytes = 4096 * 4;
@@ -4444,6 +4421,9 @@ static int launch_tn(TnParams& p, hipStream_t s, int nbatch = 1) {
     // same 64 KB -- three stages in flight, twice the barriers -- measured 35.5 against 29.7 us alone and 63.3 against 62.0 ms per step
     // in round 3; removed.)
     constexpr int NST = 2;
+    // the kernel's fixed-row addressing takes a 64-row stage for ONE sample (the 8 x 8 latent); on a smaller map a stage holds
+    // several samples and every row is decoded on its own (igemm_tn_kernel steps mb * (RM / S) samples per stage instead)
+    if (p.g.S != RM) p.rows_fixed = 0;
     // narrow outputs of the flow engine's batched launches (conv3 of the coupling nets): 64 x 256 tiles (see the kernel)
     const bool narrow = p.batch != nullptr && p.Nout <= 64 && p.Ktot >= 512 && p.max_wgs <= 0;
     if (narrow) p.tiles_k = ceil_div(p.Ktot, 256);

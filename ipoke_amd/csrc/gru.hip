@@ -603,6 +603,31 @@ int gru_plan(GruPlan& p, const ipoke_gru_desc* d, int dtype) {
   return IPOKE_OK;
 }
 
+// Dynamic LDS of the two fused kernels (the carve-ups at the top of gru_fused_fwd_kernel / gru_fused_bwd_kernel, Cx = Ch): the ONE place
+// the launch sites and the form decision read.
+size_t gru_fused_fwd_lds(int Ch, int L) {
+  const size_t PK = 2 * (size_t)(2 * Ch) + 32;
+  return 4 * 65 * PK + ((size_t)L * 64 * Ch + 2 * 64 * Ch) * 2 + (size_t)L * 3 * Ch * 4;
+}
+size_t gru_fused_bwd_lds(int Ch, int L) {
+  const size_t Kc = 2 * (size_t)Ch, PO = 2 * (size_t)Ch + 32, PU = 2 * Kc + 32;
+  return 65 * PO + 65 * PU + (64 * Kc + 64 * (size_t)Ch + (size_t)L * 2 * 64 * Ch) * 2 + (size_t)64 * Ch * 4;
+}
+// the largest request of a kernel over the stack depths the limit admits: what its dynamic-LDS attribute is raised to, once
+size_t gru_fused_lds_cap(size_t (*lds)(int, int), int Ch, size_t limit) {
+  size_t cap = 0;
+  for (int L = 1; L <= 16; ++L) if (lds(Ch, L) <= limit) cap = lds(Ch, L);
+  return cap;
+}
+// The form of the unroll as a function of the call alone: one workgroup per sample (gru_fused_fwd_kernel, then gru_fused_bwd_kernel on
+// the fragment-tiled operands it leaves) where the geometry and the operands' alignment allow it AND the LDS of BOTH directions fits
+// `lds_limit` -- the backward kernel is the larger one, and a forward pass that went fused leaves the backward pass no other form.
+bool gru_fused_applicable(const GruPlan& p, int dtype, int ldx, int ldh, int ldo, const void* x0, const void* h0, const void* out, size_t lds_limit) {
+  return dtype == IPOKE_BF16 && p.H == 8 && p.W == 8 && p.Cx == p.Ch && (p.Ch == 32 || p.Ch == 64) && p.L <= 16 &&
+         ldx % 8 == 0 && ldh % 8 == 0 && ldo % 4 == 0 && ((reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(h0)) & 15) == 0 &&
+         (reinterpret_cast<uintptr_t>(out) & 7) == 0 && gru_fused_fwd_lds(p.Ch, p.L) <= lds_limit && gru_fused_bwd_lds(p.Ch, p.L) <= lds_limit;
+}
+
 template <typename K, typename... A>
 int launch1d(K kern, long total, hipStream_t s, A... a) {
   long g = (total + 255) / 256; if (g < 1) g = 1; if (g > 4096) g = 4096;
@@ -656,14 +681,6 @@ static int gru_layout_of(const void* ws) {       // -1: no forward pass on recor
   auto it = g_gru_ws_layout.find(ws);
   return it == g_gru_ws_layout.end() ? -1 : it->second.first;
 }
-// dynamic-LDS limit of a kernel instantiation, raised once (grows monotonically)
-template <typename K> static int gru_ensure_lds(K kern, size_t bytes, size_t& granted) {
-  if (bytes > granted) {
-    IPK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    granted = bytes;
-  }
-  return IPOKE_OK;
-}
 /* Test hook: 0 = the launch-per-phase forward unroll, 1 = the fused kernel where it applies, < 0 = re-read IPOKE_GRU_FUSED at the next call. */
 extern "C" int ipoke_gru_set_fused(int mode) { g_gru_fused.store(mode < 0 ? -1 : (mode ? 1 : 0), std::memory_order_relaxed); return IPOKE_OK; }
 
@@ -672,6 +689,30 @@ extern "C" int64_t ipoke_gru_workspace_bytes(const ipoke_gru_desc* d, int dtype)
   if (gru_plan(p, d, dtype) != IPOKE_OK) return -1;
   return p.bytes;
 }
+/* Test hook: byte offsets into the workspace and row widths (elements) of the per-(cell, step) buffers, as GruPlan lays them out:
+ * out[2 k], out[2 k + 1] for k = XH, XHR, UR, U, O, DO, DUR; out[14] the total (ipoke_gru_workspace_bytes); out[15 .. 20] the weight
+ * operands: offset of cell 0's slots, bytes per cell, and within a cell the offsets of the ur, ur^T, o and o^T operands.  Buffer k of
+ * (cell l, step t) starts (l T + t) M rows behind its offset.  Host arithmetic only.  Returns the number of entries written. */
+extern "C" int ipoke_gru_workspace_layout(const ipoke_gru_desc* d, int dtype, int64_t* out, int n) {
+  GruPlan p; int rc = gru_plan(p, d, dtype); if (rc) return rc;
+  IPK_REQUIRE(out && n >= 21, "ipoke_gru_workspace_layout: room for 21 entries");
+  const int64_t v[21] = {p.XH, p.Kc, p.XHR, p.Kc, p.UR, p.N2p, p.U, p.Ch, p.O, p.Chp, p.DO, p.Chp, p.DUR, p.N2p, p.bytes,
+                         p.WOP, p.wop_layer, 0, (p.wop_ur + 255) / 256 * 256, (p.wop_ur + 255) / 256 * 256 + (p.wop_urT + 255) / 256 * 256,
+                         (p.wop_ur + 255) / 256 * 256 + (p.wop_urT + 255) / 256 * 256 + (p.wop_o + 255) / 256 * 256};
+  for (int i = 0; i < 21; ++i) out[i] = v[i];
+  return 21;
+}
+/* Test hook: 1 when a forward call with these arguments takes the fused form on a device whose workgroups may ask for `lds_limit` bytes
+ * of LDS (and ipoke_gru_set_fused / IPOKE_GRU_FUSED do not forbid it), 0 when it takes the launch-per-phase form; the pointers are only
+ * looked at for their alignment.  Host arithmetic only. */
+extern "C" int ipoke_gru_fused_applicable(const ipoke_gru_desc* d, int dtype, int ldx, int ldh, int ldo, const void* x0, const void* h0,
+                                          const void* out, int64_t lds_limit) {
+  GruPlan p; int rc = gru_plan(p, d, dtype); if (rc) return rc;
+  IPK_REQUIRE(ldx >= p.Cx && ldh >= p.Ch && ldo >= p.Ch && lds_limit >= 0, "bad arguments");
+  return gru_fused_applicable(p, dtype, ldx, ldh, ldo, x0, h0, out, (size_t)lds_limit) ? 1 : 0;
+}
+/* Test hook: the form of the last forward pass on record for this workspace: 1 fused (fragment-tiled operands), 0 launch-per-phase, -1 none */
+extern "C" int ipoke_gru_workspace_form(const void* workspace) { return gru_layout_of(workspace); }
 
 /* weights: 4 device pointers per cell -- w_ur [2Ch][Cx+Ch][3][3] (update gate rows first, as the reference's two gate convolutions stacked),
  * b_ur [2Ch], w_o [Ch][Cx+Ch][3][3], b_o [Ch], fp32 in PyTorch layout.  x0 [M][ldx] is the constant input of cell 0, h0 [M][ldh] the initial
@@ -684,9 +725,7 @@ extern "C" int ipoke_gru_unroll_forward(const ipoke_gru_desc* d, const void* x0,
   // one workgroup per sample runs the whole recurrence (gru_fused_fwd_kernel) where it applies; IPOKE_GRU_FUSED=0: the launch-per-phase form
   int fm = g_gru_fused.load(std::memory_order_relaxed);
   if (fm < 0) { fm = (getenv("IPOKE_GRU_FUSED") && atoi(getenv("IPOKE_GRU_FUSED")) == 0) ? 0 : 1; g_gru_fused.store(fm, std::memory_order_relaxed); }
-  const bool fused = fm != 0 && dtype == IPOKE_BF16 && p.H == 8 && p.W == 8 && p.Cx == p.Ch && (p.Ch == 32 || p.Ch == 64) && p.L <= 16 &&
-                     ldx % 8 == 0 && ldh % 8 == 0 && ldo % 4 == 0 && ((reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(h0)) & 15) == 0 &&
-                     (reinterpret_cast<uintptr_t>(out) & 7) == 0;
+  const bool fused = fm != 0 && gru_fused_applicable(p, dtype, ldx, ldh, ldo, x0, h0, out, device_max_lds());
   bool fused_ok = fused;
   for (int l = 0; fused_ok && l < p.L; ++l)
     fused_ok = weights[4 * l] && weights[4 * l + 1] && weights[4 * l + 2] && weights[4 * l + 3] &&
@@ -719,16 +758,15 @@ extern "C" int ipoke_gru_unroll_forward(const ipoke_gru_desc* d, const void* x0,
       P.b_ur[l] = weights[4 * l + 1]; P.b_o[l] = weights[4 * l + 3];
     }
     {
-      const int PK = 2 * p.Kc + 32;
-      const size_t lds = (size_t)4 * 65 * PK + ((size_t)p.L * 64 * p.Ch + 2 * 64 * p.Ch) * 2 + (size_t)p.L * 3 * p.Ch * 4;
+      const size_t lds = gru_fused_fwd_lds(p.Ch, p.L), cap = gru_fused_lds_cap(gru_fused_fwd_lds, p.Ch, device_max_lds());
       bf16_t* XH = reinterpret_cast<bf16_t*>(c.ws + p.XH); bf16_t* XHR = reinterpret_cast<bf16_t*>(c.ws + p.XHR);
       bf16_t* URp = reinterpret_cast<bf16_t*>(c.ws + p.UR); bf16_t* Up = reinterpret_cast<bf16_t*>(c.ws + p.U); bf16_t* Op = reinterpret_cast<bf16_t*>(c.ws + p.O);
       if (p.Ch == 64) {
-        static size_t granted64 = 0; rc = gru_ensure_lds(gru_fused_fwd_kernel<64>, lds, granted64); if (rc) return rc;
+        IPK_SET_LDS_ONCE(gru_fused_fwd_kernel<64>, cap);
         hipLaunchKernelGGL(gru_fused_fwd_kernel<64>, dim3(p.B), dim3(512), lds, c.s, (const bf16_t*)x0, ldx, (const bf16_t*)h0, ldh, P, XH, XHR, URp, Up, Op,
                            (bf16_t*)out, ldo, p.M, p.T, p.L);
       } else {
-        static size_t granted32 = 0; rc = gru_ensure_lds(gru_fused_fwd_kernel<32>, lds, granted32); if (rc) return rc;
+        IPK_SET_LDS_ONCE(gru_fused_fwd_kernel<32>, cap);
         hipLaunchKernelGGL(gru_fused_fwd_kernel<32>, dim3(p.B), dim3(512), lds, c.s, (const bf16_t*)x0, ldx, (const bf16_t*)h0, ldh, P, XH, XHR, URp, Up, Op,
                            (bf16_t*)out, ldo, p.M, p.T, p.L);
       }
@@ -792,16 +830,16 @@ extern "C" int ipoke_gru_unroll_backward(const ipoke_gru_desc* d, const void* d_
   if (fused_bwd) {
     GruFusedPtrs P; std::memset(&P, 0, sizeof(P));
     for (int l = 0; l < p.L; ++l) { P.w_ur[l] = reinterpret_cast<const bf16_t*>(c.wop(l, 1)); P.w_o[l] = reinterpret_cast<const bf16_t*>(c.wop(l, 3)); }
-    const int PO = 2 * p.Ch + 32, PU = 2 * p.Kc + 32;
-    const size_t lds = (size_t)65 * PO + (size_t)65 * PU + ((size_t)64 * p.Kc + 64 * p.Ch + (size_t)p.L * 2 * 64 * p.Ch) * 2 + (size_t)64 * p.Ch * 4;
+    const size_t lds = gru_fused_bwd_lds(p.Ch, p.L), cap = gru_fused_lds_cap(gru_fused_bwd_lds, p.Ch, device_max_lds());
+    IPK_REQUIRE(lds <= cap, "the fused backward kernel's LDS does not fit this device (the forward pass ran on another one?)");
     const bf16_t* XH = reinterpret_cast<const bf16_t*>(c.ws + p.XH); const bf16_t* URp = reinterpret_cast<const bf16_t*>(c.ws + p.UR);
     const bf16_t* Up = reinterpret_cast<const bf16_t*>(c.ws + p.U); const bf16_t* Op = reinterpret_cast<const bf16_t*>(c.ws + p.O);
     bf16_t* DOp = reinterpret_cast<bf16_t*>(c.ws + p.DO); bf16_t* DURp = reinterpret_cast<bf16_t*>(c.ws + p.DUR);
     if (p.Ch == 64) {
-      static size_t granted64 = 0; rc = gru_ensure_lds(gru_fused_bwd_kernel<64>, lds, granted64); if (rc) return rc;
+      IPK_SET_LDS_ONCE(gru_fused_bwd_kernel<64>, cap);
       hipLaunchKernelGGL(gru_fused_bwd_kernel<64>, dim3(p.B), dim3(512), lds, c.s, (const bf16_t*)d_out, ldo, P, XH, URp, Up, Op, DOp, DURp, d_x0, d_h0, p.M, p.T, p.L);
     } else {
-      static size_t granted32 = 0; rc = gru_ensure_lds(gru_fused_bwd_kernel<32>, lds, granted32); if (rc) return rc;
+      IPK_SET_LDS_ONCE(gru_fused_bwd_kernel<32>, cap);
       hipLaunchKernelGGL(gru_fused_bwd_kernel<32>, dim3(p.B), dim3(512), lds, c.s, (const bf16_t*)d_out, ldo, P, XH, URp, Up, Op, DOp, DURp, d_x0, d_h0, p.M, p.T, p.L);
     }
     IPK_LAUNCH_CHECK();

@@ -27,7 +27,7 @@ def test_test_hooks_live_in_the_developer_header():
     dev = header_functions(("ipoke_hip_dev.h",))
     hooks = {"ipoke_spin_delay", "ipoke_timing_start", "ipoke_timing_start_all", "ipoke_timing_stop", "ipoke_timing_stop_ex",
              "ipoke_set_dispatch_override", "ipoke_gru_set_fused", "ipoke_last_conv_kernel", "ipoke_last_wgrad_kernel",
-             "ipoke_conv_forward_repeat"}
+             "ipoke_conv_forward_repeat", "ipoke_gru_workspace_layout", "ipoke_gru_fused_applicable", "ipoke_gru_workspace_form"}
     assert hooks <= dev and not (hooks & public)
 
 

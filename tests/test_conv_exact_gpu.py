@@ -174,6 +174,8 @@ WCASES = {
     "wgrad_halo_outside_m4096": (lambda: _wg(4, 32, 32, 64, 64), BF, _lib.WGRAD_TN_GLDS, 0),
     "wgrad_tn_1x1_k128_n256": (lambda: _wg(4, 16, 16, 128, 256, k=1), BF, _lib.WGRAD_TN_GLDS, 0),
     "wgrad_tn_3x3_k48_n40_ragged": (lambda: _wg(3, 16, 16, 48, 40), BF, _lib.WGRAD_TN_GLDS, 0),
+    # a map of fewer than 64 positions: a 64-row stage of the LDS-DMA kernel holds several samples (the second stage starts at sample 2)
+    "wgrad_tn_3x3_k24_n32_4x8_map": (lambda: _wg(4, 4, 8, 24, 32), BF, _lib.WGRAD_TN_GLDS, 0),
     "wgrad_tn_f32_3x3_k36_n20": (lambda: _wg(2, 16, 16, 36, 20, dtype=F32), F32, _lib.WGRAD_TN, 0),
     "wgrad_tn_f32_1x1_split_atomic": (lambda: _wg(8, 16, 16, 64, 64, k=1, dtype=F32, splitm=4), F32, _lib.WGRAD_TN, 0),
 }

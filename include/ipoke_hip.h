@@ -283,6 +283,24 @@ int64_t ipoke_conv3x3_coupling_xchg_bytes(void);
 int ipoke_conv3x3_coupling_xchg_init(void* xchg, void* stream);
 int ipoke_conv3x3_coupling(const ipoke_conv_desc* conv, const ipoke_affine_desc* aff, const ipoke_coupling_epi* epi, int B, int dtype,
                            void* stream);
+/* conv2 (+ bias, ELU), conv3 and the coupling transform of a coupling net (NICEConvBlock, macow_utils.py:270-281; the affine transform
+ * and its inverse, macow_utils.py:42-66) as ONE launch:
+ *   h2 = ELU(h1 @ W2^T + b2)              `conv2`: the 1x1 convolution on dense dtype rows with its weight read N-major (w_kmajor = 0,
+ *                                         act = IPOKE_ACT_ELU, C = h2 in dtype at pitch ldc), exactly the descriptor ipoke_conv_forward
+ *                                         takes for it.  conv2->C == NULL: h2 is not stored (the reverse pass, where nothing reads it).
+ *   (mu, s) = conv3x3(h2, W3) + bias      `conv3`, `aff`, `epi`: exactly the arguments of ipoke_conv3x3_coupling, with conv3's input A =
+ *   state' = coupling(state; mu, s)       conv2's C (same pointer, row stride and column offset; ignored when conv2->C is NULL) and
+ *                                         conv3->Kc == conv2->Nout.  conv3->splitk is ignored: the hidden channels are always reduced in
+ *                                         slices of 128 (one column tile of the GEMM each) that meet inside the launch.
+ * Every output is bit-identical to ipoke_conv_forward on the 128 x 128 tile followed by ipoke_conv3x3_coupling at hidden / 128 slices
+ * (the "nt128" / "cpl_split" switches of ipoke_set_dispatch_override).  Shapes the kernel does not take
+ * (ipoke_conv_pair_coupling_applicable) are rejected with IPOKE_ERR_INVALID; callers issue the two launches there. */
+int ipoke_conv_pair_coupling(const ipoke_conv_desc* conv2, const ipoke_conv_desc* conv3, const ipoke_affine_desc* aff,
+                             const ipoke_coupling_epi* epi, int B, int dtype, void* stream);
+/* Host-only: 1 when ipoke_conv_pair_coupling takes M = 64*B rows, `hidden` channels (conv2's outputs = conv3's inputs) and nout3 = 2 Cp
+ * output columns of conv3 in `dtype`: bf16, M a multiple of 64, hidden in {512, 1024, 2048, 4096}, nout3 <= 64 and one round of
+ * workgroups (ceil(M / 128) * hidden / 128 <= 256).  Else 0. */
+int ipoke_conv_pair_coupling_applicable(int M, int hidden, int nout3, int dtype);
 int ipoke_reduce_rows(const float* src, float* dst, int R, int ncols, void* stream);
 /* multi-tensor form: entries_dev[i] = {int64 src, int64 dst (float offsets), int32 ld, int32 ncols, int32 rmul, int32 pad};
  * entry i sums R * max(rmul, 1) rows */

@@ -16,9 +16,13 @@ extern "C" {
 int ipoke_conv_forward_repeat(const ipoke_conv_desc* d, int dtype, int n, void* stream);
 /* Test hook: kernel-dispatch switch `name` ("c64": conv3x3_c64, "halo16": conv3x3_halo16) <- value (0 off, 1 the measured default
  * rule, 2 wherever the kernel can run; < 0: back to the default rule 1).  "nn128" (scripts/probe_pair_dgrad.py): 2 = the K-major GEMM
- * (ipoke_conv_desc.w_kmajor) on its 128 x 128 tile whatever M, instead of the 80- / 160-row tiles the cost rule picks. */
+ * (ipoke_conv_desc.w_kmajor) on its 128 x 128 tile whatever M, instead of the 80- / 160-row tiles the cost rule picks.  "nt128"
+ * (scripts/probe_pair_coupling.py): the same for the wide N-major GEMMs (Nout > 64): the 128 x 128 tile with one K pass, i.e. the tile
+ * and the K order of ipoke_conv_pair_coupling.  "cpl_split" <- 4 / 8 / 16 / 32: ipoke_conv3x3_coupling runs that many K slices where
+ * tiles x slices <= 256 and slices <= Kc / 64 (< 0: back to its rule, which picks by M) -- with hidden / 128 the slices of
+ * ipoke_conv_pair_coupling, at any M. */
 int ipoke_set_dispatch_override(const char* name, int value);
-/* Test hook: the kernel family the calling thread's last ipoke_conv_forward was dispatched to (ipoke_conv_pair_dgrad reports IPOKE_KERNEL_IGEMM) */
+/* Test hook: the kernel family the calling thread's last ipoke_conv_forward was dispatched to (ipoke_conv_pair_dgrad and ipoke_conv_pair_coupling report IPOKE_KERNEL_IGEMM) */
 enum { IPOKE_KERNEL_NONE = 0, IPOKE_KERNEL_IGEMM = 1, IPOKE_KERNEL_S8 = 2, IPOKE_KERNEL_HALO = 3, IPOKE_KERNEL_HALO16 = 4, IPOKE_KERNEL_C64 = 5, IPOKE_KERNEL_K8 = 6 };
 int ipoke_last_conv_kernel(void);
 /* Test hook: the weight-gradient kernel the calling thread's last ipoke_conv_wgrad / ipoke_conv_wgrad_batched was dispatched to
@@ -33,8 +37,8 @@ int ipoke_spin_delay(int us, void* stream);
 
 /* In-situ timing for the benchmark's roofline objects: between ipoke_timing_start() and ipoke_timing_stop() every launch of
  * a tagged kernel family is bracketed by HIP events on the stream it is launched on (the rest of the step runs as usual).
- * Tags: 1 = ipoke_conv_forward with a 1x1 kernel and Nout = K >= 1024 (the NICE conv2 GEMM; its data gradient too unless that is
- *       read from the K-major weight: tag 6),
+ * Tags: 1 = ipoke_conv_forward with a 1x1 kernel and Nout = K >= 1024 (the NICE conv2 GEMM -- where ipoke_conv_pair_coupling takes it, that
+ *       launch, i.e. conv2 + conv3 + coupling; its data gradient too unless that is read from the K-major weight: tag 6),
  *       2 = ipoke_conv_wgrad / _batched of the same shape (a batched launch counts once per problem and its time is divided
  *       by the problem count), 3 = ipoke_macow_unit_fwd, 4 = ipoke_macow_unit_bwd. */
 #define IPOKE_TAG_NT_SQUARE 1
@@ -66,6 +70,11 @@ int ipoke_flow_test_inject_timeout(ipoke_flow* f, int which, void* stream);
  * even where ipoke_conv_pair_dgrad applies, the second with that kernel's slices (splitk = hidden / 128): every gradient must come out
  * bit-identical (the parity test of the fused launch); 0: back to the default.  Drops the handle's captured graphs. */
 int ipoke_flow_test_split_pair_dgrad(ipoke_flow* f, int on);
+/* Test hook: on != 0 makes the flow's forward and reverse passes issue conv2 and conv3 + coupling of every coupling net as two launches
+ * even where ipoke_conv_pair_coupling applies -- conv2 on the 128 x 128 tile ("nt128"), the second launch at hidden / 128 slices
+ * ("cpl_split"; the engine sets and clears both switches around its launches while the hook is on): every state, log-det and
+ * gradient must come out bit-identical (the parity test of the fused launch); 0: back to the default.  Drops the handle's captured graphs. */
+int ipoke_flow_test_split_pair_coupling(ipoke_flow* f, int on);
 
 /* Test hook: forward unroll of the ConvGRU as one launch (1), as launches per phase (0), or the IPOKE_GRU_FUSED environment default (< 0) */
 int ipoke_gru_set_fused(int mode);

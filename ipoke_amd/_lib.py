@@ -156,6 +156,8 @@ SIGNATURES = {
     "ipoke_conv3x3_skinny_splitk": (c_int, [c_int, c_int, c_int]),
     "ipoke_conv_pair_dgrad": (c_int, [POINTER(ConvDesc), POINTER(ConvDesc), c_int, _P]),
     "ipoke_conv_pair_dgrad_applicable": (c_int, [c_int, c_int, c_int, c_int, c_int64]),
+    "ipoke_conv_pair_coupling": (c_int, [POINTER(ConvDesc), POINTER(ConvDesc), POINTER(AffineDesc), POINTER(CouplingEpi), c_int, c_int, _P]),
+    "ipoke_conv_pair_coupling_applicable": (c_int, [c_int, c_int, c_int, c_int]),
     "ipoke_conv3x3_coupling_splitk": (c_int, [c_int, c_int, c_int]),
     "ipoke_conv3x3_coupling_xchg_bytes": (c_int64, []),
     "ipoke_conv3x3_coupling_xchg_init": (c_int, [_P, _P]),
@@ -308,6 +310,7 @@ SIGNATURES = {
     "ipoke_flow_side_stream": (c_void_p, [_P]),
     "ipoke_flow_test_inject_timeout": (c_int, [_P, c_int, _P]),
     "ipoke_flow_test_split_pair_dgrad": (c_int, [_P, c_int]),
+    "ipoke_flow_test_split_pair_coupling": (c_int, [_P, c_int]),
     "ipoke_conv_wgrad_splitm": (c_int, [_P, c_int, c_int]),
     "ipoke_conv_acc_scratch_bytes": (c_int64, [c_int, c_int, c_int]),
     "ipoke_conv_acc_scratch_init": (c_int, [_P, _P]),
@@ -394,7 +397,9 @@ WGRAD_NONE, WGRAD_TN, WGRAD_TN_GLDS, WGRAD_TN_NARROW, WGRAD_LAT8, WGRAD_HALO = r
 def dispatch_override(name, value):
     """Test hook: run a block with the kernel-dispatch switch ``name`` ("c64" | "halo16") at ``value`` (0 off, 1 the measured default
     rule, 2 wherever the kernel can run), then return it to the process default (ipoke_set_dispatch_override).  "nn128" at 2 (probe
-    scripts only): every K-major GEMM of the process on its 128 x 128 tile instead of the tile the cost rule picks."""
+    scripts only): every K-major GEMM of the process on its 128 x 128 tile instead of the tile the cost rule picks; "nt128" at 2: the same for
+    the wide N-major GEMMs (one K pass); "cpl_split" at 4 / 8 / 16 / 32: that many K slices in ipoke_conv3x3_coupling where they fit --
+    together the two launches ipoke_conv_pair_coupling is bit-identical to."""
     check(lib().ipoke_set_dispatch_override(name.encode(), int(value)))
     try:
         yield

@@ -130,6 +130,7 @@ struct ipoke_flow {
   // scratch of the deterministic split-K accumulation of the conv1 data gradients (ipoke_conv_desc.acc_scratch; the chain's stream only)
   void* d_acc = nullptr; int64_t acc_bytes = 0;
   bool split_pair_dgrad = false;      // test hook (ipoke_flow_test_split_pair_dgrad): conv2's and conv1's data gradients as two launches
+  bool split_pair_coupling = false;   // test hook (ipoke_flow_test_split_pair_coupling): conv2 and conv3 + coupling as two launches
   unsigned* h_tmo = nullptr; hipEvent_t pass_ev = nullptr; hipStream_t pass_stream = nullptr; bool pass_recorded = false, pass_unchecked = false;
   int64_t xchg_bytes = 0;
   // every masked-conv layer is differentiated inside a fused MaCowUnit launch, which also writes the layer's input in the matrix
@@ -577,7 +578,21 @@ void nice_conv3_desc(const Ctx& c, const Op& op, void* h2, ipoke_conv_desc& d) {
 bool nice_fused(const Ctx& c, const Op& op) {
   return c.f->coupling_fuse && c.f->d_cxchg && ipoke_conv3x3_coupling_splitk((int)c.M, op.hidK, c.dtype) > 0;
 }
-int nice_net(const Ctx& c, const Op& op, const float* in, void* h1, void* h2, void* zc, bool zc_ready = false, bool with_conv3 = true) {
+// conv2, conv3 AND the coupling transform of this net run as one launch (ipoke_conv_pair_coupling) at this batch size
+bool nice_pair(const Ctx& c, const Op& op) {
+  return nice_fused(c, op) && op.hidK == c.f->cfg.hidden &&
+         ipoke_conv_pair_coupling_applicable((int)c.M, c.f->cfg.hidden, 2 * op.cout, c.dtype) != 0;
+}
+void nice_conv2_desc(const Ctx& c, const Op& op, const void* h1, void* h2, ipoke_conv_desc& d) {
+  const int hid = c.f->cfg.hidden;
+  set_conv8(d, c.B, 1, 0);
+  set_a_dense(d, h1, hid, hid);
+  d.W = c.sh(op.sh_c2); d.ldw = hid; d.Nout = hid; d.act = IPOKE_ACT_ELU; d.C = h2; d.ldc = op.hidK;
+}
+// conv2: 1 the dispatcher's launch, 0 none (the caller's ipoke_conv_pair_coupling takes it, with conv3), 2 on the 128 x 128 tile (the
+// two-launch form of the parity hook ipoke_flow_test_split_pair_coupling)
+int nice_net(const Ctx& c, const Op& op, const float* in, void* h1, void* h2, void* zc, bool zc_ready = false, bool with_conv3 = true,
+             int conv2 = 1) {
   const int hid = c.f->cfg.hidden;
   ipoke_conv_desc d;
   if (!zc_ready) {
@@ -588,10 +603,12 @@ int nice_net(const Ctx& c, const Op& op, const float* in, void* h1, void* h2, vo
   set_a_dense(d, zc, op.Kc1, op.Kc1);
   d.W = c.sh(op.sh_c1); d.ldw = 9 * op.Kc1; d.Nout = hid; d.act = IPOKE_ACT_ELU; d.C = h1; d.ldc = hid;
   int rc = ipoke_conv_forward(&d, c.dtype, c.stream()); if (rc) return rc;
-  set_conv8(d, c.B, 1, 0);
-  set_a_dense(d, h1, hid, hid);
-  d.W = c.sh(op.sh_c2); d.ldw = hid; d.Nout = hid; d.act = IPOKE_ACT_ELU; d.C = h2; d.ldc = op.hidK;
-  rc = ipoke_conv_forward(&d, c.dtype, c.stream()); if (rc) return rc;
+  if (conv2 == 0) return IPOKE_OK;
+  nice_conv2_desc(c, op, h1, h2, d);
+  if (conv2 == 2) { rc = ipoke_set_dispatch_override("nt128", 2); if (rc) return rc; }
+  rc = ipoke_conv_forward(&d, c.dtype, c.stream());
+  if (conv2 == 2) (void)ipoke_set_dispatch_override("nt128", -1);
+  if (rc) return rc;
   if (op.hidK > hid) {      // condition_nice: ELU(cat[conv2 out, h]) = [ELU(conv2 out) | ELU(h)], the second half is the shared activated map
     rc = ipoke_copy_cols(c.cond(), c.f->cfg.cond_channels, static_cast<unsigned char*>(h2) + (size_t)hid * c.f->esz, op.hidK,
                          c.f->cfg.cond_channels, c.M, c.dtype, c.stream());
@@ -600,6 +617,20 @@ int nice_net(const Ctx& c, const Op& op, const float* in, void* h1, void* h2, vo
   if (!with_conv3) return IPOKE_OK;
   nice_conv3_desc(c, op, h2, d);
   return ipoke_conv_forward(&d, c.dtype, c.stream());
+}
+// conv3 + coupling behind nice_net: the one launch that also takes conv2 (pair), or ipoke_conv3x3_coupling -- at the slices of the former when
+// the parity hook asks for the two launches (split)
+int nice_coupling(const Ctx& c, const Op& op, bool pair, bool split, const void* h1, void* h2, bool store_h2, const ipoke_affine_desc& a,
+                  const ipoke_coupling_epi& e) {
+  ipoke_conv_desc d3; nice_conv3_desc(c, op, h2, d3);
+  if (pair && !split) {
+    ipoke_conv_desc d2; nice_conv2_desc(c, op, h1, store_h2 ? h2 : nullptr, d2);
+    return ipoke_conv_pair_coupling(&d2, &d3, &a, &e, c.B, c.dtype, c.stream());
+  }
+  if (pair) { int rc = ipoke_set_dispatch_override("cpl_split", c.f->cfg.hidden / 128); if (rc) return rc; }
+  const int rc = ipoke_conv3x3_coupling(&d3, &a, &e, c.B, c.dtype, c.stream());
+  if (pair) (void)ipoke_set_dispatch_override("cpl_split", -1);
+  return rc;
 }
 void nice_affine_desc(const Ctx& c, const Op& op, ipoke_affine_desc& a) {
   a.raw = c.partials(); a.nsplit = nice_splitk(c); a.split_stride = c.M * 64; a.ldraw = 64;
@@ -1259,6 +1290,13 @@ extern "C" int ipoke_flow_test_split_pair_dgrad(ipoke_flow* f, int on) {
   drop_graphs(f);      // captured passes hold the other form
   return IPOKE_OK;
 }
+/* Test hook (include/ipoke_hip_dev.h): the two-launch form of the coupling nets' conv2 and conv3 + coupling */
+extern "C" int ipoke_flow_test_split_pair_coupling(ipoke_flow* f, int on) {
+  IPK_REQUIRE(f != nullptr, "null flow handle");
+  f->split_pair_coupling = on != 0;
+  drop_graphs(f);      // captured passes hold the other form
+  return IPOKE_OK;
+}
 /* Synchronising query: waits for the last pass of this flow and writes the hand-off time-out counts since the scratches were last
  * (re-)initialised: out[0] row-split MaCowUnit launches, out[1] fused conv3 + coupling launches.  Returns IPOKE_OK; non-zero counts
  * mean that a pass finished on garbage (the next entry point fails with IPOKE_ERR_STATE and re-initialises the scratches). */
@@ -1360,7 +1398,8 @@ static int run_forward(ipoke_flow* f, const float* params, const int32_t* perm, 
         void* zc = save ? l.rows(op.ws_g, (int64_t)op.Kc1 * f->esz) : l.rows(l.plan.tmp_zc, 64L * f->esz);
         const bool have_zc = (i > 0 && nice_feeds(f->ops[i - 1], op)) || (!init && unit_feeds(f, i));
         const bool one_launch = !init && nice_fused(l, op);
-        rc = nice_net(l, op, in, h1, h2, zc, have_zc, !one_launch); if (rc) return rc;
+        const bool pair = one_launch && nice_pair(l, op), split = pair && f->split_pair_coupling;
+        rc = nice_net(l, op, in, h1, h2, zc, have_zc, !one_launch, pair ? (split ? 2 : 0) : 1); if (rc) return rc;
         ipoke_affine_desc a; nice_affine_desc(l, op, a);
         void* ext = nullptr; int ext_ld = 0;
         if (i + 1 < f->ops.size() && nice_feeds(op, f->ops[i + 1])) {
@@ -1369,7 +1408,6 @@ static int run_forward(ipoke_flow* f, const float* params, const int32_t* perm, 
           ext_ld = nx.Kc1;
         }
         if (one_launch) {
-          ipoke_conv_desc d3; nice_conv3_desc(l, op, h2, d3);
           ipoke_coupling_epi e; std::memset(&e, 0, sizeof(e));
           e.mode = with_an ? 1 : 0; e.in = in; e.scale_out = save ? l.rowsf(op.ws_c, op.cout) : nullptr;
           e.logdet_slot = l.slot(op.slot); e.slot_stride = 4; e.xchg = f->d_cxchg;
@@ -1381,7 +1419,7 @@ static int run_forward(ipoke_flow* f, const float* params, const int32_t* perm, 
           } else {
             e.out = out; e.ext = ext; e.ext_ld = ext_ld;
           }
-          rc = ipoke_conv3x3_coupling(&d3, &a, &e, l.B, l.dtype, l.stream());
+          rc = nice_coupling(l, op, pair, split, h1, h2, true, a, e);      // (h2 is stored: the backward pass reads it)
         } else if (with_an) {
           const Op& an = f->ops[op.an_next];
           rc = ipoke_affine_actnorm_fwd(&a, in, save ? l.state((int)i + 1) : nullptr, out, save ? l.rowsf(op.ws_c, op.cout) : nullptr,
@@ -1503,18 +1541,19 @@ static int run_reverse(ipoke_flow* f, const float* params, const int32_t* perm, 
         // the conditioning channels are untouched by the coupling, so the net sees the same input as in forward
         const bool have_zc = i + 1 < (int)f->ops.size() && (nice_feeds(f->ops[i + 1], op) || actnorm_feeds(i + 1));     // written by the layer inverted just before this one
         const bool one_launch = nice_fused(l, op);
+        const bool pair = one_launch && nice_pair(l, op), split = pair && f->split_pair_coupling;
+        void* h1 = l.rows(l.plan.tmp_h1, hb);
         void* h2 = l.rows(l.plan.tmp_h2, (int64_t)op.hidK * f->esz);
-        rc = nice_net(l, op, in, l.rows(l.plan.tmp_h1, hb), h2, l.rows(l.plan.tmp_zc, 64L * f->esz), have_zc, !one_launch);
+        rc = nice_net(l, op, in, h1, h2, l.rows(l.plan.tmp_zc, 64L * f->esz), have_zc, !one_launch, pair ? (split ? 2 : 0) : 1);
         if (rc) return rc;
         ipoke_affine_desc a; nice_affine_desc(l, op, a);
         const bool feed = i > 0 && nice_feeds(op, f->ops[i - 1]);
         void* ext = feed ? l.rows(l.plan.tmp_zc, 64L * f->esz) : nullptr;
         const int ext_ld = feed ? f->ops[i - 1].Kc1 : 0;
         if (one_launch) {
-          ipoke_conv_desc d3; nice_conv3_desc(l, op, h2, d3);
           ipoke_coupling_epi e; std::memset(&e, 0, sizeof(e));
           e.mode = 2; e.in = in; e.out = out; e.ext = ext; e.ext_ld = ext_ld; e.xchg = f->d_cxchg;
-          rc = ipoke_conv3x3_coupling(&d3, &a, &e, l.B, l.dtype, l.stream());
+          rc = nice_coupling(l, op, pair, split, h1, h2, false, a, e);     // (nothing reads h2 behind this launch: not stored)
         } else {
           rc = ipoke_affine_inv_ext(&a, in, out, l.B, ext, ext_ld, l.dtype, l.stream());
         }

@@ -1185,8 +1185,10 @@ static void pick_xcd_map(NtParams& p) {
 // the same hand-over sums -- tests/test_pair_dgrad_gpu.py compares them bit for bit and fails when they diverge.
 //
 // NSPLIT > 0 (conv3x3_s8_coupling_kernel): the K splits of a row tile meet INSIDE the launch and the coupling transform the
-// convolution feeds (affine_fwd / affine_actnorm_fwd / affine_inv of elementwise.hip) runs in the same launch -- see the tail
-// of the body.
+// convolution feeds (affine_fwd / affine_actnorm_fwd / affine_inv of elementwise.hip) runs in the same launch -- CouplingTail below,
+// which igemm_nt_coupling_kernel (further down: conv2's GEMM in front of a COPY of this body's K-block loop, the input image taken
+// from LDS) shares.  That copy must keep the K-block order and the four-group sum of this body: tests/test_pair_coupling_gpu.py
+// compares the two bit for bit.
 struct CouplingEpi {
   const float* bias; const float* in; float* out; float* out2; float* scale_out; float* logdet_slot;
   const float* an_ls; const float* an_bias; const int* an_idx; void* ext; void* xchg;
@@ -1202,128 +1204,46 @@ static constexpr unsigned kCplSpinMax = 1u << 21;
 #else
 #define S8_STAMP(i) do {} while (0)
 #endif
-// NREP = 2: 32 output columns (the conv1 data gradient of a coupling that conditions on <= 32 channels): half the filter ring --
-// 88 KB of LDS instead of 137, which fits beside ONE resident weight-gradient workgroup instead of waiting for a whole CU -- and
-// half the matrix-core work.
-template <int NSPLIT, int NREP = 4>
-__device__ __forceinline__ void conv3x3_s8_body(const NtParams& p, const CouplingEpi& e, const int tile, const int z) {
-  typedef bf16_t T;
-  typedef typename ET<T>::frag frag_t;
-  typedef __attribute__((address_space(3))) void lds_void;
-  typedef const __attribute__((address_space(1))) void glb_void;
-  constexpr int BM = 128, BN = 16 * NREP, NTHR = 512, R = 12;     // ring: three rounds of four filter K-blocks
-  constexpr int ABUF = BM * 128, WSLOT = BN * 128;
-  constexpr int A_IT = BM * 8 / NTHR;                      // DMA instructions per thread and input chunk (2)
-  constexpr int MREP = 4;
-  constexpr int WJ = BN / 16;                              // filter DMA instructions per wave and round (8 rows each)
-  constexpr int EP = BN * 4 + 16;                          // nt_epilogue's staging pitch
-  constexpr unsigned kInvalid = 0xffffffffu;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* abuf = smem;                              // 2 x ABUF: the input chunk, double-buffered
-  unsigned char* zrow = smem + 2 * ABUF;                   // 256 bytes of zeros: the "outside the map" row
-  unsigned char* ring = zrow + 256;                        // R filter K-blocks
-  unsigned char* dummy = ring + R * WSLOT;                 // landing zone of padding DMAs, 1 KB per wave
-  S8_STAMP(0);
-  if (p.prio == 1) __builtin_amdgcn_s_setprio(1); else if (p.prio == 2) __builtin_amdgcn_s_setprio(2); else if (p.prio == 3) __builtin_amdgcn_s_setprio(3);
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int mh = wave & 1, kq = wave >> 1;
-  const GeomDev& g = p.g;
-  const int m0 = tile * BM;
-  const int nchunks = p.Kc >> 6;
-  const int c_begin = z * p.kb_per_split, c_end = min(nchunks, c_begin + p.kb_per_split);
-  const int nch = max(0, c_end - c_begin), nkb = nch * 9, nrounds = (nkb + 3) >> 2;
-  const int sgn = g.transposed ? -1 : 1;
-
-  if (tid < 16) reinterpret_cast<f32x4*>(zrow)[tid] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const T* Abase = reinterpret_cast<const T*>(p.A);
-  const T* Wbase = reinterpret_cast<const T*>(p.W);
-  const T* zero = reinterpret_cast<const T*>(g_zero_chunk);
-  unsigned a_src[A_IT];
-#pragma unroll
-  for (int i = 0; i < A_IT; ++i) {
-    const int ch = (wave + 8 * i) * 64 + lane, row = ch >> 3, pos = ch & 7, m = m0 + row;
-    a_src[i] = kInvalid;
-    if (m < g.M) {
-      const long off = (long)(m >> 6) * p.a_sn + (long)((m >> 3) & 7) * p.a_sh + (long)(m & 7) * p.a_sw + p.a_coff;
-      a_src[i] = (unsigned)(off + c_begin * 64 + ((pos ^ ((row >> 1) & 7)) * 8));
-    }
+// The coupling side of a fused launch: what conv3x3_s8_coupling_kernel and igemm_nt_coupling_kernel do around and behind the K loop of the
+// skinny convolution.  ONE piece of code for both (tests/test_pair_coupling_gpu.py compares the two launches bit for bit): prefetch()
+// ahead of the K loop, pin() behind the loop's last wait for vector memory, run() with the accumulators of the four K groups of the
+// [128 rows x 64 columns] tile.
+template <int NSPLIT>
+struct CouplingTail {
+  static constexpr int BM = 128, NTHR = 512, MREP = 4, NREP = 4, EP = 16 * NREP * 4 + 16;
+  static constexpr int NOWN = NSPLIT == 0 ? 1 : (NSPLIT < 8 ? NSPLIT : 8), RPO = BM / NOWN;   // owners per tile, rows per owner (16 or 32)
+  static constexpr int SLOT = RPO * 256;                                                      // one sender's rows for one owner, bytes
+  static constexpr int NSL = RPO / 16;                                                        // 16-row slices per owner (1 or 2)
+  // one slice per owner (NSPLIT >= 8): both halves of the workgroup share its elements (element u of thread t256 of the 256-thread
+  // affine kernels goes to half u); two slices (NSPLIT = 4): a half per slice, two elements per thread
+  static constexpr int NU = NSL == 1 ? 1 : 2;                 // transformed elements per thread (Cp <= 32)
+  static constexpr int NC = NSL == 1 ? 2 : 4;                 // copied (untouched) elements per thread (ld <= 64)
+  const CouplingEpi& e;
+  bool owner, valid, with_an, col_fixed; int hf, t256, u0, ld, Cp, an_src; long row0; float an_e, an_b;
+  float pre_c[NC], pre_t[NU]; f32x4 pre_bias;
+  __device__ __forceinline__ explicit CouplingTail(const CouplingEpi& e_) : e(e_) {}
+  __device__ __forceinline__ void div_ld(int i, int& q, int& r) const { if (e.ld_sh >= 0) { q = i >> e.ld_sh; r = i & (ld - 1); } else { q = i / ld; r = i - q * ld; } }
+  __device__ __forceinline__ void div_cp(int i, int& q, int& r) const { if (e.cp_sh >= 0) { q = i >> e.cp_sh; r = i & (Cp - 1); } else { q = i / Cp; r = i - q * Cp; } }
+  __device__ __forceinline__ bool is_transformed(int col) const {
+    const int rel = col - e.t_off;
+    if (e.ts_sh >= 0) return rel >= 0 && (rel & (e.t_stride - 1)) == 0 && (rel >> e.ts_sh) < Cp;
+    return rel >= 0 && rel % e.t_stride == 0 && rel / e.t_stride < Cp;
   }
-  // filter DMA of a round: wave w brings rows 32*(w >> 2) .. +31 (4 instructions of 8 rows) of K-block 4r + (w & 3)
-  unsigned w_src[WJ];
-#pragma unroll
-  for (int j = 0; j < WJ; ++j) {
-    const int n = 8 * WJ * (wave >> 2) + 8 * j + (lane >> 3), pos = lane & 7;
-    w_src[j] = n < p.Nout ? (unsigned)((long)n * p.ldw + c_begin * 64 + ((pos ^ ((n >> 1) & 7)) * 8)) : kInvalid;
-  }
-  int wi_g = wave & 3, wi_c = 0, wi_t = wave & 3;          // K-block index / (chunk, tap) of this wave's next filter request
-  auto issue_w = [&]() {
-    const bool in = wi_g < nkb;
-#pragma unroll
-    for (int j = 0; j < WJ; ++j) {
-#if defined(IPOKE_GEMM_STAMPS) && IPOKE_GEMM_ABL == 3
-      continue;
-#endif
-#if defined(IPOKE_GEMM_STAMPS) && IPOKE_GEMM_ABL == 2
-      const bool real = false;
-#else
-      const bool real = in && w_src[j] != kInvalid;
-#endif
-      const T* src = real ? Wbase + w_src[j] + (long)wi_t * p.Kc + wi_c * 64 : zero;
-      unsigned char* dst = in ? ring + (wi_g % R) * WSLOT + (WJ * (wave >> 2) + j) * 1024 : dummy + wave * 1024;
-      __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)dst, 16, 0, 0);
-    }
-    wi_g += 4; wi_t += 4;
-    if (wi_t >= 9) { wi_t -= 9; ++wi_c; }
-  };
-  int a_next = 0;                                          // next input chunk to request
-  auto issue_a = [&]() {
-#pragma unroll
-    for (int i = 0; i < A_IT; ++i) {
-#if defined(IPOKE_GEMM_STAMPS) && IPOKE_GEMM_ABL == 3
-      continue;
-#endif
-#if defined(IPOKE_GEMM_STAMPS) && IPOKE_GEMM_ABL == 2
-      const bool real = false;
-#else
-      const bool real = a_next < nch && a_src[i] != kInvalid;
-#endif
-      const T* src = real ? Abase + a_src[i] + a_next * 64 : zero;
-      unsigned char* dst = a_next < nch ? abuf + (a_next & 1) * ABUF + (wave + 8 * i) * 1024 : dummy + wave * 1024;
-      __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)dst, 16, 0, 0);
-    }
-    ++a_next;
-  };
   // fused launch: what the coupling at the end needs besides the convolution's sums is requested NOW, ahead of the K loop -- the
   // slice's state rows, the bias and the ActNorm parameters of this thread's column (otherwise three dependent round trips behind
   // the hand-off).  Index arithmetic: shifts when ld / Cp / t_stride are powers of two (the integer-division sequences of the
   // general path cost the affine kernels ~1 us per launch).
-  constexpr int NOWN = NSPLIT == 0 ? 1 : (NSPLIT < 8 ? NSPLIT : 8), RPO = BM / NOWN;   // owners per tile, rows per owner (16 or 32)
-  constexpr int SLOT = RPO * 256;                                                      // one sender's rows for one owner, bytes
-  constexpr int NSL = RPO / 16;                                                        // 16-row slices per owner (1 or 2)
-  // one slice per owner (NSPLIT >= 8): both halves of the workgroup share its elements (element u of thread t256 of the 256-thread
-  // affine kernels goes to half u); two slices (NSPLIT = 4): a half per slice, two elements per thread
-  constexpr int NU = NSL == 1 ? 1 : 2;                 // transformed elements per thread (Cp <= 32)
-  constexpr int NC = NSL == 1 ? 2 : 4;                 // copied (untouched) elements per thread (ld <= 64)
-  const bool owner = NSPLIT > 0 && z < NOWN;
-  const int hf = tid >> 8, t256 = tid & 255;
-  const int u0 = NSL == 1 ? hf : 0;                    // first element index (of the 256-thread numbering) this thread handles
-  const long row0 = (long)m0 + z * RPO + (NSL == 1 ? 0 : hf * 16);                     // first state row of this thread's slice
-  const bool valid = owner && row0 < g.M;
-  const bool with_an = e.mode == 1;
-  const int ld = e.ld, Cp = e.Cp;
-  auto div_ld = [&](int i, int& q, int& r) { if (e.ld_sh >= 0) { q = i >> e.ld_sh; r = i & (ld - 1); } else { q = i / ld; r = i - q * ld; } };
-  auto div_cp = [&](int i, int& q, int& r) { if (e.cp_sh >= 0) { q = i >> e.cp_sh; r = i & (Cp - 1); } else { q = i / Cp; r = i - q * Cp; } };
-  auto is_transformed = [&](int col) {
-    const int rel = col - e.t_off;
-    if (e.ts_sh >= 0) return rel >= 0 && (rel & (e.t_stride - 1)) == 0 && (rel >> e.ts_sh) < Cp;
-    return rel >= 0 && rel % e.t_stride == 0 && rel / e.t_stride < Cp;
-  };
-  float pre_c[NC], pre_t[NU];
-  f32x4 pre_bias = f32x4{0.f, 0.f, 0.f, 0.f};
-  bool col_fixed = false; int an_src = 0; float an_e = 1.f, an_b = 0.f;
-  if constexpr (NSPLIT > 0) {
+  __device__ __forceinline__ void prefetch(const int M, const int m0, const int z) {
+    const int tid = threadIdx.x;
+    owner = NSPLIT > 0 && z < NOWN;
+    hf = tid >> 8; t256 = tid & 255;
+    u0 = NSL == 1 ? hf : 0;                              // first element index (of the 256-thread numbering) this thread handles
+    row0 = (long)m0 + z * RPO + (NSL == 1 ? 0 : hf * 16);                           // first state row of this thread's slice
+    valid = owner && row0 < M;
+    with_an = e.mode == 1;
+    ld = e.ld; Cp = e.Cp;
+    pre_bias = f32x4{0.f, 0.f, 0.f, 0.f};
+    col_fixed = false; an_src = 0; an_e = 1.f; an_b = 0.f;
 #pragma unroll
     for (int u = 0; u < NC; ++u) pre_c[u] = 0.f;
 #pragma unroll
@@ -1356,91 +1276,9 @@ __device__ __forceinline__ void conv3x3_s8_body(const NtParams& p, const Couplin
       for (int q = 0; q < 4; ++q) if (j + q < 2 * Cp) pre_bias[q] = e.bias[j + q];
     }
   }
-  issue_a();                 // chunk 0
-  issue_w(); issue_w();      // rounds 0 and 1
-
-  // fragment bookkeeping: row r of the tile is position (y, x) = ((r >> 3) & 7, r & 7) of sample r >> 6
-  unsigned vmask[MREP];
-#pragma unroll
-  for (int i = 0; i < MREP; ++i) {
-    const int r = i * 16 + (lane & 15);                    // row inside this wave's sample (mh)
-    const int y = (r >> 3) & 7, x = r & 7;
-    unsigned vm = 0;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      const int yy = y + sgn * (t / 3 - 1), xx = x + sgn * (t % 3 - 1);
-      if ((unsigned)yy < 8u && (unsigned)xx < 8u) vm |= 1u << t;
-    }
-    vmask[i] = vm;
-  }
-  const int qlo = lane >> 4;
-  int b_rd[NREP];                                          // half-step 0; half-step 1 is the chunk position ^ 4, i.e. byte offset ^ 64
-#pragma unroll
-  for (int j = 0; j < NREP; ++j) {
-    const int n = j * 16 + (lane & 15);
-    b_rd[j] = n * 128 + ((qlo ^ ((n >> 1) & 7)) * 16);
-  }
-  f32x4 acc[MREP][NREP];
-#pragma unroll
-  for (int i = 0; i < MREP; ++i)
-#pragma unroll
-    for (int j = 0; j < NREP; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  int gk = kq, ci = 0, t = kq;                             // this wave's K-block of the round: index, chunk, tap
-  for (int r = 0; r < nrounds; ++r) {
-    wait_vmcnt<WJ>();                // everything but this wave's share of round r + 1 has landed (input chunks included)
-    __builtin_amdgcn_s_barrier();
-    if (r == 0) S8_STAMP(1);
-    // the first K-block of this round lies in chunk (4r)/9: request the chunk after it once (its buffer held chunk - 1,
-    // whose last K-block was consumed before this barrier)
-    if (a_next <= (4 * r) / 9 + 1) issue_a();          // (issued before the filter blocks: the wait above counts those only)
-    issue_w();                       // round r + 2 into the slots of round r - 1
-    if (gk < nkb) {
-      const unsigned char* ab = abuf + (ci & 1) * ABUF + mh * 64 * 128;
-      const unsigned char* wb = ring + (gk % R) * WSLOT;
-      const int th = t / 3, tw = t - 3 * th;
-      const int shift = sgn * ((th - 1) * 8 + (tw - 1));
-      const unsigned char* arow[MREP]; int aswz[MREP];
-#pragma unroll
-      for (int i = 0; i < MREP; ++i) {
-        const bool ok = (vmask[i] >> t) & 1u;
-        const int sr = i * 16 + (lane & 15) + shift;       // row inside the sample
-        arow[i] = ok ? ab + sr * 128 : zrow;
-        aswz[i] = ok ? (sr >> 1) & 7 : 0;
-      }
-      frag_t fa[2][MREP], fb[2][NREP];
-#pragma unroll
-      for (int hs = 0; hs < 2; ++hs) {
-#pragma unroll
-        for (int i = 0; i < MREP; ++i) fa[hs][i] = *reinterpret_cast<const frag_t*>(arow[i] + (((hs * 4 + qlo) ^ aswz[i]) * 16));
-#pragma unroll
-        for (int j = 0; j < NREP; ++j) fb[hs][j] = *reinterpret_cast<const frag_t*>(wb + (b_rd[j] ^ (hs * 64)));
-      }
-#pragma unroll
-      for (int hs = 0; hs < 2; ++hs)
-#pragma unroll
-        for (int i = 0; i < MREP; ++i)
-#pragma unroll
-          for (int j = 0; j < NREP; ++j) GEMM_MMA(fa[hs][i], fb[hs][j], acc[i][j]);
-      // issue order: the eight fragments of the first half-step, then the second half-step's reads one per two MFMAs of the first.
-      // (hipcc's own schedule reads just in time, four MFMAs per s_waitcnt lgkmcnt(0): eight exposed LDS latencies per K-block.)
-      constexpr int NF = MREP + NREP, NM = MREP * NREP, PER = NM / NF;        // fragment reads / MFMAs per half-step
-      __builtin_amdgcn_sched_group_barrier(0x100, NF, 0);
-#pragma unroll
-      for (int q = 0; q < NF; ++q) {
-        __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, 2 * NM - NF * PER, 0);
-    }
-    gk += 4; t += 4;
-    if (t >= 9) { t -= 9; ++ci; }
-  }
-  wait_vmcnt<0>();
-  S8_STAMP(2);
-  if constexpr (NSPLIT > 0) {
-    // the values requested ahead of the K loop have landed: pin that here, so that no use further down waits on the vector-memory
-    // counter (which by then also counts the hand-off's write-through stores)
+  // the values requested ahead of the K loop have landed: pin that (behind a wait for vmcnt(0)), so that no use further down waits on
+  // the vector-memory counter (which by then also counts the hand-off's write-through stores)
+  __device__ __forceinline__ void pin() {
 #pragma unroll
     for (int u = 0; u < NC; ++u) asm volatile("" : "+v"(pre_c[u]));
 #pragma unroll
@@ -1448,34 +1286,10 @@ __device__ __forceinline__ void conv3x3_s8_body(const NtParams& p, const Couplin
     asm volatile("" : "+v"(pre_bias));
     asm volatile("" : "+v"(an_src), "+v"(an_e), "+v"(an_b));
   }
-  if constexpr (NSPLIT == 0) {
-  // the four K groups meet: groups 2, 3 hand over to groups 0, 1, then group 1 to group 0 (nt_epilogue's staging layout)
-  {
-    unsigned char* st = smem + (mh * MREP * 16 + (lane & 15)) * EP + (lane >> 4) * 16;
-    __syncthreads();                 // the ring and the input buffers are dead
-#pragma unroll
-    for (int round = 0; round < 2; ++round) {
-      const int give_lo = round == 0 ? 2 : 1, take_hi = round == 0 ? 2 : 1;      // givers: kq in [give_lo, 2*give_lo); takers: kq < take_hi
-      if (kq >= give_lo && kq < 2 * give_lo) {
-        unsigned char* d = st + (kq - give_lo) * BM * EP;
-#pragma unroll
-        for (int i = 0; i < MREP; ++i)
-#pragma unroll
-          for (int j = 0; j < NREP; ++j) *reinterpret_cast<f32x4*>(d + i * 16 * EP + j * 64) = acc[i][j];
-      }
-      __syncthreads();
-      if (kq < take_hi) {
-        const unsigned char* d = st + kq * BM * EP;
-#pragma unroll
-        for (int i = 0; i < MREP; ++i)
-#pragma unroll
-          for (int j = 0; j < NREP; ++j) acc[i][j] += *reinterpret_cast<const f32x4*>(d + i * 16 * EP + j * 64);
-      }
-      if (round == 0) __syncthreads();
-    }
-  }
-  nt_epilogue<T, 2, 1, MREP, NREP, NTHR, true>(p, acc, smem, m0, 0, mh, 0, z, kq == 0);
-  } else {
+  template <typename P>
+  __device__ __forceinline__ void run(const P& p, unsigned char* smem, const int tile, const int z, const int mh, const int kq,
+                                      f32x4 (&acc)[MREP][NREP]) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // ---- the K splits of this row tile meet inside the launch (reduce-scatter), then the rows' owners apply the coupling ----
     // Before: 16 partial tiles -> 5 MB of fp32 slabs -> kernel boundary -> affine_* re-reads and sums them (14 us + boundary +
     // 9 us per coupling, 215 couplings per pass).  Here the 128 rows of a tile are dealt in 16-row slices (= one block of the
@@ -1695,6 +1509,216 @@ __device__ __forceinline__ void conv3x3_s8_body(const NtParams& p, const Couplin
         }
       }
     }
+  }
+};
+
+// NREP = 2: 32 output columns (the conv1 data gradient of a coupling that conditions on <= 32 channels): half the filter ring --
+// 88 KB of LDS instead of 137, which fits beside ONE resident weight-gradient workgroup instead of waiting for a whole CU -- and
+// half the matrix-core work.
+template <int NSPLIT, int NREP = 4>
+__device__ __forceinline__ void conv3x3_s8_body(const NtParams& p, const CouplingEpi& e, const int tile, const int z) {
+  typedef bf16_t T;
+  typedef typename ET<T>::frag frag_t;
+  typedef __attribute__((address_space(3))) void lds_void;
+  typedef const __attribute__((address_space(1))) void glb_void;
+  constexpr int BM = 128, BN = 16 * NREP, NTHR = 512, R = 12;     // ring: three rounds of four filter K-blocks
+  constexpr int ABUF = BM * 128, WSLOT = BN * 128;
+  constexpr int A_IT = BM * 8 / NTHR;                      // DMA instructions per thread and input chunk (2)
+  constexpr int MREP = 4;
+  constexpr int WJ = BN / 16;                              // filter DMA instructions per wave and round (8 rows each)
+  constexpr int EP = BN * 4 + 16;                          // nt_epilogue's staging pitch
+  constexpr unsigned kInvalid = 0xffffffffu;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  unsigned char* abuf = smem;                              // 2 x ABUF: the input chunk, double-buffered
+  unsigned char* zrow = smem + 2 * ABUF;                   // 256 bytes of zeros: the "outside the map" row
+  unsigned char* ring = zrow + 256;                        // R filter K-blocks
+  unsigned char* dummy = ring + R * WSLOT;                 // landing zone of padding DMAs, 1 KB per wave
+  S8_STAMP(0);
+  if (p.prio == 1) __builtin_amdgcn_s_setprio(1); else if (p.prio == 2) __builtin_amdgcn_s_setprio(2); else if (p.prio == 3) __builtin_amdgcn_s_setprio(3);
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int mh = wave & 1, kq = wave >> 1;
+  const GeomDev& g = p.g;
+  const int m0 = tile * BM;
+  const int nchunks = p.Kc >> 6;
+  const int c_begin = z * p.kb_per_split, c_end = min(nchunks, c_begin + p.kb_per_split);
+  const int nch = max(0, c_end - c_begin), nkb = nch * 9, nrounds = (nkb + 3) >> 2;
+  const int sgn = g.transposed ? -1 : 1;
+
+  if (tid < 16) reinterpret_cast<f32x4*>(zrow)[tid] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const T* Abase = reinterpret_cast<const T*>(p.A);
+  const T* Wbase = reinterpret_cast<const T*>(p.W);
+  const T* zero = reinterpret_cast<const T*>(g_zero_chunk);
+  unsigned a_src[A_IT];
+#pragma unroll
+  for (int i = 0; i < A_IT; ++i) {
+    const int ch = (wave + 8 * i) * 64 + lane, row = ch >> 3, pos = ch & 7, m = m0 + row;
+    a_src[i] = kInvalid;
+    if (m < g.M) {
+      const long off = (long)(m >> 6) * p.a_sn + (long)((m >> 3) & 7) * p.a_sh + (long)(m & 7) * p.a_sw + p.a_coff;
+      a_src[i] = (unsigned)(off + c_begin * 64 + ((pos ^ ((row >> 1) & 7)) * 8));
+    }
+  }
+  // filter DMA of a round: wave w brings rows 32*(w >> 2) .. +31 (4 instructions of 8 rows) of K-block 4r + (w & 3)
+  unsigned w_src[WJ];
+#pragma unroll
+  for (int j = 0; j < WJ; ++j) {
+    const int n = 8 * WJ * (wave >> 2) + 8 * j + (lane >> 3), pos = lane & 7;
+    w_src[j] = n < p.Nout ? (unsigned)((long)n * p.ldw + c_begin * 64 + ((pos ^ ((n >> 1) & 7)) * 8)) : kInvalid;
+  }
+  int wi_g = wave & 3, wi_c = 0, wi_t = wave & 3;          // K-block index / (chunk, tap) of this wave's next filter request
+  auto issue_w = [&]() {
+    const bool in = wi_g < nkb;
+#pragma unroll
+    for (int j = 0; j < WJ; ++j) {
+#if defined(IPOKE_GEMM_STAMPS) && IPOKE_GEMM_ABL == 3
+      continue;
+#endif
+#if defined(IPOKE_GEMM_STAMPS) && IPOKE_GEMM_ABL == 2
+      const bool real = false;
+#else
+      const bool real = in && w_src[j] != kInvalid;
+#endif
+      const T* src = real ? Wbase + w_src[j] + (long)wi_t * p.Kc + wi_c * 64 : zero;
+      unsigned char* dst = in ? ring + (wi_g % R) * WSLOT + (WJ * (wave >> 2) + j) * 1024 : dummy + wave * 1024;
+      __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)dst, 16, 0, 0);
+    }
+    wi_g += 4; wi_t += 4;
+    if (wi_t >= 9) { wi_t -= 9; ++wi_c; }
+  };
+  int a_next = 0;                                          // next input chunk to request
+  auto issue_a = [&]() {
+#pragma unroll
+    for (int i = 0; i < A_IT; ++i) {
+#if defined(IPOKE_GEMM_STAMPS) && IPOKE_GEMM_ABL == 3
+      continue;
+#endif
+#if defined(IPOKE_GEMM_STAMPS) && IPOKE_GEMM_ABL == 2
+      const bool real = false;
+#else
+      const bool real = a_next < nch && a_src[i] != kInvalid;
+#endif
+      const T* src = real ? Abase + a_src[i] + a_next * 64 : zero;
+      unsigned char* dst = a_next < nch ? abuf + (a_next & 1) * ABUF + (wave + 8 * i) * 1024 : dummy + wave * 1024;
+      __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)dst, 16, 0, 0);
+    }
+    ++a_next;
+  };
+  CouplingTail<NSPLIT> ct(e);      // (NSPLIT == 0: unused)
+  if constexpr (NSPLIT > 0) { static_assert(NREP == 4, "the coupling's raw sums are 64 columns wide"); ct.prefetch(g.M, m0, z); }
+  issue_a();                 // chunk 0
+  issue_w(); issue_w();      // rounds 0 and 1
+
+  // fragment bookkeeping: row r of the tile is position (y, x) = ((r >> 3) & 7, r & 7) of sample r >> 6
+  unsigned vmask[MREP];
+#pragma unroll
+  for (int i = 0; i < MREP; ++i) {
+    const int r = i * 16 + (lane & 15);                    // row inside this wave's sample (mh)
+    const int y = (r >> 3) & 7, x = r & 7;
+    unsigned vm = 0;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      const int yy = y + sgn * (t / 3 - 1), xx = x + sgn * (t % 3 - 1);
+      if ((unsigned)yy < 8u && (unsigned)xx < 8u) vm |= 1u << t;
+    }
+    vmask[i] = vm;
+  }
+  const int qlo = lane >> 4;
+  int b_rd[NREP];                                          // half-step 0; half-step 1 is the chunk position ^ 4, i.e. byte offset ^ 64
+#pragma unroll
+  for (int j = 0; j < NREP; ++j) {
+    const int n = j * 16 + (lane & 15);
+    b_rd[j] = n * 128 + ((qlo ^ ((n >> 1) & 7)) * 16);
+  }
+  f32x4 acc[MREP][NREP];
+#pragma unroll
+  for (int i = 0; i < MREP; ++i)
+#pragma unroll
+    for (int j = 0; j < NREP; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  int gk = kq, ci = 0, t = kq;                             // this wave's K-block of the round: index, chunk, tap
+  for (int r = 0; r < nrounds; ++r) {
+    wait_vmcnt<WJ>();                // everything but this wave's share of round r + 1 has landed (input chunks included)
+    __builtin_amdgcn_s_barrier();
+    if (r == 0) S8_STAMP(1);
+    // the first K-block of this round lies in chunk (4r)/9: request the chunk after it once (its buffer held chunk - 1,
+    // whose last K-block was consumed before this barrier)
+    if (a_next <= (4 * r) / 9 + 1) issue_a();          // (issued before the filter blocks: the wait above counts those only)
+    issue_w();                       // round r + 2 into the slots of round r - 1
+    if (gk < nkb) {
+      const unsigned char* ab = abuf + (ci & 1) * ABUF + mh * 64 * 128;
+      const unsigned char* wb = ring + (gk % R) * WSLOT;
+      const int th = t / 3, tw = t - 3 * th;
+      const int shift = sgn * ((th - 1) * 8 + (tw - 1));
+      const unsigned char* arow[MREP]; int aswz[MREP];
+#pragma unroll
+      for (int i = 0; i < MREP; ++i) {
+        const bool ok = (vmask[i] >> t) & 1u;
+        const int sr = i * 16 + (lane & 15) + shift;       // row inside the sample
+        arow[i] = ok ? ab + sr * 128 : zrow;
+        aswz[i] = ok ? (sr >> 1) & 7 : 0;
+      }
+      frag_t fa[2][MREP], fb[2][NREP];
+#pragma unroll
+      for (int hs = 0; hs < 2; ++hs) {
+#pragma unroll
+        for (int i = 0; i < MREP; ++i) fa[hs][i] = *reinterpret_cast<const frag_t*>(arow[i] + (((hs * 4 + qlo) ^ aswz[i]) * 16));
+#pragma unroll
+        for (int j = 0; j < NREP; ++j) fb[hs][j] = *reinterpret_cast<const frag_t*>(wb + (b_rd[j] ^ (hs * 64)));
+      }
+#pragma unroll
+      for (int hs = 0; hs < 2; ++hs)
+#pragma unroll
+        for (int i = 0; i < MREP; ++i)
+#pragma unroll
+          for (int j = 0; j < NREP; ++j) GEMM_MMA(fa[hs][i], fb[hs][j], acc[i][j]);
+      // issue order: the eight fragments of the first half-step, then the second half-step's reads one per two MFMAs of the first.
+      // (hipcc's own schedule reads just in time, four MFMAs per s_waitcnt lgkmcnt(0): eight exposed LDS latencies per K-block.)
+      constexpr int NF = MREP + NREP, NM = MREP * NREP, PER = NM / NF;        // fragment reads / MFMAs per half-step
+      __builtin_amdgcn_sched_group_barrier(0x100, NF, 0);
+#pragma unroll
+      for (int q = 0; q < NF; ++q) {
+        __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      }
+      __builtin_amdgcn_sched_group_barrier(0x008, 2 * NM - NF * PER, 0);
+    }
+    gk += 4; t += 4;
+    if (t >= 9) { t -= 9; ++ci; }
+  }
+  wait_vmcnt<0>();
+  S8_STAMP(2);
+  if constexpr (NSPLIT > 0) ct.pin();
+  if constexpr (NSPLIT == 0) {
+  // the four K groups meet: groups 2, 3 hand over to groups 0, 1, then group 1 to group 0 (nt_epilogue's staging layout)
+  {
+    unsigned char* st = smem + (mh * MREP * 16 + (lane & 15)) * EP + (lane >> 4) * 16;
+    __syncthreads();                 // the ring and the input buffers are dead
+#pragma unroll
+    for (int round = 0; round < 2; ++round) {
+      const int give_lo = round == 0 ? 2 : 1, take_hi = round == 0 ? 2 : 1;      // givers: kq in [give_lo, 2*give_lo); takers: kq < take_hi
+      if (kq >= give_lo && kq < 2 * give_lo) {
+        unsigned char* d = st + (kq - give_lo) * BM * EP;
+#pragma unroll
+        for (int i = 0; i < MREP; ++i)
+#pragma unroll
+          for (int j = 0; j < NREP; ++j) *reinterpret_cast<f32x4*>(d + i * 16 * EP + j * 64) = acc[i][j];
+      }
+      __syncthreads();
+      if (kq < take_hi) {
+        const unsigned char* d = st + kq * BM * EP;
+#pragma unroll
+        for (int i = 0; i < MREP; ++i)
+#pragma unroll
+          for (int j = 0; j < NREP; ++j) acc[i][j] += *reinterpret_cast<const f32x4*>(d + i * 16 * EP + j * 64);
+      }
+      if (round == 0) __syncthreads();
+    }
+  }
+  nt_epilogue<T, 2, 1, MREP, NREP, NTHR, true>(p, acc, smem, m0, 0, mh, 0, z, kq == 0);
+  } else {
+    ct.run(p, smem, tile, z, mh, kq, acc);
   }
   S8_STAMP(3);
 }
@@ -2537,7 +2561,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // Dispatch switches of the two persistent / wide 3 x 3 kernels: 0 off, 1 (default) where measured faster, 2 wherever the kernel can run.
 // The parity tests move them at run time through ipoke_set_dispatch_override (atomics because launches on distinct streams may come
 // from distinct threads).
-static std::atomic<int> g_c64_mode{1}, g_halo16_mode{1}, g_nn128_mode{1};
+static std::atomic<int> g_c64_mode{1}, g_halo16_mode{1}, g_nn128_mode{1}, g_nt128_mode{1};
+static std::atomic<int> g_cpl_split{0};      // "cpl_split": K slices of ipoke_conv3x3_coupling where they fit (0: the rule of coupling_splits)
 
 static bool c64_applicable(const NtParams& p) {
   // mode 1 (default): at >= 512 patches (two per CU)
@@ -2819,14 +2844,15 @@ static int launch_conv3x3_k64(NtParams& p, hipStream_t s) {
 }
 
 static constexpr int kS8SamplesPerTile = 2;      // 8x8 maps per 128-row tile of conv3x3_s8
-static bool s8_applicable(const NtParams& p) {
+static bool s8_shape(const NtParams& p) {      // (host only: no device query)
   const GeomDev& g = p.g;
-  return kLdsS8 <= device_max_lds() && !p.c_scatter && !p.a_f32 && g.taps == 9 && g.khw == 9 && g.kw == 3 && g.Di == 1 && g.Hi == 8 && g.Wi == 8 &&
+  return !p.c_scatter && !p.a_f32 && g.taps == 9 && g.khw == 9 && g.kw == 3 && g.Di == 1 && g.Hi == 8 && g.Wi == 8 &&
          g.lDo == 0 && g.lHo == 3 && g.lWo == 3 && g.sd == 1 && g.sh == 1 && g.sw == 1 && g.pd == 0 && g.ph == 1 && g.pw == 1 &&
          p.Kc % 64 == 0 && p.Kc_real == p.Kc && p.Kc >= 256 && p.Nout <= 64 && (p.a_coff & 7) == 0 && p.ldw >= p.Ktot &&
          ((p.a_sn | p.a_sh | p.a_sw) & 7) == 0 && (long)(g.M >> 6) * p.a_sn + 7 * p.a_sh + 7 * p.a_sw + p.Kc < (1L << 31) &&
          (long)p.Nout * p.ldw < (1L << 31);
 }
+static bool s8_applicable(const NtParams& p) { return kLdsS8 <= device_max_lds() && s8_shape(p); }
 static int launch_conv3x3_s8(NtParams& p, hipStream_t s) {
   constexpr int BM = 128;
   p.tiles_m = ceil_div(p.g.M, BM); p.tiles_n = 1; p.xa = p.xb = 0;
@@ -2910,7 +2936,11 @@ extern "C" int ipoke_conv3x3_coupling(const ipoke_conv_desc* conv, const ipoke_a
                             : (ep->out != nullptr), "bad outputs");
   IPK_REQUIRE(!ep->logdet_slot || ep->slot_stride >= 4, "log-det slots are 4 wide (one per 16-row slice of a sample)");
   IPK_REQUIRE(!ep->ext || ep->ext_ld >= a->Cp, "bad extra operand output");
-  const int ns = coupling_splits(p.g.M, p.Kc);
+  int ns = coupling_splits(p.g.M, p.Kc);
+  {      // test hook (ipoke_set_dispatch_override "cpl_split"): the slices of ipoke_conv_pair_coupling at shapes the rule gives other counts
+    const int ov = g_cpl_split.load(std::memory_order_relaxed);
+    if (ov > 0 && (long)ceil_div(p.g.M, 128) * ov <= 256 && ov <= p.Kc / 64) ns = ov;
+  }
   IPK_REQUIRE(ns >= 4, "too many row tiles for an in-launch exchange (ipoke_conv3x3_coupling_splitk == 0)");
   CouplingEpi e{};
   e.bias = a->bias; e.in = ep->in; e.out = ep->out; e.out2 = ep->mode == 1 ? ep->out2 : nullptr;
@@ -2954,6 +2984,9 @@ static int dispatch_nt(NtParams& p, hipStream_t s) {
   }
   if (!p.a_f32) {
     if (N <= 64) return launch_nt_glds<T, 4, 1, 1, 4, 4>(p, s);         // 64 x 64, skinny N
+    // developer hook (ipoke_set_dispatch_override "nt128" = 2, scripts/probe_pair_coupling.py): EVERY wide N-major GEMM of the process on
+    // the 128 x 128 tile with one K pass -- the tile and the K order of ipoke_conv_pair_coupling
+    if (g_nt128_mode.load(std::memory_order_relaxed) == 2) return launch_nt_glds<T, 2, 4, 4, 2, 2, 2>(p, s);
     {
       // Row-tile height: the flow's GEMMs have M = 64*B rows (1280 at B = 20) and N = 2048, i.e. 160 tiles of 128 x 128 on
       // 256 CUs.  80- or 160-row tiles give exactly 256 workgroups at B = 20 / 40; pick the height with the least
@@ -3588,6 +3621,312 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   q.splitk = p.tiles_n; q.tiles_n = 1; q.c_acc = 1; q.c_f32 = 1; q.acc_cnt = e.acc_cnt; q.acc_part = e.acc_part;
   q.C = e.C2; q.ldc = e.ldc2; q.c_coff = e.c_coff2; q.c_cstride = e.c_cstride2; q.Nout = e.cin;
   nt_epilogue<T, 2, 1, MREP, CREP, NTHR, true>(q, acc2, smem, m0, 0, mh, 0, tn, kq == 0);
+}
+
+// =============================================================================================
+// conv2 (+ bias, ELU), conv3 AND the coupling transform of a coupling net as one launch (ipoke_conv_pair_coupling): the forward
+// counterpart of igemm_nn_pair_kernel.  conv3 -- the skinny 3x3 convolution conv3x3_s8_coupling_kernel runs as hidden / 128 K slices of
+// two 64-channel chunks -- is a split-K reduction over the hidden channels, and a slice is exactly one 128-column N tile of conv2's
+// GEMM: the workgroup that owns the [128 rows (two samples) x 128 columns] tile of h2 holds, after bias + ELU, the whole input image
+// of slice z = its N tile.  It writes the bf16 values from its accumulators straight into the two chunk images of conv3x3_s8_body
+// (same swizzle, same zero row; no fp32 staging tile), runs the slice's 18 K-blocks against the matching slab of conv3's filter
+// operand and joins the reduce-scatter + coupling of CouplingTail -- the very code of the two-launch form, with its exchange scratch,
+// sentinels and bounded spins: no new hand-off.  Per coupling one chain launch, the L2 -> LDS re-read of h2 and the skinny kernel's
+// ramp disappear; with C == NULL (the reverse pass: nothing reads h2 afterwards) so does the store of h2.
+// Block order: slice z is the FAST index of the 1-D grid (block = tile * NSPLIT + z), so the NSPLIT partners of a row tile are adjacent
+// in dispatch order and a partly resident grid finishes tile by tile (the progress argument of CouplingTail::run).
+// The GEMM main loop is igemm_nt_glds_kernel's (W read N-major) on the 128 x 128 tile of igemm_nn_pair_kernel, one K pass, 3 slots;
+// the K-block loop of the convolution is conv3x3_s8_body's (chunk-major, nine taps inside, K group kq takes every fourth block) -- the
+// results equal ipoke_conv_forward on the 128 x 128 tile followed by ipoke_conv3x3_coupling at hidden / 128 slices bit for bit.
+//
+// LDS (137.25 KB): the filter ring keeps its three rounds of four 8 KB K-blocks, but only round 0 has a region of its own -- rounds 1
+// and 2 are requested INTO THE GEMM SLOTS AS THEY RETIRE (in place of the padding DMAs of the last two GEMM iterations: same number of
+// DMA instructions per wave, the counted waits do not change), the chunk images take the slot of the last K-block, rounds 3 and 4
+// follow rounds 0 and 1.  The parked tiles of CouplingTail::run (4 x 128 x 272 B from offset 0) fit underneath.
+struct NtCplEpi { const void* W3; int ldw3, nout3; };      // conv3's filter operand [nout3][9 * hidden] (tap-major) and its output columns
+static constexpr int kCplSub = 2 * 128 * 128, kCplF = 3 * kCplSub, kCplZrow = kCplF + 4 * 64 * 128, kCplDummy = kCplZrow + 256;
+static constexpr int kCplBias = kCplDummy + 8 * 1024;      // conv2's 128 bias values of this N tile (1 KB: one DMA instruction)
+static constexpr size_t kLdsNtCpl = kCplBias + 1024;
+static_assert(kCplSub == 4 * 64 * 128 && kCplSub == 2 * 128 * 128, "a GEMM slot holds one filter round or the two chunk images");
+static_assert(4 * 128 * (64 * 4 + 16) <= kLdsNtCpl, "the parked tiles of CouplingTail::run");
+static_assert(kLdsNtCpl <= 160 * 1024, "LDS per workgroup");
+
+template <int NSPLIT>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void igemm_nt_coupling_kernel(const NtParams p, const NtCplEpi q3, const CouplingEpi e) {
+  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)(sizeof(NtParams) + sizeof(NtCplEpi) + sizeof(CouplingEpi)) < 512 ? (int)(sizeof(NtParams) + sizeof(NtCplEpi) + sizeof(CouplingEpi)) : 512>();
+  typedef bf16_t T;
+  typedef typename ET<T>::frag frag_t;
+  typedef typename Pack4<T>::type pack_t;
+  typedef __attribute__((address_space(3))) void lds_void;
+  typedef const __attribute__((address_space(1))) void glb_void;
+  constexpr int WN = 4, MREP = 4, NREP = 2, NSTAGE = 3, NTHR = 512, BM = 128, BN = 128;
+  constexpr int A_IT = BM * 8 / NTHR, B_IT = BN * 8 / NTHR, L = A_IT + B_IT;
+  constexpr int SUB = kCplSub;
+  constexpr int CREP = 4, WSLOT = 64 * 128, WJ = 4, ABUF = BM * 128;    // the filter K-blocks and the input images of conv3x3_s8_body<NSPLIT>
+  constexpr int NKB = 18, NROUNDS = 5;                                  // 2 chunks x 9 taps, four K-blocks per round
+  static_assert(L == WJ, "a filter round takes the place of a GEMM slot's DMA instructions");
+  constexpr unsigned kInvalid = 0xffffffffu;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  unsigned char* zrow = smem + kCplZrow;
+  unsigned char* dummy = smem + kCplDummy;
+  if (p.prio == 1) __builtin_amdgcn_s_setprio(1); else if (p.prio == 2) __builtin_amdgcn_s_setprio(2); else if (p.prio == 3) __builtin_amdgcn_s_setprio(3);
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave / WN, wn = wave % WN;
+  const GeomDev& g = p.g;
+  const int tile = blockIdx.x / NSPLIT, z = blockIdx.x % NSPLIT;
+  const int m0 = tile * BM, n0 = z * BN;
+  const int hid = p.Nout;                                // conv3's input channels = the GEMM's columns
+  const int nkb = p.Ktot >> 6;
+  const T* zero = reinterpret_cast<const T*>(g_zero_chunk);
+  if (tid < 16) reinterpret_cast<f32x4*>(zrow)[tid] = f32x4{0.f, 0.f, 0.f, 0.f};      // (outside every ring: first read after many barriers)
+  // where the filter rounds and the images go: round r in region r % 3
+  const int reg1 = (nkb % NSTAGE) * SUB, reg2 = ((nkb + 1) % NSTAGE) * SUB;
+  unsigned char* img = smem + ((nkb + NSTAGE - 1) % NSTAGE) * SUB;
+
+  // ---- what the epilogue and the coupling need from global memory is requested first (the oldest requests of the launch)
+  // conv2's bias goes through LDS (every wave requests the same 128 floats; no bias: zeros): a register loaded here would make the
+  // epilogue wait for every DMA in flight behind the GEMM loop
+  {
+    const void* src = (p.bias && lane < BN / 4) ? static_cast<const void*>(p.bias + n0 + 4 * lane) : static_cast<const void*>(zero);
+    __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)(smem + kCplBias), 16, 0, 0);
+  }
+  CouplingTail<NSPLIT> ct(e);
+  ct.prefetch(g.M, m0, z);
+
+  // ---- conv3 filter slab of this slice: wave w brings rows 32 * (w >> 2) .. + 31 (4 instructions of 8 rows) of K-block 4r + (w & 3)
+  const T* W3 = reinterpret_cast<const T*>(q3.W3);
+  unsigned w_src[WJ];
+#pragma unroll
+  for (int j = 0; j < WJ; ++j) {
+    const int n = 8 * WJ * (wave >> 2) + 8 * j + (lane >> 3), pos = lane & 7;
+    w_src[j] = n < q3.nout3 ? (unsigned)((long)n * q3.ldw3 + n0 + ((pos ^ ((n >> 1) & 7)) * 8)) : kInvalid;
+  }
+  int wi_g = wave & 3, wi_c = 0, wi_t = wave & 3;          // K-block index / (chunk, tap) of this wave's next filter request
+  int wi_reg = kCplF, wi_r3 = 0;                           // region of that round
+  auto issue_w = [&]() {
+    const bool in = wi_g < NKB;
+#pragma unroll
+    for (int j = 0; j < WJ; ++j) {
+      const bool real = in && w_src[j] != kInvalid;
+      const T* src = real ? W3 + w_src[j] + (long)wi_t * hid + wi_c * 64 : zero;
+      unsigned char* dst = in ? smem + wi_reg + (wi_g & 3) * WSLOT + (WJ * (wave >> 2) + j) * 1024 : dummy + wave * 1024;
+      __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)dst, 16, 0, 0);
+    }
+    wi_g += 4; wi_t += 4;
+    if (wi_t >= 9) { wi_t -= 9; ++wi_c; }
+    wi_r3 = wi_r3 == 2 ? 0 : wi_r3 + 1;
+    wi_reg = wi_r3 == 0 ? kCplF : (wi_r3 == 1 ? reg1 : reg2);
+  };
+  issue_w();                                               // round 0
+
+  // ---- conv2: the main loop of igemm_nt_glds_kernel on the 128 x 128 tile, one K pass
+  unsigned a_off[A_IT], b_off[B_IT];
+#pragma unroll
+  for (int i = 0; i < A_IT; ++i) {
+    const int ch = tid + NTHR * i, row = ch >> 3, pos = ch & 7;
+    a_off[i] = (m0 + row < g.M) ? (unsigned)((long)(m0 + row) * p.a_sw + p.a_coff + ((pos ^ ((row >> 1) & 7)) * 8)) : kInvalid;
+  }
+#pragma unroll
+  for (int i = 0; i < B_IT; ++i) {
+    const int ch = tid + NTHR * i, row = ch >> 3, pos = ch & 7;
+    b_off[i] = (unsigned)((long)(n0 + row) * p.ldw + ((pos ^ ((row >> 1) & 7)) * 8));
+  }
+  const T* Abase = reinterpret_cast<const T*>(p.A);
+  const T* Wbase = reinterpret_cast<const T*>(p.W);
+  int kb_issue = 0;
+  auto issue_slot = [&](int slot) {
+    if (kb_issue < nkb) {
+      unsigned char* sa = smem + slot * SUB;
+#pragma unroll
+      for (int i = 0; i < A_IT; ++i) {
+        const T* src = a_off[i] != kInvalid ? Abase + a_off[i] : zero;
+        __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)(sa + (wave * 64 + NTHR * i) * 16), 16, 0, 0);
+        if (a_off[i] != kInvalid) a_off[i] += 64;
+      }
+#pragma unroll
+      for (int i = 0; i < B_IT; ++i) {
+        __builtin_amdgcn_global_load_lds((glb_void*)(Wbase + b_off[i]), (lds_void*)(sa + BM * 128 + (wave * 64 + NTHR * i) * 16), 16, 0, 0);
+        b_off[i] += 64;
+      }
+    } else {
+      issue_w();             // filter rounds 1 and 2 into the slots of K-blocks nkb - 3 and nkb - 2 (read before the barrier just passed)
+    }
+    ++kb_issue;
+  };
+  f32x4 acc[MREP][NREP];
+#pragma unroll
+  for (int i = 0; i < MREP; ++i)
+#pragma unroll
+    for (int j = 0; j < NREP; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  {
+    int a_rd[MREP][2], b_rd[NREP][2];
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+      const int qq = s2 * 4 + (lane >> 4);
+#pragma unroll
+      for (int i = 0; i < MREP; ++i) {
+        const int row = wm * MREP * 16 + i * 16 + (lane & 15);
+        a_rd[i][s2] = row * 128 + ((qq ^ ((row >> 1) & 7)) * 16);
+      }
+#pragma unroll
+      for (int j = 0; j < NREP; ++j) {
+        const int row = wn * NREP * 16 + j * 16 + (lane & 15);
+        b_rd[j][s2] = BM * 128 + row * 128 + ((qq ^ ((row >> 1) & 7)) * 16);
+      }
+    }
+#pragma unroll
+    for (int s2 = 0; s2 < NSTAGE - 1; ++s2) issue_slot(s2);
+    int slot = 0;
+    for (int kb = 0; kb < nkb; ++kb) {
+      wait_vmcnt<(NSTAGE - 2) * L>();                 // this wave's share of the oldest slot has landed
+      __builtin_amdgcn_s_barrier();                   // ... and everybody else's; all reads of the slot refilled below are done
+      issue_slot((slot + NSTAGE - 1) % NSTAGE);
+      const unsigned char* base = smem + slot * SUB;
+      slot = (slot + 1) % NSTAGE;
+      frag_t fa[2][MREP], fb[2][NREP];
+#pragma unroll
+      for (int i = 0; i < MREP; ++i) fa[0][i] = *reinterpret_cast<const frag_t*>(base + a_rd[i][0]);
+#pragma unroll
+      for (int j = 0; j < NREP; ++j) fb[0][j] = *reinterpret_cast<const frag_t*>(base + b_rd[j][0]);
+#pragma unroll
+      for (int i = 0; i < MREP; ++i) fa[1][i] = *reinterpret_cast<const frag_t*>(base + a_rd[i][1]);
+#pragma unroll
+      for (int j = 0; j < NREP; ++j) fb[1][j] = *reinterpret_cast<const frag_t*>(base + b_rd[j][1]);
+#pragma unroll
+      for (int hs = 0; hs < 2; ++hs)
+#pragma unroll
+        for (int i = 0; i < MREP; ++i)
+#pragma unroll
+          for (int j = 0; j < NREP; ++j) GEMM_MMA(fa[hs][i], fb[hs][j], acc[i][j]);
+    }
+  }
+  // (filter rounds 1 and 2 are in flight: no wait here)
+
+  // ---- h2 = bf16(ELU(acc + bias)), the arithmetic of nt_epilogue's dense path, from the accumulators into the chunk images: column c of
+  // the tile = channel c & 63 of chunk c >> 6, 16-byte units swizzled by (row >> 1) & 7; rows beyond M are zero (as the DMA of
+  // conv3x3_s8_body leaves them)
+  auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+  lds_barrier();                     // the GEMM slot the images take is dead
+#pragma unroll
+  for (int j = 0; j < NREP; ++j) {
+    const int col = (wn * NREP + j) * 16 + (lane >> 4) * 4, cc = col & 63, pos = cc >> 3;
+    const f32x4 b4 = *reinterpret_cast<const f32x4*>(smem + kCplBias + col * 4);      // (the oldest request of the launch: long landed)
+#pragma unroll
+    for (int i = 0; i < MREP; ++i) {
+      const int row = wm * MREP * 16 + i * 16 + (lane & 15);
+      const f32x4 v = acc[i][j] + b4;
+      pack_t o;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[r] = ET<T>::from_f32(fast_act<T>(IPOKE_ACT_ELU, v[r]));
+      typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+      const unsigned keep = m0 + row < g.M ? 0xffffffffu : 0u;      // (a mask, not a branch around the ELU)
+      const u32x2 bits = __builtin_bit_cast(u32x2, o) & u32x2{keep, keep};
+      *reinterpret_cast<u32x2*>(img + (col >> 6) * ABUF + row * 128 + ((pos ^ ((row >> 1) & 7)) * 16) + ((cc >> 2) & 1) * 8) = bits;
+    }
+  }
+  lds_barrier();                     // the images are complete
+  // the copy that goes to C: a thread takes one 4-column group in 8 rows (row-contiguous stores) and keeps it in registers; the stores
+  // are issued behind the convolution's K loop, whose counted waits they would otherwise sit in
+  constexpr int G4F = BN / 4, ITER = BM * G4F / NTHR, RSTEP = NTHR / G4F;
+  const int c4 = tid % G4F, r0 = tid / G4F;
+  const bool store_c = p.C != nullptr;
+  pack_t oc[ITER];
+#pragma unroll
+  for (int k = 0; k < ITER; ++k) oc[k] = pack_t{};
+  if (store_c) {
+    const int pos = (c4 & 15) >> 1;
+#pragma unroll
+    for (int k = 0; k < ITER; ++k) {
+      const int row = r0 + k * RSTEP;
+      oc[k] = *reinterpret_cast<const pack_t*>(img + (c4 >> 4) * ABUF + row * 128 + ((pos ^ ((row >> 1) & 7)) * 16) + (c4 & 1) * 8);
+    }
+  }
+
+  // ---- conv3 of this slice: the K-block loop of conv3x3_s8_body (2 row halves x 4 K groups, chunk-major, nine taps inside) on the images
+  const int mh = wave & 1, kq = wave >> 1;
+  unsigned vmask[MREP];
+#pragma unroll
+  for (int i = 0; i < MREP; ++i) {
+    const int r = i * 16 + (lane & 15);
+    const int y = (r >> 3) & 7, x = r & 7;
+    unsigned vm = 0;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      const int yy = y + (t / 3 - 1), xx = x + (t % 3 - 1);
+      if ((unsigned)yy < 8u && (unsigned)xx < 8u) vm |= 1u << t;
+    }
+    vmask[i] = vm;
+  }
+  const int qlo = lane >> 4;
+  int w_rd[CREP];
+#pragma unroll
+  for (int j = 0; j < CREP; ++j) {
+    const int n = j * 16 + (lane & 15);
+    w_rd[j] = n * 128 + ((qlo ^ ((n >> 1) & 7)) * 16);
+  }
+  f32x4 acc2[MREP][CREP];
+#pragma unroll
+  for (int i = 0; i < MREP; ++i)
+#pragma unroll
+    for (int j = 0; j < CREP; ++j) acc2[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  int gk = kq, ci = 0, t = kq;
+  int rd_reg = kCplF, rd_r3 = 0;
+  for (int r = 0; r < NROUNDS; ++r) {
+    wait_vmcnt<WJ>();                // everything but this wave's share of the newest round has landed
+    lds_barrier();
+    if (r >= 1) issue_w();           // round r + 2 into the region of round r - 1 (rounds 0 .. 2 were requested beside the GEMM)
+    if (gk < NKB) {
+      const unsigned char* ab = img + ci * ABUF + mh * 64 * 128;
+      const unsigned char* wb = smem + rd_reg + (gk & 3) * WSLOT;
+      const int th = t / 3, tw = t - 3 * th;
+      const int shift = (th - 1) * 8 + (tw - 1);
+      const unsigned char* arow[MREP]; int aswz[MREP];
+#pragma unroll
+      for (int i = 0; i < MREP; ++i) {
+        const bool ok = (vmask[i] >> t) & 1u;
+        const int sr = i * 16 + (lane & 15) + shift;
+        arow[i] = ok ? ab + sr * 128 : zrow;
+        aswz[i] = ok ? (sr >> 1) & 7 : 0;
+      }
+      frag_t fa[2][MREP], fb[2][CREP];
+#pragma unroll
+      for (int hs = 0; hs < 2; ++hs) {
+#pragma unroll
+        for (int i = 0; i < MREP; ++i) fa[hs][i] = *reinterpret_cast<const frag_t*>(arow[i] + (((hs * 4 + qlo) ^ aswz[i]) * 16));
+#pragma unroll
+        for (int j = 0; j < CREP; ++j) fb[hs][j] = *reinterpret_cast<const frag_t*>(wb + (w_rd[j] ^ (hs * 64)));
+      }
+#pragma unroll
+      for (int hs = 0; hs < 2; ++hs)
+#pragma unroll
+        for (int i = 0; i < MREP; ++i)
+#pragma unroll
+          for (int j = 0; j < CREP; ++j) GEMM_MMA(fa[hs][i], fb[hs][j], acc2[i][j]);
+      // (issue order as in conv3x3_s8_body: the first half-step's fragments, then the second half-step's reads between the MFMAs of the first)
+      constexpr int NF = MREP + CREP, NM = MREP * CREP, PER = NM / NF;
+      __builtin_amdgcn_sched_group_barrier(0x100, NF, 0);
+#pragma unroll
+      for (int f = 0; f < NF; ++f) {
+        __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      }
+      __builtin_amdgcn_sched_group_barrier(0x008, 2 * NM - NF * PER, 0);
+    }
+    gk += 4; t += 4;
+    if (t >= 9) { t -= 9; ++ci; }
+    rd_r3 = rd_r3 == 2 ? 0 : rd_r3 + 1;
+    rd_reg = rd_r3 == 0 ? kCplF : (rd_r3 == 1 ? reg1 : reg2);
+  }
+  wait_vmcnt<0>();
+  ct.pin();
+  if (store_c) {                     // h2 to C (the backward pass reads it)
+    T* Cp = reinterpret_cast<T*>(p.C) + (long)(m0 + r0) * p.ldc + p.c_coff + n0 + 4 * c4;
+#pragma unroll
+    for (int k = 0; k < ITER; ++k)
+      if (m0 + r0 + k * RSTEP < g.M) *reinterpret_cast<pack_t*>(Cp + (long)k * RSTEP * p.ldc) = oc[k];
+  }
+  ct.run(p, smem, tile, z, mh, kq, acc2);
 }
 
 // RM = reduction rows per ring slot (64).
@@ -4479,11 +4818,19 @@ extern "C" void ipoke_gemm_set_stamps(long long* base) { g_gemm_stamps = base; }
 #endif
 
 /* Test hook: moves a kernel-dispatch switch at run time ("c64" / "halo16": 0 off, 1 default rule, 2 wherever the kernel can run;
- * "nn128": 2 = the K-major GEMM on its 128 x 128 tile at any M; value < 0 goes back to the default rule 1). */
+ * "nn128" / "nt128": 2 = the K-major / N-major GEMM on its 128 x 128 tile at any M; value < 0 goes back to the default rule 1;
+ * "cpl_split": 4 / 8 / 16 / 32 K slices for ipoke_conv3x3_coupling where tiles x slices <= 256 and slices <= Kc / 64, < 0 the default rule). */
 extern "C" int ipoke_set_dispatch_override(const char* name, int value) {
-  IPK_REQUIRE(name != nullptr && value <= 2, "bad arguments");
-  std::atomic<int>* slot = !strcmp(name, "c64") ? &g_c64_mode : (!strcmp(name, "halo16") ? &g_halo16_mode : (!strcmp(name, "nn128") ? &g_nn128_mode : nullptr));
-  IPK_REQUIRE(slot != nullptr, "unknown dispatch switch (c64 | halo16 | nn128)");
+  IPK_REQUIRE(name != nullptr, "bad arguments");
+  if (!strcmp(name, "cpl_split")) {
+    IPK_REQUIRE(value < 0 || value == 4 || value == 8 || value == 16 || value == 32, "cpl_split: 4, 8, 16 or 32 slices (< 0: the default rule)");
+    g_cpl_split.store(value < 0 ? 0 : value, std::memory_order_relaxed);
+    return IPOKE_OK;
+  }
+  IPK_REQUIRE(value <= 2, "bad arguments");
+  std::atomic<int>* slot = !strcmp(name, "c64") ? &g_c64_mode : (!strcmp(name, "halo16") ? &g_halo16_mode : (!strcmp(name, "nn128") ? &g_nn128_mode :
+                           (!strcmp(name, "nt128") ? &g_nt128_mode : nullptr)));
+  IPK_REQUIRE(slot != nullptr, "unknown dispatch switch (c64 | halo16 | nn128 | nt128 | cpl_split)");
   slot->store(value < 0 ? 1 : value, std::memory_order_relaxed);
   return IPOKE_OK;
 }
@@ -4651,6 +4998,96 @@ extern "C" int ipoke_conv_pair_dgrad(const ipoke_conv_desc* conv2, const ipoke_c
   if (ts.slot >= 0)
     ts.annotate(square ? 0 : IPOKE_TAG_CONV_BASE + IPOKE_KERNEL_IGEMM, 2.0 * g.M * p.Nout * ((double)p.Kc + 9.0 * p1.Nout),
                 2.0 * ((double)g.M * p.Kc + (double)p.Nout * p.Kc + (double)g.M * p.Nout + 9.0 * p1.Nout * p.Nout) + 4.0 * g.M * p1.Nout);
+  return IPOKE_OK;
+}
+
+extern "C" int ipoke_conv_pair_coupling_applicable(int M, int hidden, int nout3, int dtype) {
+  if (dtype != IPOKE_BF16 || M < 64 || M % 64 != 0 || nout3 < 2 || nout3 > 64) return 0;
+  if (hidden != 512 && hidden != 1024 && hidden != 2048 && hidden != 4096) return 0;      // 4, 8, 16 or 32 slices of 128 channels
+  return (long)ceil_div(M, 128) * (hidden / 128) <= 256 ? 1 : 0;                            // one round of workgroups
+}
+
+namespace ipoke {
+template <int NSPLIT>
+static int launch_nt_coupling(const NtParams& p, const NtCplEpi& q3, const CouplingEpi& e, hipStream_t s) {
+  auto kern = igemm_nt_coupling_kernel<NSPLIT>;
+  IPK_SET_LDS_ONCE(kern, kLdsNtCpl);
+  hipLaunchKernelGGL(kern, dim3((unsigned)(p.tiles_m * NSPLIT)), dim3(512), kLdsNtCpl, s, p, q3, e);
+  IPK_LAUNCH_CHECK();
+  return IPOKE_OK;
+}
+}  // namespace ipoke
+
+extern "C" int ipoke_conv_pair_coupling(const ipoke_conv_desc* conv2, const ipoke_conv_desc* conv3, const ipoke_affine_desc* a,
+                                        const ipoke_coupling_epi* ep, int B, int dtype, void* stream) {
+  IPK_REQUIRE(conv2 && conv3 && a && ep, "null descriptor");
+  IPK_REQUIRE(dtype == IPOKE_BF16, "the fused conv2 + conv3 + coupling launch is bf16 only");
+  IPK_REQUIRE(ep->xchg != nullptr && ((uintptr_t)ep->xchg & 15) == 0, "exchange scratch missing (ipoke_conv3x3_coupling_xchg_bytes / _init)");
+  const bool store_h2 = conv2->C != nullptr;
+  // conv_params wants non-null tensors: without a stored h2 neither conv2->C nor conv3->A is ever dereferenced
+  ipoke_conv_desc d2 = *conv2, d3 = *conv3;
+  if (!store_h2) { d2.C = ep->xchg; d2.ldc = d2.Nout; d2.c_coff = 0; d3.A = ep->xchg; }
+  d3.C = ep->xchg; d3.c_f32 = 1; d3.ldc = 64; d3.splitk = 1; d3.c_accumulate = 0;       // (no partial-sum slabs: validation only)
+  NtParams p, p3;
+  int rc = conv_params(p, &d2, dtype); if (rc) return rc;
+  rc = conv_params(p3, &d3, dtype); if (rc) return rc;
+  const GeomDev& g = p.g; const GeomDev& g3 = p3.g;
+  IPK_REQUIRE(!d2.w_kmajor && g.taps == 1 && !g.transposed && g.sd == 1 && g.sh == 1 && g.sw == 1 && g.pd == 0 && g.ph == 0 && g.pw == 0 &&
+              !p.a_f32 && p.Kc == p.Kc_real && p.Kc % 64 == 0 && p.Kc >= 128 && (p.a_coff & 7) == 0 && (p.a_sw & 7) == 0 && (p.ldw & 7) == 0 &&
+              p.ldw >= p.Ktot && p.splitk == 1 && !p.c_scatter && p.a_sh == (long)g.Wi * p.a_sw && p.a_sn == (long)g.Hi * g.Wi * p.a_sw &&
+              (long)g.M * p.a_sw + p.Kc < (1L << 31) && (long)p.Nout * p.ldw < (1L << 31),
+              "conv2: N-major weights, 1x1 kernel over dense bf16 channels-last rows, K a multiple of 64");
+  IPK_REQUIRE(p.act == IPOKE_ACT_ELU && !p.dact && !p.c_f32 && !p.c_acc && !p.row_scale && (!p.bias || ((uintptr_t)p.bias & 15) == 0),
+              "conv2: bias (16-byte aligned) + ELU into a dense dtype output");
+  IPK_REQUIRE(!store_h2 || (((p.ldc | p.c_coff) & 3) == 0 && p.ldc >= p.c_coff + p.Nout && ((uintptr_t)p.C & 7) == 0 && (long)g.M * p.ldc < (1L << 31)),
+              "conv2: h2 rows are 8-byte aligned, ldc >= c_coff + Nout");
+  IPK_REQUIRE(!d3.bias && d3.act == IPOKE_ACT_NONE && !d3.dact && !d3.row_scale && !d3.w_kmajor, "conv3 of a coupling: raw sums only (the bias is the coupling's)");
+  IPK_REQUIRE(s8_shape(p3) && g3.M == 64 * B && g3.M == g.M && !g3.transposed, "conv3: the skinny 3x3 convolution of a coupling net on 8x8 maps, conv2's rows");
+  IPK_REQUIRE(p3.Kc == p.Nout, "conv3 reads exactly conv2's output channels (a wider input takes the two launches)");
+  IPK_REQUIRE(!store_h2 || (p3.A == p.C && p3.a_coff == p.c_coff && p3.a_sw == p.ldc && p3.a_sh == 8 * p.ldc && p3.a_sn == 64 * p.ldc),
+              "conv3 reads conv2's output (same pointer, column offset and row stride)");
+  IPK_REQUIRE(a->Cp >= 1 && 2 * a->Cp == d3.Nout && a->t_stride >= 1 && a->P == 64 && a->ld >= 1 && a->ld <= 256 &&
+              a->t_off >= 0 && a->t_off + (a->Cp - 1) * a->t_stride < a->ld, "bad coupling geometry");
+  IPK_REQUIRE(ep->mode >= 0 && ep->mode <= 2 && ep->in, "bad mode / null input state");
+  IPK_REQUIRE(ep->mode == 1 ? (ep->out2 && ep->out2 != ep->in && ep->an_C >= 1 && ep->an_c0 >= 0 && ep->an_c0 + ep->an_C <= a->ld &&
+                               (ep->an_log_scale == nullptr) == (ep->an_bias == nullptr) && !ep->ext)
+                            : (ep->out != nullptr), "bad outputs");
+  IPK_REQUIRE(!ep->logdet_slot || ep->slot_stride >= 4, "log-det slots are 4 wide (one per 16-row slice of a sample)");
+  IPK_REQUIRE(!ep->ext || ep->ext_ld >= a->Cp, "bad extra operand output");
+  IPK_REQUIRE(ipoke_conv_pair_coupling_applicable(g.M, p.Nout, p3.Nout, dtype),
+              "shape not taken by the fused launch (ipoke_conv_pair_coupling_applicable)");
+  IPK_REQUIRE(kLdsNtCpl <= device_max_lds(), "the fused launch needs 138 KB of LDS per workgroup");
+  CouplingEpi e{};
+  e.bias = a->bias; e.in = ep->in; e.out = ep->out; e.out2 = ep->mode == 1 ? ep->out2 : nullptr;
+  e.scale_out = ep->mode == 2 ? nullptr : ep->scale_out; e.logdet_slot = ep->mode == 2 ? nullptr : ep->logdet_slot;
+  e.an_ls = ep->an_log_scale; e.an_bias = ep->an_bias; e.an_idx = ep->an_idx; e.ext = ep->ext; e.xchg = ep->xchg;
+  e.xchg_bytes = (int)ipoke_conv3x3_coupling_xchg_bytes(); e.slot_stride = ep->slot_stride < 1 ? 1 : ep->slot_stride;
+  e.Cp = a->Cp; e.t_off = a->t_off; e.t_stride = a->t_stride; e.ld = a->ld; e.mode = ep->mode; e.an_c0 = ep->an_c0; e.an_C = ep->an_C;
+  e.ext_ld = ep->ext_ld; e.ext_bf16 = 1;
+  auto log2_or = [](int v) { int sh = 0; while ((1 << sh) < v) ++sh; return (1 << sh) == v ? sh : -1; };
+  e.ld_sh = log2_or(a->ld); e.cp_sh = log2_or(a->Cp); e.ts_sh = log2_or(a->t_stride);
+  NtCplEpi q3; q3.W3 = p3.W; q3.ldw3 = p3.ldw; q3.nout3 = p3.Nout;
+  if (!store_h2) p.C = nullptr;
+  p.prio = 2;                                              // (as ipoke_conv_forward: the chain's GEMMs win the issue arbitration)
+  p.w_kmajor = 0;
+  p.tiles_m = ceil_div(g.M, 128); p.tiles_n = p.Nout / 128; p.xa = p.xb = 0;      // block = tile * slices + slice: no XCD map
+  p.splitk = 1; p.kb_per_split = p.Ktot / 64;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  g_last_kernel = IPOKE_KERNEL_IGEMM;                      // ipoke_last_conv_kernel: the GEMM family, as for the conv2 launch this replaces
+  // tagged as ipoke_conv_forward tags conv2: that family's time now includes conv3 and the coupling
+  const bool square = p.Nout == p.Ktot && p.Nout >= 1024;
+  TimedScope ts(square ? IPOKE_TAG_NT_SQUARE : IPOKE_TAG_CONV_BASE, s);
+  switch (p.tiles_n) {
+    case 4: rc = launch_nt_coupling<4>(p, q3, e, s); break;
+    case 8: rc = launch_nt_coupling<8>(p, q3, e, s); break;
+    case 16: rc = launch_nt_coupling<16>(p, q3, e, s); break;
+    default: rc = launch_nt_coupling<32>(p, q3, e, s); break;
+  }
+  if (rc) return rc;
+  if (ts.slot >= 0)
+    ts.annotate(square ? 0 : IPOKE_TAG_CONV_BASE + IPOKE_KERNEL_IGEMM, 2.0 * g.M * p.Nout * ((double)p.Kc + 9.0 * p3.Nout),
+                2.0 * ((double)g.M * p.Kc + (double)p.Nout * p.Kc + (store_h2 ? (double)g.M * p.Nout : 0.0) + 9.0 * p3.Nout * p.Nout) +
+                    8.0 * g.M * a->ld);
   return IPOKE_OK;
 }
 

@@ -76,7 +76,7 @@ int ipoke_flow_test_split_pair_dgrad(ipoke_flow* f, int on);
  * gradient must come out bit-identical (the parity test of the fused launch); 0: back to the default.  Drops the handle's captured graphs. */
 int ipoke_flow_test_split_pair_coupling(ipoke_flow* f, int on);
 
-/* Test hook: forward unroll of the ConvGRU as one launch (1), as launches per phase (0), or the IPOKE_GRU_FUSED environment default (< 0) */
+/* Test hook: forward unroll of the ConvGRU as one launch (1), as launches per phase (0); < 0 goes back to the default (1) */
 int ipoke_gru_set_fused(int mode);
 /* Test hook: byte offsets into the ConvGRU unroll's workspace and row widths (in elements) of its per-(cell, step) buffers:
  * out[2 k], out[2 k + 1] for k = XH, XHR, UR, U, O, DO, DUR (operands [x | h], [x | h r]; pre-activations ur, the update gate u, the

@@ -128,9 +128,6 @@ __device__ __forceinline__ float act_grad_from_pre(int act, float f) {
 }
 
 // ---- kernel-argument prefetch ------------------------------------------------
-#ifndef IPK_KERNARG_PREFETCH
-#define IPK_KERNARG_PREFETCH 1      // (0: developer A/B build)
-#endif
 // hipcc fetches kernel arguments lazily (an s_load next to each first use, each behind its own s_waitcnt).  The argument block of a launch
 // is cold -- the command processor has just written it -- so every first touch of a 64-byte line is a memory round trip (~0.3 us) and a
 // kernel with a few hundred bytes of arguments starts with a CHAIN of them.  One dword of every line of the first BYTES bytes requested
@@ -157,12 +154,9 @@ __device__ __forceinline__ void kernarg_prefetch() {
 // x / d and x % d for a launch-uniform divisor: a shift / mask when d is a power of two (the state widths, channel counts and strides
 // of the shipped flows are), the compiler's ~25-instruction division sequence otherwise.  The test on `sh` is scalar; the element-wise
 // kernels of the chain spent 1-3 us per launch on index arithmetic before this.  Dividends are non-negative.
-#ifndef IPK_FDIV
-#define IPK_FDIV 1      // 0: always divide (developer A/B)
-#endif
 struct FDiv {
   int d, sh;
-  __device__ __forceinline__ explicit FDiv(int d_) : d(d_), sh(IPK_FDIV && d_ > 0 && (d_ & (d_ - 1)) == 0 ? __builtin_ctz((unsigned)d_) : -1) {}
+  __device__ __forceinline__ explicit FDiv(int d_) : d(d_), sh(d_ > 0 && (d_ & (d_ - 1)) == 0 ? __builtin_ctz((unsigned)d_) : -1) {}
   __device__ __forceinline__ int div(int x) const { return sh >= 0 ? x >> sh : x / d; }
   __device__ __forceinline__ int mod(int x) const { return sh >= 0 ? x & (d - 1) : x % d; }
   __device__ __forceinline__ long div(long x) const { return sh >= 0 ? x >> sh : x / d; }

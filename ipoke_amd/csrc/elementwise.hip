@@ -304,7 +304,7 @@ __device__ __forceinline__ void affine_ext_pad(const AffineArgs& a, void* ext, i
 __global__ void affine_fwd_kernel(AffineArgs a, const float* __restrict__ in, float* __restrict__ out,
                                   float* __restrict__ scale_out, float* __restrict__ logdet_slot, int slot_stride, int Q,
                                   void* __restrict__ ext, int ext_ld, int ext_bf16) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(AffineArgs) + 64>();
+  kernarg_prefetch<(int)sizeof(AffineArgs) + 64>();
   if (IPK_CHAIN_PRIO) __builtin_amdgcn_s_setprio(2);
   extern __shared__ float raw_s[];
   __shared__ float red[8];
@@ -375,7 +375,7 @@ __global__ __launch_bounds__(1024) void affine_bwd_kernel(int Cp, int t_off, int
                                                           const float* __restrict__ scale, const float* __restrict__ dld,
                                                           float* __restrict__ dx, T* __restrict__ dparams, int ldp,
                                                           float* __restrict__ dbias_part) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<84>();
+  kernarg_prefetch<84>();
   if (IPK_CHAIN_PRIO) __builtin_amdgcn_s_setprio(2);
   // Thread (r0, i) owns transformed channel i of rows r0, r0 + rows_par, ...: it loads (dy, scale, x) once for BOTH outputs
   // (d mu, d s), keeps their column sums in registers and hands them to a deterministic LDS reduction.  (Rounds 1-2: every
@@ -458,7 +458,7 @@ struct ActNormArgs { int c0, C; const float* ls; const float* bias; const int* i
 __global__ void affine_actnorm_fwd_kernel(AffineArgs a, ActNormArgs n, const float* __restrict__ in, float* __restrict__ out,
                                           float* __restrict__ out2, float* __restrict__ scale_out, float* __restrict__ logdet_slot,
                                           int slot_stride, int Q) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)(sizeof(AffineArgs) + sizeof(ActNormArgs)) + 48>();
+  kernarg_prefetch<(int)(sizeof(AffineArgs) + sizeof(ActNormArgs)) + 48>();
   if (IPK_CHAIN_PRIO) __builtin_amdgcn_s_setprio(2);
   extern __shared__ float raw_s[];                 // [rows][2Cp] raw (mu, s), then [rows][ld] the coupling's output rows
   __shared__ float red[8];
@@ -550,7 +550,7 @@ __global__ __launch_bounds__(1024) void actnorm_affine_bwd_kernel(ActNormArgs n,
                                                                   const float* __restrict__ dld, float* __restrict__ dx,
                                                                   T* __restrict__ dparams, int ldp, float* __restrict__ part,
                                                                   float* __restrict__ dbias_part) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(ActNormArgs) + 96>();
+  kernarg_prefetch<(int)sizeof(ActNormArgs) + 96>();
   if (IPK_CHAIN_PRIO) __builtin_amdgcn_s_setprio(2);
   extern __shared__ float sm[];                    // [P][ld] gradient w.r.t. the coupling's output, then the partial-sum area
   const int tid = threadIdx.x, b = blockIdx.x;
@@ -1071,8 +1071,7 @@ extern "C" int ipoke_adam_amsgrad_step_grid(float* p, const float* g, float* m, 
   // Persistent grid-stride launch: 4096 workgroups saturate HBM when the update runs alone; an update issued underneath
   // other work (max_blocks, the overlapped data-parallel path) uses one workgroup per CU so that it does not take every
   // wave slot of the chip for its whole duration (85.2 -> 81.3 ms when measured on one GPU).
-  static const int env_blocks = getenv("IPOKE_ADAM_BLOCKS") ? atoi(getenv("IPOKE_ADAM_BLOCKS")) : 0;
-  const int adam_blocks = env_blocks > 0 ? env_blocks : (max_blocks > 0 ? max_blocks : 4096);
+  const int adam_blocks = max_blocks > 0 ? max_blocks : 4096;
   const AdamHyper h{lr / (float)bc1, beta1, beta2, eps, weight_decay, (float)sqrt(bc2), grad_scale};
   hipLaunchKernelGGL(adam_amsgrad_kernel, dim3(grid_for((n + 3) / 4, 256, adam_blocks)), dim3(256), 0, STREAM(stream), p, g, m, v,
                      vmax, (long)n, h);

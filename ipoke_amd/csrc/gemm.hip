@@ -45,30 +45,7 @@ struct NtParams {
   // deterministic split-K accumulation (c_acc && splitk > 1, ipoke_conv_desc.acc_scratch): per-tile arrival counters (zero between
   // launches) and the slab area [tile][split][BM][BN] fp32; null -> the K slices are added with atomics (order-dependent rounding)
   unsigned* acc_cnt; float* acc_part; long acc_part_bytes;
-#ifdef IPOKE_GEMM_STAMPS
-  long long* stamps = nullptr;   // probe build only (scripts/probe_gemm_stamps.py): 4 wall-clock stamps per workgroup
-#endif
 };
-
-#if defined(IPOKE_GEMM_STAMPS) && IPOKE_GEMM_ABL == 1     // probe build: fragment reads kept alive, matrix cores idle
-#define GEMM_MMA(a, b, c) asm volatile("" :: "v"(a), "v"(b))
-#else
-#define GEMM_MMA(a, b, c) mma64(a, b, c)
-#endif
-#ifdef IPOKE_GEMM_STAMPS
-#define GEMM_STAMP(i) do { if (p.stamps && threadIdx.x == 0) p.stamps[(blockIdx.x + blockIdx.y * gridDim.x) * 4 + (i)] = wall_clock64(); } while (0)
-#else
-#define GEMM_STAMP(i) do {} while (0)
-#endif
-
-// Probe builds of the LDS-DMA weight-gradient kernel (scripts/probe_tn_phases.sh; never in the shipped library):
-// -DIPOKE_TN_ABL=1 matrix cores idle, 2 neither fragment reads nor matrix cores, 3 no DMA, 4 no epilogue stores
-#ifndef IPOKE_TN_ABL
-#define IPOKE_TN_ABL 0
-#endif
-#ifndef IPOKE_H16_ABL         // the same for conv3x3_halo16_kernel: 1 matrix cores idle, 2 DMA and barriers only, 3 no DMA
-#define IPOKE_H16_ABL 0
-#endif
 
 // one problem of a batched weight-gradient launch (blockIdx.z): byte/float offsets against the launch's bases
 struct TnBatchEntry { long a_off, y_off, w_off; int kh, kw, ph, pw; long sh_off; };      // sh_off: element offset of the problem's operand copy (fused Adam)
@@ -442,7 +419,7 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[MREP
 // =============================================================================================
 template <typename T, int WM, int WN, int MREP, int NREP>
 __global__ __launch_bounds__(256) void igemm_nt_kernel(const NtParams p) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(NtParams)>();
+  kernarg_prefetch<(int)sizeof(NtParams)>();
   constexpr int BM = WM * MREP * 16, BN = WN * NREP * 16;
   constexpr int E16 = ET<T>::E16;
   constexpr int BK = 128 / (int)sizeof(T);
@@ -596,7 +573,7 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_
 // bound the math side of these small-M GEMMs (every wave re-reads the whole A tile).
 template <typename T, int WM, int WN, int MREP, int NREP, int NSTAGE, int KPB, bool SIMPLE, int WK = 1>
 __global__ __launch_bounds__(WM * WN * WK * 64) void igemm_nt_glds_kernel(const NtParams p) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(NtParams)>();
+  kernarg_prefetch<(int)sizeof(NtParams)>();
   constexpr int NTHR = WM * WN * WK * 64;          // 4 or 8 wave64 (8 waves = two per SIMD: one's LDS reads hide under the other's MFMAs)
   constexpr int BM = WM * MREP * 16, BN = WN * NREP * 16;
   constexpr int E16 = ET<T>::E16;
@@ -613,7 +590,6 @@ __global__ __launch_bounds__(WM * WN * WK * 64) void igemm_nt_glds_kernel(const 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* dummy = smem + NSTAGE * STAGE;                         // 1 KB per wave: landing zone of padding DMAs
   int* taptab = reinterpret_cast<int*>(smem + NSTAGE * STAGE + NTHR * 16);
-  GEMM_STAMP(0);
   if (p.prio == 1) __builtin_amdgcn_s_setprio(1); else if (p.prio == 2) __builtin_amdgcn_s_setprio(2); else if (p.prio == 3) __builtin_amdgcn_s_setprio(3);     // chain kernels win the SIMD's issue arbitration against co-resident side-stream waves
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -640,9 +616,6 @@ __global__ __launch_bounds__(WM * WN * WK * 64) void igemm_nt_glds_kernel(const 
   const int nkb_total = (p.Ktot + BK - 1) / BK;
   const int kb_begin = z * p.kb_per_split;
   const int kb_end = min(nkb_total, kb_begin + p.kb_per_split);
-#if defined(IPOKE_GEMM_STAMPS) && IPOKE_GEMM_ABL == 8      // probe build: stamp 1 = kernel arguments have arrived (tile indices computed)
-  if (kb_end > m0 + n0 - 1000000) GEMM_STAMP(1);
-#endif
 
   fill_taptab(taptab, g);
 
@@ -712,11 +685,6 @@ __global__ __launch_bounds__(WM * WN * WK * 64) void igemm_nt_glds_kernel(const 
       if (!SIMPLE) b_k[i] += BK;
       if (b_off[i] != kInvalid) b_off[i] += BK;
     }
-#if defined(IPOKE_GEMM_STAMPS) && (IPOKE_GEMM_ABL == 5 || IPOKE_GEMM_ABL == 6)   // probe build: every K-block re-reads the first one (L2 hits only)
-#pragma unroll
-    for (int i = 0; i < B_IT; ++i) if (b_off[i] != kInvalid) b_off[i] -= BK;
-    return;
-#endif
     if (SIMPLE) {
       c_uni += BK;
       if (c_uni >= p.Kc) {                          // uniform: every chunk enters the next tap together
@@ -763,18 +731,10 @@ __global__ __launch_bounds__(WM * WN * WK * 64) void igemm_nt_glds_kernel(const 
   auto issue_slot = [&](int slot) {
 #pragma unroll
     for (int u = 0; u < KPB; ++u) {
-#if defined(IPOKE_GEMM_STAMPS) && IPOKE_GEMM_ABL == 2      // probe build: no operand traffic (every DMA goes to the dummy zone)
-      issue(slot * STAGE + u * SUB, false);
-#elif defined(IPOKE_GEMM_STAMPS) && IPOKE_GEMM_ABL == 3    // probe build: no DMA instructions at all
-#else
       issue(slot * STAGE + u * SUB, kb_issue < kb_end);
-#endif
       ++kb_issue;
     }
   };
-#if defined(IPOKE_GEMM_STAMPS) && IPOKE_GEMM_ABL == 7      // probe build: stamp 1 = set-up done, nothing requested yet
-  GEMM_STAMP(1);
-#endif
 #pragma unroll
   for (int s = 0; s < NSTAGE - 1; ++s) issue_slot(s);
 
@@ -799,16 +759,10 @@ __global__ __launch_bounds__(WM * WN * WK * 64) void igemm_nt_glds_kernel(const 
   for (int kb = kb_begin; kb < kb_end; kb += KPB) {
     wait_vmcnt<(NSTAGE - 2) * L * KPB>();      // this wave's share of the oldest slot has landed
     __builtin_amdgcn_s_barrier();                     // ... and everybody else's; all reads of the slot refilled below are done
-#if !(defined(IPOKE_GEMM_STAMPS) && (IPOKE_GEMM_ABL == 7 || IPOKE_GEMM_ABL == 8))
-    if (kb == kb_begin) GEMM_STAMP(1);
-#endif
     issue_slot((slot + NSTAGE - 1) % NSTAGE);
     const unsigned char* base = smem + slot * STAGE;
     slot = (slot + 1) % NSTAGE;
     const int nsub = min(KPB, kb_end - kb);
-#if defined(IPOKE_GEMM_STAMPS) && (IPOKE_GEMM_ABL == 4 || IPOKE_GEMM_ABL == 5)      // probe build: operand stream only
-    if (nsub < 0)
-#endif
     if constexpr (WK == 1) {
       // 2*nsub half-steps; fragments of half-step h+1 are fetched while the matrix cores work on h
       frag_t fa[2][MREP], fb[2][NREP];
@@ -820,7 +774,7 @@ __global__ __launch_bounds__(WM * WN * WK * 64) void igemm_nt_glds_kernel(const 
 #pragma unroll
           for (int i = 0; i < MREP; ++i)
 #pragma unroll
-            for (int j = 0; j < NREP; ++j) GEMM_MMA(fa[h & 1][i], fb[h & 1][j], acc[i][j]);
+            for (int j = 0; j < NREP; ++j) mma64(fa[h & 1][i], fb[h & 1][j], acc[i][j]);
         }
       }
     } else {
@@ -834,13 +788,12 @@ __global__ __launch_bounds__(WM * WN * WK * 64) void igemm_nt_glds_kernel(const 
 #pragma unroll
           for (int i = 0; i < MREP; ++i)
 #pragma unroll
-            for (int j = 0; j < NREP; ++j) GEMM_MMA(fa[t & 1][i], fb[t & 1][j], acc[i][j]);
+            for (int j = 0; j < NREP; ++j) mma64(fa[t & 1][i], fb[t & 1][j], acc[i][j]);
         }
       }
     }
   }
   wait_vmcnt<0>();                         // only padding DMAs (to the dummy zone) can still be in flight
-  GEMM_STAMP(2);
   if constexpr (WK > 1) {                  // the two K halves meet: group 1 hands its partial sums to group 0 through LDS
     constexpr int EP = BN * 4 + 16;
     unsigned char* st2 = smem + BM * EP + (wm * MREP * 16 + (lane & 15)) * EP + (wn * NREP * 16 + (lane >> 4) * 4) * 4;
@@ -860,14 +813,13 @@ __global__ __launch_bounds__(WM * WN * WK * 64) void igemm_nt_glds_kernel(const 
     }
   }
   nt_epilogue<T, WM, WN, MREP, NREP, NTHR, WK == 1 && NtDet<WM, WN, MREP, NREP>::value>(p, acc, smem, m0, n0, wm, wn, z, wk == 0);
-  GEMM_STAMP(3);
 }
 
 // =============================================================================================
 // weight gradient
 template <typename T, int NR>
 __global__ __launch_bounds__(256) void igemm_tn_kernel(const TnParams pin) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(TnParams)>();
+  kernarg_prefetch<(int)sizeof(TnParams)>();
   TnParams p = pin;
   if (pin.batch) {                       // batched launch: blockIdx.z selects operands and the 2-D tap geometry
     const TnBatchEntry e = pin.batch[blockIdx.z + pin.z0];
@@ -1199,11 +1151,6 @@ static constexpr int kCplHeader = 256;                 // bytes: word 0 counts s
 static constexpr unsigned kCplEmpty = 0xffffffffu;     // a dword of the exchange scratch nobody has written yet (a NaN no sum produces)
 static constexpr unsigned kCplSpinMax = 1u << 21;
 
-#ifdef IPOKE_GEMM_STAMPS      // probe build: 4 (plain) / 8 (fused) wall-clock stamps per workgroup
-#define S8_STAMP(i) do { if (p.stamps && threadIdx.x == 0) p.stamps[(blockIdx.x + blockIdx.y * gridDim.x) * (NSPLIT ? 16 : 4) + (i)] = wall_clock64(); } while (0)
-#else
-#define S8_STAMP(i) do {} while (0)
-#endif
 // The coupling side of a fused launch: what conv3x3_s8_coupling_kernel and igemm_nt_coupling_kernel do around and behind the K loop of the
 // skinny convolution.  ONE piece of code for both (tests/test_pair_coupling_gpu.py compares the two launches bit for bit): prefetch()
 // ahead of the K loop, pin() behind the loop's last wait for vector memory, run() with the accumulators of the four K groups of the
@@ -1329,7 +1276,6 @@ struct CouplingTail {
       else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_x,
                                                   kCplHeader + (((tile * NOWN + o) * NSPLIT + z) * RPO + r) * 256 + cq * 16, 0, 16);
     }
-    S8_STAMP(4);
     if (!owner) return;              // (uniform) this workgroup owns no rows
     // LDS from here on: own [RPO][64] | bsum [4][RPO][64] | raw_s [RPO][64] | an_tile [NSL][16][ld] | red [8]
     float* own = reinterpret_cast<float*>(smem);
@@ -1352,7 +1298,6 @@ struct CouplingTail {
         }
       lds_barrier();                 // every read of the parked tiles is done
       if (mine_off >= 0) *reinterpret_cast<f32x4*>(reinterpret_cast<unsigned char*>(own) + mine_off) = mine;
-      S8_STAMP(7);
       unsigned spins = 0;
       for (;;) {
         bool ok = true;
@@ -1371,7 +1316,6 @@ struct CouplingTail {
             if (ro[ch][m] >= 0 && (rv[ch][m][0] == kCplEmpty || rv[ch][m][1] == kCplEmpty || rv[ch][m][2] == kCplEmpty || rv[ch][m][3] == kCplEmpty))
               rv[ch][m] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, ro[ch][m], 0, 16);
       }
-      S8_STAMP(5);
       lds_barrier();                 // own rows are in LDS
 #pragma unroll
       for (int ch = 0; ch < NCH; ++ch) {
@@ -1387,7 +1331,6 @@ struct CouplingTail {
         *reinterpret_cast<f32x4*>(bsum + gq * RPO * 64 + (tl + 128 * ch) * 4) = b;
       }
       lds_barrier();
-      S8_STAMP(8);
       if (tid < RPO * 16) {
         const f32x4 b0 = *reinterpret_cast<const f32x4*>(bsum + tid * 4), b1 = *reinterpret_cast<const f32x4*>(bsum + RPO * 64 + tid * 4),
                     b2 = *reinterpret_cast<const f32x4*>(bsum + 2 * RPO * 64 + tid * 4), b3 = *reinterpret_cast<const f32x4*>(bsum + 3 * RPO * 64 + tid * 4);
@@ -1401,7 +1344,6 @@ struct CouplingTail {
       }
       lds_barrier();
     }
-    S8_STAMP(6);
     // the scratch goes back to its initial state (nothing waits for these stores; they drain under the coupling's arithmetic)
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch)
@@ -1438,7 +1380,6 @@ struct CouplingTail {
           }
         }
       }
-      S8_STAMP(9);
       float ld_acc = 0.f;
       if (valid) {
 #pragma unroll
@@ -1472,7 +1413,6 @@ struct CouplingTail {
           }
         }
       }
-      S8_STAMP(10);
       if (e.mode != 2) {             // per-slice log-det: block_sum of a 256-thread block
         if constexpr (NSL == 1) {    // thread t256 of the block summed its first, then its second element
           if (hf == 1) lx[t256] = ld_acc;
@@ -1487,7 +1427,6 @@ struct CouplingTail {
         if (valid && t256 == 0 && (NSL > 1 || hf == 0) && e.logdet_slot)
           e.logdet_slot[(long)(row0 >> 6) * e.slot_stride + ((int)(row0 >> 4) & 3)] = tot;
       }
-      S8_STAMP(11);
       if (with_an && valid) {        // ActNorm (+ shuffle) of the slice's rows: out2
         for (int el = NSL == 1 ? tid : t256; el < 16 * ld; el += NSL == 1 ? 512 : 256) {
           int pp, col; div_ld(el, pp, col);
@@ -1533,7 +1472,6 @@ __device__ __forceinline__ void conv3x3_s8_body(const NtParams& p, const Couplin
   unsigned char* zrow = smem + 2 * ABUF;                   // 256 bytes of zeros: the "outside the map" row
   unsigned char* ring = zrow + 256;                        // R filter K-blocks
   unsigned char* dummy = ring + R * WSLOT;                 // landing zone of padding DMAs, 1 KB per wave
-  S8_STAMP(0);
   if (p.prio == 1) __builtin_amdgcn_s_setprio(1); else if (p.prio == 2) __builtin_amdgcn_s_setprio(2); else if (p.prio == 3) __builtin_amdgcn_s_setprio(3);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1572,14 +1510,7 @@ __device__ __forceinline__ void conv3x3_s8_body(const NtParams& p, const Couplin
     const bool in = wi_g < nkb;
 #pragma unroll
     for (int j = 0; j < WJ; ++j) {
-#if defined(IPOKE_GEMM_STAMPS) && IPOKE_GEMM_ABL == 3
-      continue;
-#endif
-#if defined(IPOKE_GEMM_STAMPS) && IPOKE_GEMM_ABL == 2
-      const bool real = false;
-#else
       const bool real = in && w_src[j] != kInvalid;
-#endif
       const T* src = real ? Wbase + w_src[j] + (long)wi_t * p.Kc + wi_c * 64 : zero;
       unsigned char* dst = in ? ring + (wi_g % R) * WSLOT + (WJ * (wave >> 2) + j) * 1024 : dummy + wave * 1024;
       __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)dst, 16, 0, 0);
@@ -1591,14 +1522,7 @@ __device__ __forceinline__ void conv3x3_s8_body(const NtParams& p, const Couplin
   auto issue_a = [&]() {
 #pragma unroll
     for (int i = 0; i < A_IT; ++i) {
-#if defined(IPOKE_GEMM_STAMPS) && IPOKE_GEMM_ABL == 3
-      continue;
-#endif
-#if defined(IPOKE_GEMM_STAMPS) && IPOKE_GEMM_ABL == 2
-      const bool real = false;
-#else
       const bool real = a_next < nch && a_src[i] != kInvalid;
-#endif
       const T* src = real ? Abase + a_src[i] + a_next * 64 : zero;
       unsigned char* dst = a_next < nch ? abuf + (a_next & 1) * ABUF + (wave + 8 * i) * 1024 : dummy + wave * 1024;
       __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)dst, 16, 0, 0);
@@ -1641,7 +1565,6 @@ __device__ __forceinline__ void conv3x3_s8_body(const NtParams& p, const Couplin
   for (int r = 0; r < nrounds; ++r) {
     wait_vmcnt<WJ>();                // everything but this wave's share of round r + 1 has landed (input chunks included)
     __builtin_amdgcn_s_barrier();
-    if (r == 0) S8_STAMP(1);
     // the first K-block of this round lies in chunk (4r)/9: request the chunk after it once (its buffer held chunk - 1,
     // whose last K-block was consumed before this barrier)
     if (a_next <= (4 * r) / 9 + 1) issue_a();          // (issued before the filter blocks: the wait above counts those only)
@@ -1672,7 +1595,7 @@ __device__ __forceinline__ void conv3x3_s8_body(const NtParams& p, const Couplin
 #pragma unroll
         for (int i = 0; i < MREP; ++i)
 #pragma unroll
-          for (int j = 0; j < NREP; ++j) GEMM_MMA(fa[hs][i], fb[hs][j], acc[i][j]);
+          for (int j = 0; j < NREP; ++j) mma64(fa[hs][i], fb[hs][j], acc[i][j]);
       // issue order: the eight fragments of the first half-step, then the second half-step's reads one per two MFMAs of the first.
       // (hipcc's own schedule reads just in time, four MFMAs per s_waitcnt lgkmcnt(0): eight exposed LDS latencies per K-block.)
       constexpr int NF = MREP + NREP, NM = MREP * NREP, PER = NM / NF;        // fragment reads / MFMAs per half-step
@@ -1688,7 +1611,6 @@ __device__ __forceinline__ void conv3x3_s8_body(const NtParams& p, const Couplin
     if (t >= 9) { t -= 9; ++ci; }
   }
   wait_vmcnt<0>();
-  S8_STAMP(2);
   if constexpr (NSPLIT > 0) ct.pin();
   if constexpr (NSPLIT == 0) {
   // the four K groups meet: groups 2, 3 hand over to groups 0, 1, then group 1 to group 0 (nt_epilogue's staging layout)
@@ -1720,22 +1642,21 @@ __device__ __forceinline__ void conv3x3_s8_body(const NtParams& p, const Couplin
   } else {
     ct.run(p, smem, tile, z, mh, kq, acc);
   }
-  S8_STAMP(3);
 }
 
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_s8_kernel(const NtParams p) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(NtParams)>();
+  kernarg_prefetch<(int)sizeof(NtParams)>();
   CouplingEpi none{};
   conv3x3_s8_body<0>(p, none, blockIdx.x, blockIdx.y);
 }
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_s8n32_kernel(const NtParams p) {      // <= 32 output columns
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(NtParams)>();
+  kernarg_prefetch<(int)sizeof(NtParams)>();
   CouplingEpi none{};
   conv3x3_s8_body<0, 2>(p, none, blockIdx.x, blockIdx.y);
 }
 template <int NSPLIT>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_s8_coupling_kernel(const NtParams p, const CouplingEpi e) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)(sizeof(NtParams) + sizeof(CouplingEpi))>();
+  kernarg_prefetch<(int)(sizeof(NtParams) + sizeof(CouplingEpi))>();
   conv3x3_s8_body<NSPLIT>(p, e, blockIdx.x / NSPLIT, blockIdx.x % NSPLIT);
 }
 
@@ -1750,7 +1671,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // [Nout][9 * Kc] operand, the nine blocks stream through six slots in rounds of three; 8 waves = 2 row halves x 4 column groups of
 // 64 x 32 wave tiles; the epilogue is nt_epilogue (bias, ELU, ELU' mask of the data-gradient form, dtype output).
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_k64_kernel(const NtParams p) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(NtParams)>();
+  kernarg_prefetch<(int)sizeof(NtParams)>();
   typedef bf16_t T;
   typedef typename ET<T>::frag frag_t;
   typedef __attribute__((address_space(3))) void lds_void;
@@ -1856,7 +1777,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
       for (int i = 0; i < MREP; ++i)
 #pragma unroll
-        for (int j = 0; j < NREP; ++j) GEMM_MMA(fa[i], fb[j], acc[i][j]);
+        for (int j = 0; j < NREP; ++j) mma64(fa[i], fb[j], acc[i][j]);
     }
   };
 
@@ -1890,7 +1811,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // minus the "outside the map" masks (the zero border is materialised by the staging DMA).  Output channels are tiled by 64
 // over blockIdx.y.  transposed (data gradient): the taps are mirrored, the caller supplies the transposed filter operand.
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_halo_kernel(const NtParams p) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(NtParams)>();
+  kernarg_prefetch<(int)sizeof(NtParams)>();
   typedef bf16_t T;
   typedef typename ET<T>::frag frag_t;
   typedef typename Pack4<T>::type pack_t;
@@ -2007,7 +1928,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int i = 0; i < MREP; ++i)
 #pragma unroll
-          for (int j = 0; j < NREP; ++j) GEMM_MMA(fa[hs][i], fb[hs][j], acc[i][j]);
+          for (int j = 0; j < NREP; ++j) mma64(fa[hs][i], fb[hs][j], acc[i][j]);
       // issue order as in conv3x3_s8_kernel: first half-step's fragments, then one read of the second per two MFMAs of the first
       __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
 #pragma unroll
@@ -2117,7 +2038,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // through a three-slot ring.  Per output the DMA traffic is a third of the implicit GEMM's and the loop is bound by the matrix
 // cores: 8 waves = 4 pixel-row groups x 2 channel halves, 64 x 64 outputs each, 32 MFMAs per wave and barrier.
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_halo16_kernel(const NtParams p) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(NtParams)>();
+  kernarg_prefetch<(int)sizeof(NtParams)>();
   typedef bf16_t T;
   typedef typename ET<T>::frag frag_t;
   typedef typename Pack4<T>::type pack_t;
@@ -2251,7 +2172,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
       for (int i = 0; i < MREP; ++i)
 #pragma unroll
-        for (int j = 0; j < NREP; ++j) GEMM_MMA(fa[hs][i], fb[hs][j], acc[i][j]);
+        for (int j = 0; j < NREP; ++j) mma64(fa[hs][i], fb[hs][j], acc[i][j]);
   };
   // Round r: [K-block r + 1 has landed] barrier | DMA of K-block r + 3 (and, every ninth round, of the next halo image) | fragment
   // reads of K-block r + 1 into the other register set | 32 MFMAs on K-block r, two MFMAs per read in issue order.  The LDS latency
@@ -2268,39 +2189,26 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (t == 1 || t == 2) wait_vmcnt<A_IT + W_IT>(); else wait_vmcnt<W_IT>();
     __builtin_amdgcn_s_barrier();
     const int tn = t == tlast ? 0 : t + 1, cn = t == tlast ? ci + 1 : ci;
-#if IPOKE_H16_ABL != 2
     read_frags(fa_nxt, fb_nxt, r + 1, cn, tn);      // (past the last K-block: stale LDS contents, never multiplied)
-#if IPOKE_H16_ABL == 1
-#pragma unroll
-    for (int hs = 0; hs < 2; ++hs)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { asm volatile("" :: "v"(fa_cur[hs][i])); asm volatile("" :: "v"(fb_cur[hs][i])); }
-#else
     // first half of the matrix work, one fragment read per MFMA in issue order: with the sixteen reads in front, eight waves queue
     // 128 ds_read_b128 on the LDS pipe after every barrier before any of them reaches its first MFMA (no-DMA build: 0.95 -> 0.79 us
     // per round, against 0.54 of MFMA time)
 #pragma unroll
     for (int i = 0; i < MREP; ++i)
 #pragma unroll
-      for (int j = 0; j < NREP; ++j) GEMM_MMA(fa_cur[0][i], fb_cur[0][j], acc[i][j]);
+      for (int j = 0; j < NREP; ++j) mma64(fa_cur[0][i], fb_cur[0][j], acc[i][j]);
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
       __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
     }
-#endif
-#endif
-#if IPOKE_H16_ABL != 3
     // the round's transfers are issued between the two halves: behind the barrier they would keep every wave off the matrix cores
     issue_w();                                   // K-block r + 3 -> the slot of K-block r - 1
     if (t == 0) issue_a();                       // image ci + 1 -> the buffer of image ci - 1 (a padding transfer past the end)
-#endif
-#if IPOKE_H16_ABL == 0
 #pragma unroll
     for (int i = 0; i < MREP; ++i)
 #pragma unroll
-      for (int j = 0; j < NREP; ++j) GEMM_MMA(fa_cur[1][i], fb_cur[1][j], acc[i][j]);
-#endif
+      for (int j = 0; j < NREP; ++j) mma64(fa_cur[1][i], fb_cur[1][j], acc[i][j]);
     t = tn; ci = cn;
   };
   for (int r = 0; r < nkb; r += 2) {
@@ -2384,15 +2292,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // per image.  Taps are the kh x kw window at offsets a - ph (ph - a for the data gradient), all within the one-pixel halo.
 // 8 waves = 4 pixel-row groups x 2 halves of 32 output channels; fragments beyond Nout are skipped (the image head computes 16 of
 // 64 columns); the epilogue runs from the accumulators.
-#ifndef IPOKE_C64_ABL
-// probe builds (scripts/probe_c64.py): 1 no MFMA, 2 no epilogue, 3 no image stream.  Round 4, 64 -> 64 at 128 x 128, 480 images: 937 us
+// Measured with one phase taken out at a time (no MFMA / no epilogue / no image stream), 64 -> 64 at 128 x 128, 480 images: 937 us
 // full, 681 / 663 / 756 us ablated -- the three phases of a patch (wait for the image 1.5 us, MFMAs 2.2 us, epilogue 2.4 us) run one after
 // the other; deferring the epilogue by one image (its stores issued in front of the next patch's MFMAs) measured 964 us: not the stores'
 // acknowledgement at the loop's vmcnt(0).
-#define IPOKE_C64_ABL 0
-#endif
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_c64_kernel(const NtParams p) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(NtParams)>();
+  kernarg_prefetch<(int)sizeof(NtParams)>();
   typedef bf16_t T;
   typedef typename ET<T>::frag frag_t;
   typedef typename Pack4<T>::type pack_t;
@@ -2466,9 +2371,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int ch = v % nch;
     wait_vmcnt<0>();                               // this image (and, the first time, the filter) has landed
     __builtin_amdgcn_s_barrier();                  // ... everybody's share of it; the other buffer is no longer read
-#if IPOKE_C64_ABL != 3
     issue_image(next_image(v), buf ^ 1);
-#endif
     if (ch == 0) {
 #pragma unroll
       for (int i = 0; i < MREP; ++i)
@@ -2492,22 +2395,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
 #pragma unroll
         for (int j = 0; j < NREP; ++j) fb[j] = *reinterpret_cast<const frag_t*>(wb + (b_rd[j] ^ (hs * 64)));
-#if IPOKE_C64_ABL == 1
-#pragma unroll
-        for (int i = 0; i < MREP; ++i) asm volatile("" :: "v"(fa[i]), "v"(fb[0]), "v"(fb[1]));
-#else
 #pragma unroll
         for (int i = 0; i < MREP; ++i) {
-          GEMM_MMA(fa[i], fb[0], acc[i][0]);
-          if (nfrag > 1) GEMM_MMA(fa[i], fb[1], acc[i][1]);
+          mma64(fa[i], fb[0], acc[i][0]);
+          if (nfrag > 1) mma64(fa[i], fb[1], acc[i][1]);
         }
-#endif
       }
     }
     if (ch + 1 < nch) continue;
-#if IPOKE_C64_ABL == 2
-    if (v >= 0) { asm volatile("" :: "v"(acc[0][0]), "v"(acc[1][0]), "v"(acc[2][0]), "v"(acc[3][0]), "v"(acc[0][1]), "v"(acc[1][1]), "v"(acc[2][1]), "v"(acc[3][1])); continue; }
-#endif
     // ---- epilogue straight from the accumulators: acc[i][j][e] = pixel (wm*4 + i, lane & 15), channel wn*32 + 16 j + 4 (lane >> 4) + e
     const int tile = v / nch;
     const int tx = tile % tiles_x, t2 = tile / tiles_x, ty = t2 % tiles_y, img = t2 / tiles_y;
@@ -2737,7 +2632,7 @@ static int launch_nt(NtParams& p, hipStream_t s) {
 // 48 registers per lane, and with the operand roles of mma64 a lane ends up with four consecutive output channels of its pixel: 8-byte
 // stores.  Persistent waves, the next group's three loads in flight under the twelve matrix-core instructions of the current one.
 __global__ __launch_bounds__(256) void conv3x3_k8_kernel(const NtParams p) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(NtParams)>();
+  kernarg_prefetch<(int)sizeof(NtParams)>();
   const GeomDev& g = p.g;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int m16 = lane & 15, kg = lane >> 4;
@@ -2882,7 +2777,6 @@ extern "C" int ipoke_conv3x3_skinny_splitk(int M, int Kc, int dtype) {
 }
 
 static thread_local int g_last_kernel = IPOKE_KERNEL_NONE;     // (see ipoke_last_conv_kernel)
-static long long* g_gemm_stamps = nullptr;                          // probe builds (ipoke_gemm_set_stamps)
 static int conv_params(NtParams& p, const ipoke_conv_desc* d, int dtype);
 
 // K splits of the fused conv3 + coupling launch: the largest power of two (4 .. 32) that keeps tiles x splits within one round of
@@ -2952,10 +2846,6 @@ extern "C" int ipoke_conv3x3_coupling(const ipoke_conv_desc* conv, const ipoke_a
   auto log2_or = [](int v) { int sh = 0; while ((1 << sh) < v) ++sh; return (1 << sh) == v ? sh : -1; };
   e.ld_sh = log2_or(a->ld); e.cp_sh = log2_or(a->Cp); e.ts_sh = log2_or(a->t_stride);
   p.prio = 2;
-#ifdef IPOKE_GEMM_STAMPS
-  p.stamps = g_gemm_stamps;
-  if (g_gemm_stamps) g_gemm_stamps += 16 * 4096;               // one slab of 4096 workgroups x 16 stamps per fused launch
-#endif
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   g_last_kernel = IPOKE_KERNEL_S8;
   switch (ns) {
@@ -3032,7 +2922,7 @@ __device__ __forceinline__ int tn_swz(int row) { return 2 * ((row & 3) | (((row 
 // The transposing reads are inline assembly, not __builtin_amdgcn_ds_read_tr16_b64: hipcc's wait-count insertion treats every
 // LDS read with a memory operand as a possible reader of ALL LDS-DMA writes in flight and puts `s_waitcnt vmcnt(0)` in front of the
 // first fragment read of an iteration -- the stage issued a few instructions earlier had to land before the stage already in
-// LDS could be read, i.e. DMA and math ran one after the other (conv2 shape, phase-ablation builds -DIPOKE_TN_ABL: DMA alone
+// LDS could be read, i.e. DMA and math ran one after the other (conv2 shape, one phase at a time: DMA alone
 // 11.9 us, reads + matrix cores alone 13.2 us, epilogue 4.1 us, whole kernel 29.2 us = their sum).  The assembly reads carry no
 // memory operand; the kernel waits for them itself (tn_wait_frags ties the registers to the s_waitcnt).
 typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 tn_tr4_t;
@@ -3056,7 +2946,7 @@ template <typename F> __device__ __forceinline__ void tn_wait_frags(F (&f)[6]) {
 // read with the transposing ds_read_b64_tr_b16 (two per fragment; inline assembly, see tn_ds_tr).
 template <int WM, int WN, int MREP, int NSTAGE, int WK>
 __global__ __launch_bounds__(WM * WN * WK * 64) void igemm_nn_glds_kernel(const NtParams p) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(NtParams)>();
+  kernarg_prefetch<(int)sizeof(NtParams)>();
   typedef bf16_t T;
   constexpr int NREP = 2, NTHR = WM * WN * WK * 64, NWAVE = NTHR / 64;
   constexpr int BM = WM * MREP * 16, BN = WN * NREP * 16;
@@ -3190,7 +3080,7 @@ __global__ __launch_bounds__(WM * WN * WK * 64) void igemm_nn_glds_kernel(const 
 #pragma unroll
       for (int i = 0; i < MREP; ++i)
 #pragma unroll
-        for (int j = 0; j < NREP; ++j) GEMM_MMA(fa[i], fb[j], acc[i][j]);
+        for (int j = 0; j < NREP; ++j) mma64(fa[i], fb[j], acc[i][j]);
     } else {
       frag_t fa[2][MREP], fb[2][NREP];
       read_b(fb[0], sb, 0);
@@ -3203,12 +3093,12 @@ __global__ __launch_bounds__(WM * WN * WK * 64) void igemm_nn_glds_kernel(const 
 #pragma unroll
       for (int i = 0; i < MREP; ++i)
 #pragma unroll
-        for (int j = 0; j < NREP; ++j) GEMM_MMA(fa[0][i], fb[0][j], acc[i][j]);
+        for (int j = 0; j < NREP; ++j) mma64(fa[0][i], fb[0][j], acc[i][j]);
       wait_b(fb[1]);
 #pragma unroll
       for (int i = 0; i < MREP; ++i)
 #pragma unroll
-        for (int j = 0; j < NREP; ++j) GEMM_MMA(fa[1][i], fb[1][j], acc[i][j]);
+        for (int j = 0; j < NREP; ++j) mma64(fa[1][i], fb[1][j], acc[i][j]);
     }
   }
   wait_vmcnt<0>();
@@ -3293,7 +3183,7 @@ static constexpr size_t kLdsPair = kPairDummy + 8 * 1024;
 static_assert(kPairZrow + 256 <= kPairRing && 3 * (128 * 128 + 64 * 256) <= kPairRing, "LDS regions of igemm_nn_pair_kernel overlap");
 
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void igemm_nn_pair_kernel(const NtParams p, const PairEpi e) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)(sizeof(NtParams) + sizeof(PairEpi)) < 512 ? (int)(sizeof(NtParams) + sizeof(PairEpi)) : 512>();
+  kernarg_prefetch<(int)(sizeof(NtParams) + sizeof(PairEpi)) < 512 ? (int)(sizeof(NtParams) + sizeof(PairEpi)) : 512>();
   typedef bf16_t T;
   typedef typename ET<T>::frag frag_t;
   typedef typename Pack4<T>::type pack_t;
@@ -3454,12 +3344,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
       for (int i = 0; i < MREP; ++i)
 #pragma unroll
-        for (int j = 0; j < NREP; ++j) GEMM_MMA(fa[0][i], fb[0][j], acc[i][j]);
+        for (int j = 0; j < NREP; ++j) mma64(fa[0][i], fb[0][j], acc[i][j]);
       wait_b(fb[1]);
 #pragma unroll
       for (int i = 0; i < MREP; ++i)
 #pragma unroll
-        for (int j = 0; j < NREP; ++j) GEMM_MMA(fa[1][i], fb[1][j], acc[i][j]);
+        for (int j = 0; j < NREP; ++j) mma64(fa[1][i], fb[1][j], acc[i][j]);
     }
   }
   wait_vmcnt<0>();
@@ -3569,7 +3459,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int i = 0; i < MREP; ++i)
 #pragma unroll
-          for (int j = 0; j < CREP; ++j) GEMM_MMA(fa[hs][i], fb[hs][j], acc2[i][j]);
+          for (int j = 0; j < CREP; ++j) mma64(fa[hs][i], fb[hs][j], acc2[i][j]);
       // (issue order as in conv3x3_s8_body: the first half-step's fragments, then one read of the second per MFMA of the first)
       constexpr int NF = MREP + CREP, NM = MREP * CREP, PER = NM / NF;
       __builtin_amdgcn_sched_group_barrier(0x100, NF, 0);
@@ -3653,7 +3543,7 @@ static_assert(kLdsNtCpl <= 160 * 1024, "LDS per workgroup");
 
 template <int NSPLIT>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void igemm_nt_coupling_kernel(const NtParams p, const NtCplEpi q3, const CouplingEpi e) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)(sizeof(NtParams) + sizeof(NtCplEpi) + sizeof(CouplingEpi)) < 512 ? (int)(sizeof(NtParams) + sizeof(NtCplEpi) + sizeof(CouplingEpi)) : 512>();
+  kernarg_prefetch<(int)(sizeof(NtParams) + sizeof(NtCplEpi) + sizeof(CouplingEpi)) < 512 ? (int)(sizeof(NtParams) + sizeof(NtCplEpi) + sizeof(CouplingEpi)) : 512>();
   typedef bf16_t T;
   typedef typename ET<T>::frag frag_t;
   typedef typename Pack4<T>::type pack_t;
@@ -3798,7 +3688,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int i = 0; i < MREP; ++i)
 #pragma unroll
-          for (int j = 0; j < NREP; ++j) GEMM_MMA(fa[hs][i], fb[hs][j], acc[i][j]);
+          for (int j = 0; j < NREP; ++j) mma64(fa[hs][i], fb[hs][j], acc[i][j]);
     }
   }
   // (filter rounds 1 and 2 are in flight: no wait here)
@@ -3902,7 +3792,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int i = 0; i < MREP; ++i)
 #pragma unroll
-          for (int j = 0; j < CREP; ++j) GEMM_MMA(fa[hs][i], fb[hs][j], acc2[i][j]);
+          for (int j = 0; j < CREP; ++j) mma64(fa[hs][i], fb[hs][j], acc2[i][j]);
       // (issue order as in conv3x3_s8_body: the first half-step's fragments, then the second half-step's reads between the MFMAs of the first)
       constexpr int NF = MREP + CREP, NM = MREP * CREP, PER = NM / NF;
       __builtin_amdgcn_sched_group_barrier(0x100, NF, 0);
@@ -3936,7 +3826,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // (its upper 64 columns stay zero) and TWO A images (k0 .. k0 + 127, k0 + 128 .. k0 + 255); the eight waves own 64 x 32 each, side by side in k.
 template <int NSTAGE, int RM, bool NARROW = false, bool ADAM = false>
 __global__ __launch_bounds__(512) void igemm_tn_glds_kernel(const TnParams pin) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(TnParams)>();
+  kernarg_prefetch<(int)sizeof(TnParams)>();
   typedef bf16_t T;
   TnParams p = pin;
   if (pin.batch) {                       // batched launch: blockIdx.z selects operands and the 2-D tap geometry
@@ -4115,15 +4005,10 @@ __global__ __launch_bounds__(512) void igemm_tn_glds_kernel(const TnParams pin) 
 #pragma unroll
     for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   auto mma_frags = [&](frag_t (&f)[6]) {
-#if IPOKE_TN_ABL == 1
-#pragma unroll
-    for (int q = 0; q < 6; ++q) asm volatile("" :: "v"(f[q]));
-#else
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 2; ++j) mma64(f[i], f[4 + j], acc[i][j]);
-#endif
   };
 
   // reads of the next step's fragments (into fn) interleaved with the MFMAs of this step's (fc): three reads behind every second
@@ -4134,11 +4019,7 @@ __global__ __launch_bounds__(512) void igemm_tn_glds_kernel(const TnParams pin) 
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const int i = q >> 1, j = q & 1;
-#if IPOKE_TN_ABL == 1
-      asm volatile("" :: "v"(fc[i]), "v"(fc[4 + j]));
-#else
       mma64(fc[i], fc[4 + j], acc[i][j]);
-#endif
       if (q < 6) {                                   // fragment q of the next step: two transposing reads
         const unsigned a = (q < 4 ? y_rd[q & 3] : x_rd[q & 1]) + sb;
         const tn_tr4_t lo = tn_ds_tr<KS * 32 * 256>(a), hi = tn_ds_tr<KS * 32 * 256 + 4 * 256>(a);
@@ -4158,44 +4039,25 @@ __global__ __launch_bounds__(512) void igemm_tn_glds_kernel(const TnParams pin) 
   wait_vmcnt<(NSTAGE - 1) * L>();                 // this wave's share of stage 0 has landed
   __builtin_amdgcn_s_barrier();                   // ... and everybody else's
   frag_t FA[6], FB[6];
-#if IPOKE_TN_ABL != 2
   read_frags(FA, 0u, K0{});
-#endif
   int slot = 0;
   for (int it = 0; it < nst; ++it) {
     const unsigned sb = (unsigned)(slot * STAGE);
     const int nslot = slot + 1 == NSTAGE ? 0 : slot + 1;
-#if IPOKE_TN_ABL != 2
     tn_wait_frags(FA);
     __builtin_amdgcn_sched_barrier(0);
     read_mma(FB, sb, K1{}, FA);
-#endif
     wait_vmcnt<(NSTAGE - 2) * L>();               // this wave's share of stage it + 1 has landed
-#if IPOKE_TN_ABL != 2
     tn_wait_frags(FB);                            // ... and its reads of stage it are complete: the slot may be refilled
-#endif
     __builtin_amdgcn_s_barrier();
-#if IPOKE_TN_ABL != 3
     issue(slot, mb_begin + issued, issued < nst);
-#endif
     ++issued;
-#if IPOKE_TN_ABL != 2
     __builtin_amdgcn_sched_barrier(0);
     read_mma(FA, (unsigned)(nslot * STAGE), K0{}, FB);      // (past the last stage: a padding slot, never multiplied)
-#endif
     slot = nslot;
   }
-#if IPOKE_TN_ABL != 2
   tn_wait_frags(FA);
-#endif
   wait_vmcnt<0>();
-#if IPOKE_TN_ABL == 4
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) asm volatile("" :: "v"(acc[i][j]));
-  return;
-#endif
 
   // epilogue: acc[i][j][r] = dW[n = n0 + wn2*64 + 16i + (lane&15)][k = k0 + wk*32 + 16j + 4*(lane>>4) + r]
   if constexpr (ADAM) {
@@ -4294,7 +4156,7 @@ struct Lat8Params {
 
 template <int NSTAGE>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void wgrad3x3_lat8_kernel(const Lat8Params p) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(Lat8Params)>();
+  kernarg_prefetch<(int)sizeof(Lat8Params)>();
   typedef bf16_t T;
   typedef ET<T>::frag frag_t;
   typedef __attribute__((address_space(3))) void lds_void;
@@ -4481,7 +4343,7 @@ struct HaloWgParams {
 };
 
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void wgrad3x3_halo_kernel(const HaloWgParams p) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(HaloWgParams)>();
+  kernarg_prefetch<(int)sizeof(HaloWgParams)>();
   typedef bf16_t T;
   typedef ET<T>::frag frag_t;
   typedef __attribute__((address_space(3))) void lds_void;
@@ -4813,10 +4675,6 @@ static int launch_tn(TnParams& p, hipStream_t s, int nbatch = 1) {
 
 using namespace ipoke;
 
-#ifdef IPOKE_GEMM_STAMPS
-extern "C" void ipoke_gemm_set_stamps(long long* base) { g_gemm_stamps = base; }
-#endif
-
 /* Test hook: moves a kernel-dispatch switch at run time ("c64" / "halo16": 0 off, 1 default rule, 2 wherever the kernel can run;
  * "nn128" / "nt128": 2 = the K-major / N-major GEMM on its 128 x 128 tile at any M; value < 0 goes back to the default rule 1;
  * "cpl_split": 4 / 8 / 16 / 32 K slices for ipoke_conv3x3_coupling where tiles x slices <= 256 and slices <= Kc / 64, < 0 the default rule). */
@@ -4901,10 +4759,6 @@ extern "C" int ipoke_conv_forward(const ipoke_conv_desc* d, int dtype, void* str
   // s_setprio(2) in the chain's GEMMs: their waves win the issue arbitration against the co-resident weight-gradient /
   // optimizer waves of the side streams (64.6 -> 63.3 ms per step; levels 1 / 2 / 3 measure the same)
   p.prio = 2;
-#ifdef IPOKE_GEMM_STAMPS
-  p.stamps = g_gemm_stamps;
-  if (g_gemm_stamps) g_gemm_stamps += 4 * 4096;                // one slab of 4096 workgroups per launch
-#endif
   const bool square = p.g.taps == 1 && d->Nout == p.Ktot && d->Nout >= 1024 && p.splitk == 1;
   TimedScope ts(square ? (d->w_kmajor ? IPOKE_TAG_NN_SQUARE : IPOKE_TAG_NT_SQUARE) : IPOKE_TAG_CONV_BASE, s);
   p.w_kmajor = d->w_kmajor;
@@ -5132,9 +4986,6 @@ static int fill_tn(TnParams& p, const ipoke_wgrad_desc* d, int dtype, bool batch
 }
 
 extern "C" int ipoke_conv_wgrad(const ipoke_wgrad_desc* d, int dtype, void* stream) {
-#ifdef IPOKE_PROBE_NO_WGRAD
-  return IPOKE_OK;
-#endif
   TnParams p;
   int rc = fill_tn(p, d, dtype, false); if (rc) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -5182,9 +5033,6 @@ extern "C" int ipoke_wgrad_batch_entry_size(void) { return (int)sizeof(TnBatchEn
  * from the entry) in one launch.  entries_dev[i] = {a_off bytes, y_off bytes, w_off floats, kh, kw, ph, pw}. */
 extern "C" int ipoke_conv_wgrad_batched(const ipoke_wgrad_desc* d, const void* entries_dev, int nbatch, const void* a_base,
                                         const void* y_base, float* w_base, int dtype, void* stream) {
-#ifdef IPOKE_PROBE_NO_WGRAD
-  return IPOKE_OK;
-#endif
   IPK_REQUIRE(entries_dev && nbatch >= 1 && a_base && y_base && w_base, "bad batch arguments");
   TnParams p;
   int rc = fill_tn(p, d, dtype, true); if (rc) return rc;

@@ -561,8 +561,7 @@ static int fill_params(McfParams& P, const ipoke_mcf_desc* d, int dtype) {
 
 // the register-resident weight path covers the shipped widths (C <= 64, 4C + Cc <= 384) in bf16
 static bool fast_ok(const McfParams& P) {
-  static const bool off = getenv("IPOKE_MCF_NOFAST") != nullptr;
-  return !off && P.Cp <= kW1Steps * 32 && P.K2p <= kW2Steps * 32 && P.Hq <= 8 * 32 && P.K3p <= 4 * 32;
+  return P.Cp <= kW1Steps * 32 && P.K2p <= kW2Steps * 32 && P.Hq <= 8 * 32 && P.K3p <= 4 * 32;
 }
 
 }  // namespace ipoke

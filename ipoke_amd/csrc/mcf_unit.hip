@@ -90,7 +90,6 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_kernel(const UnitP
   unit_kernarg_prefetch();
   const int b = blockIdx.x, tid = threadIdx.x;
   McfW<T> wr;
-  UNIT_STAMP(0);
   const int C = U.C, N2 = 2 * C, ld = U.ld;
   constexpr int K2c = UC<WIDE>::N2S * 32;                          // tile width of the class (zero beyond K2p)
   const int xs_pitch = U.Cp * (int)sizeof(T) + kTilePad;
@@ -170,7 +169,6 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_kernel(const UnitP
     }
   }
   __syncthreads();
-  UNIT_STAMP(1);
 #pragma unroll 1
   for (int k = 0; k < 4; ++k) {
     const UnitLayer& Lk = U.L[k];
@@ -184,10 +182,8 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_kernel(const UnitP
     unit_gemm1<T, WIDE>(xs, xs_pitch, g, a2, a2_pitch, U.H, wr, 0, lane, wave);
     unit_gemm1<T, WIDE>(xs, xs_pitch, g, a2, a2_pitch, U.H, wr, 1, lane, wave);
     __builtin_amdgcn_sched_barrier(0);
-    UNIT_STAMP(2 + 6 * k);
     if (k < 3) unit_load_w1<T, WIDE>(wr, U.L[k + 1].W1, U);      // next layer's shifted-conv weights: their registers are free
     __syncthreads();
-    UNIT_STAMP(3 + 6 * k);
     if (Lk.a2_save) {
       constexpr int E16 = ET<T>::E16;
       const int chunks = U.K2p / E16;
@@ -197,11 +193,8 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_kernel(const UnitP
         *reinterpret_cast<u32x4*>(dst + (long)row * U.K2p + ch * E16) = *reinterpret_cast<const u32x4*>(a2 + row * a2_pitch + ch * 16);
       }
     }
-    UNIT_STAMP(4 + 6 * k);
     unit_gemm2<T, WIDE>(a2, a2_pitch, prm, N2, prm_ld, wr, lane, wave);
-    UNIT_STAMP(5 + 6 * k);
     __syncthreads();
-    UNIT_STAMP(6 + 6 * k);
     // affine coupling (+ ActNorm): y = (tanh(s/2) + 1) x + mu ; the fp32 state and its operand copy are updated in place
     float ld_acc = 0.f;
     const float* bk = bias_s + k * N2;
@@ -246,7 +239,6 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_kernel(const UnitP
       }
     }
     const float tot = block_sum(ld_acc, red);       // two barriers: the state update above is complete behind them
-    UNIT_STAMP(7 + 6 * k);
     if (tid == 0 && Lk.ld_slot) Lk.ld_slot[(long)b * U.slot_w] = tot;
     if (Lk.zc) {
       // conditioning operand of the coupling behind the unit: the selected columns of the (rounded) state tile in LDS, two per
@@ -326,7 +318,6 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_bwd_kernel(const UnitP
       for (int st = 0; st < HS; ++st)
         w1t[t][st] = buf_frag<T>(rs, vo_w1t, st < hs ? (t * hs + st) * 1024 : kOob);
   };
-  UNIT_STAMP(0);
 
   constexpr int dp_pitch = N3S * 32 * (int)sizeof(T) + kTilePad;        // class widths: columns beyond K3p / Hq stay zero
   constexpr int dc_pitch = HS * 32 * (int)sizeof(T) + kTilePad;
@@ -377,7 +368,6 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_bwd_kernel(const UnitP
     asm volatile("" : "+v"(tl));
     const int lane = tl & 63, wave = tl >> 6, r = lane & 15, gq = lane >> 4, nfrag = wave & 3, kh = wave >> 2;
     const int c2 = (tl % G2) * 2, r0 = tl / G2;
-    UNIT_STAMP(1 + 6 * (3 - k));
     // (a) thread (r0, c2) owns the channel pair c2 of rows r0, r0 + rows_par, ... (at most 4)
     if (r0 < rows_used) {
       f32x2 xv[4], scv[4], ypv[4];
@@ -456,9 +446,7 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_bwd_kernel(const UnitP
         }
       }
     }
-    UNIT_STAMP(2 + 6 * (3 - k));
     __syncthreads();
-    UNIT_STAMP(3 + 6 * (3 - k));
     {   // column sums of the per-thread partials: Q threads per column, then one thread per column
       const int Q = kMcfThreads / N2;                            // >= 4
       const int col = tid % N2, part = tid / N2;
@@ -522,9 +510,7 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_bwd_kernel(const UnitP
         dcs[(row0 + p) * U.Hq + c] = (T)0.f;
       }
     }
-    UNIT_STAMP(4 + 6 * (3 - k));
     __syncthreads();
-    UNIT_STAMP(5 + 6 * (3 - k));
     if (tid < N2 && Lk.dbias_part) {
       const int Q = kMcfThreads / N2;
       float t = 0.f;
@@ -576,12 +562,9 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_bwd_kernel(const UnitP
       };
       pass_c(std::integral_constant<int, 0>(), acc_lo);
       __builtin_amdgcn_sched_barrier(0);
-      UNIT_STAMP(32 + 4 * (3 - k));
       pass_c(std::integral_constant<int, 1>(), acc_hi);
       __builtin_amdgcn_sched_barrier(0);
-      UNIT_STAMP(33 + 4 * (3 - k));
       if (k > 0) load_w1t(U.L[k - 1]);
-      UNIT_STAMP(34 + 4 * (3 - k));
       // the two tap halves meet in LDS: 16-byte accesses, a lane's 4 channels are contiguous (columns >= C are padding)
       if (kh == 1 && n < C) {
 #pragma unroll
@@ -609,8 +592,6 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_bwd_kernel(const UnitP
         }
       }
       __syncthreads();
-      UNIT_STAMP(35 + 4 * (3 - k));
-      UNIT_STAMP(6 + 6 * (3 - k));
       if (k > 0) {   // `part` aliased the dparams tile: restore the zero K padding phase (a) does not rewrite
         const int padc = N3S * 32 - N2;
         for (int e = tid; e < 64 * padc; e += kMcfThreads) {
@@ -714,7 +695,6 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_inv_kernel(const UnitP
     if (e < rows * G2) *reinterpret_cast<f32x2*>(yf + p * C + c) = yin[i];
   }
   __syncthreads();
-  UNIT_STAMP(0);
 #pragma unroll 1
   for (int k = 3; k >= 0; --k) {
     const UnitLayer& Lk = U.L[k];
@@ -763,8 +743,6 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_inv_kernel(const UnitP
       constexpr bool LAST = decltype(last_tag)::value;
       const int si = backwards ? 7 - step : step;
       unsigned char* a2b = a2 + (step & 1) * 16 * a2_pitch;
-      UNIT_STAMP(1 + 6 * step + 0 + (k == 3 ? 0 : 1000));
-      UNIT_STAMP(1 + 6 * step + 1 + (k == 3 ? 0 : 1000));
       {   // hidden = ELU(shifted conv of the strips reconstructed so far)
         const int sidx = r >> 3, j = r & 7;
         const int pos = rows_first ? si * 8 + j : j * 8 + si;
@@ -804,9 +782,7 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_inv_kernel(const UnitP
         }
       }
       __builtin_amdgcn_sched_barrier(0);
-      UNIT_STAMP(1 + 6 * step + 2 + (k == 3 ? 0 : 1000));
       __syncthreads();
-      UNIT_STAMP(1 + 6 * step + 3 + (k == 3 ? 0 : 1000));
       {   // raw (mu, s) of the 16 rows, two channels per lane, and x = (y - mu) / (scale + 1e-12) (macow_utils.py:61-66) straight from
           // the accumulator; the strip joins the operand tile
         const int c = 8 * wave + 2 * gq;                       // this lane: row r, channels c, c + 1
@@ -828,8 +804,6 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_inv_kernel(const UnitP
           }
         }
         __builtin_amdgcn_sched_barrier(0);
-        UNIT_STAMP(1 + 6 * step + 4 + (k == 3 ? 0 : 1000));
-        UNIT_STAMP(1 + 6 * step + 5 + (k == 3 ? 0 : 1000));
         if (live) {
           f32x2 xv;
           xv[0] = __fdividef(yv[0] - (acc[0] + bm[0]), fast_scale(acc[1] + bs[0]) + 1e-12f);
@@ -845,7 +819,6 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_inv_kernel(const UnitP
 #pragma unroll 1
     for (int step = 0; step < 7; ++step) strip(step, std::false_type{});
     strip(7, std::true_type{});
-    UNIT_STAMP(49 + (3 - k));
   }
   for (int e = tid; e < rows * G2; e += kMcfThreads) {
     const int p = e / G2, c = (e - p * G2) * 2;
@@ -897,10 +870,6 @@ static int unit_params(UnitParams& U, const ipoke_mcf_desc* d, int dtype, bool b
 
 using namespace ipoke;
 
-#ifdef IPOKE_UNIT_STAMPS
-static unsigned long long* g_stamps = nullptr;
-extern "C" void ipoke_macow_unit_set_stamps(void* p) { g_stamps = reinterpret_cast<unsigned long long*>(p); }
-#endif
 
 extern "C" int ipoke_macow_unit_supported(int C, int Cc, int dtype) {
   return dtype == IPOKE_BF16 && C >= 2 && C <= 64 && C % 2 == 0 && Cc % 8 == 0 && Cc <= 128 && 4 * C + Cc <= kW2Steps * 32;
@@ -915,9 +884,6 @@ extern "C" int ipoke_macow_unit_fwd(const ipoke_mcf_desc* d4, int dtype, void* s
   UnitParams U;
   int rc = unit_params(U, d4, dtype, false); if (rc) return rc;
   IPK_REQUIRE(U.x && U.L[3].y, "null input / output state");
-#ifdef IPOKE_UNIT_STAMPS
-  U.stamps = g_stamps;
-#endif
   const bool wide = U.Cp > 32;
   const size_t lds = (size_t)65 * (U.Cp * 2 + kTilePad) + (size_t)64 * ((wide ? 384 : 256) * 2 + kTilePad) + (size_t)64 * (2 * U.C + 4) * 4 +
                      (size_t)64 * U.C * 4 + (size_t)(8 * U.C + 8 * U.C + 8) * 4;
@@ -952,9 +918,6 @@ extern "C" int ipoke_macow_unit_bwd(const ipoke_mcf_desc* d4, int dtype, void* s
     U.pair.x0 = q.x0; U.pair.scale = q.scale; U.pair.dparams = q.dparams; U.pair.dbias_part = q.dbias_part; U.pair.dx = q.dx;
     U.pair.Cp = q.Cp; U.pair.t_off = q.t_off; U.pair.t_stride = q.t_stride; U.pair.ldp = q.ldp; U.pair.on = 1;
   }
-#ifdef IPOKE_UNIT_STAMPS
-  U.stamps = g_stamps;
-#endif
   const bool wide = U.Cp > 32;
   const size_t dp_bytes = (size_t)64 * ((wide ? 128 : 64) * 2 + kTilePad);
   const size_t CP = unit_gb_pitch(U.C);
@@ -979,9 +942,6 @@ extern "C" int ipoke_macow_unit_inv(const ipoke_mcf_desc* d4, int dtype, void* s
   UnitParams U;
   int rc = unit_params(U, d4, dtype, false); if (rc) return rc;
   IPK_REQUIRE(U.L[3].x && U.L[0].y && U.L[3].x != U.L[0].y, "null / aliased state");
-#ifdef IPOKE_UNIT_STAMPS
-  U.stamps = g_stamps;
-#endif
   const bool wide = U.Cp > 32;
   const size_t lds = (size_t)2 * 65 * (U.Cp * 2 + kTilePad) + (size_t)2 * 16 * ((wide ? 384 : 256) * 2 + kTilePad) + (size_t)2 * 64 * U.Cc * 2 +
                      (size_t)2 * 64 * U.C * 4 + (size_t)(8 * U.C + 8 * U.C) * 4;

@@ -35,18 +35,7 @@ struct UnitParams {
   int ld, C, B, Cc, H, Cp, K1p, K2p, K3p, Hq, slot_w;
   unsigned long long* xchg; int xchg_stride;       // row-split launches (mcf_unit_split.hip): granule scratch, granules per (sample, layer, part)
   UnitPair pair;                                   // row-split backward only
-#ifdef IPOKE_UNIT_STAMPS
-  unsigned long long* stamps;       // probe build only (scripts/exp): shader-clock stamps of block 0
-#endif
 };
-#ifdef IPOKE_UNIT_STAMPS
-#define UNIT_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0 && U.stamps && (i) < 64) U.stamps[i] = __builtin_amdgcn_s_memtime(); } while (0)
-// row-split kernels: the first four workgroups stamp, 64 slots each
-#define UNIT_STAMP_S(i) do { if (blockIdx.x < 4 && threadIdx.x == 0 && U.stamps && (i) < 64) U.stamps[blockIdx.x * 64 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define UNIT_STAMP(i) do { } while (0)
-#define UNIT_STAMP_S(i) do { } while (0)
-#endif
 
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;

@@ -98,9 +98,7 @@ __device__ __forceinline__ void halo_end(const UnitParams& U, Halo<NI>& h) {
 // re-requested for the NEXT layer (buffer rs_next; soff_bias = kOob behind the last layer: zeros, no traffic) as soon as the tap's
 // matrix-core instructions have been issued -- the 36 KB per wave trickle out underneath the remaining taps instead of stalling
 // all eight waves in a burst behind the contraction.
-#ifndef IPOKE_UNIT_SPREAD
-#define IPOKE_UNIT_SPREAD 1      // 1: the next layer's weight requests in batches of 4-8 per wave between the phases of this layer (0: in
-#endif                           //    one burst inside the first contraction's last tile -- developer A/B)
+// The next layer's weight requests go out in batches of 4-8 per wave between the phases of this layer.
 // re-request the fragments of taps [LO, HI) of the shifted-conv weights / of K steps [LO, HI) of the 1x1 weights from another layer's operand
 template <typename T, bool WIDE, int LO, int HI>
 __device__ __forceinline__ void reload_w1(McfW<T>& w, rsrc_t rs, int lane, int wave, int nks, int soff_bias) {
@@ -121,20 +119,11 @@ __device__ __forceinline__ void reload_w2(McfW<T>& w, rsrc_t rs, int lane, int w
 }
 template <typename T, bool WIDE, bool RELOAD>
 __device__ __forceinline__ void split_gemm1_tile(const unsigned char* xs, int xs_pitch, const McfGeom& g, unsigned char* a2t, int a2_pitch, int H,
-                                                 McfW<T>& w, int ptile, int lane, int wave, rsrc_t rs_next, int nks, int soff_bias, rsrc_t rs_w2,
-                                                 int n2) {
+                                                 McfW<T>& w, int ptile, int lane, int wave, rsrc_t rs_next, int nks, int soff_bias) {
   constexpr int KS = K64<T>::value, E16 = ET<T>::E16, J1 = UC<WIDE>::J1, CS = UC<WIDE>::CS;
   typedef typename ET<T>::frag frag_t;
   const int r = lane & 15, gq = lane >> 4;
   const unsigned char* zrow = xs + 64 * xs_pitch;
-  if (RELOAD && !IPOKE_UNIT_SPREAD) {
-    // THIS layer's 1x1 weights (their registers are free since the previous layer's second contraction): requested here -- behind
-    // the halo sweep, so that the sweep's loads and the previous coupling's hand-off stores do not queue behind them in the CU's
-    // one vector-memory pipeline -- they land underneath this tile and the barrier behind it
-    const int voff2 = wave * n2 * 1024 + lane * 16;
-#pragma unroll
-    for (int st = 0; st < UC<WIDE>::N2S; ++st) w.w2[st][0] = buf_frag<T>(rs_w2, voff2, st < n2 ? st * 1024 : kOob);
-  }
   f32x4 acc[J1];
 #pragma unroll
   for (int j = 0; j < J1; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -150,12 +139,12 @@ __device__ __forceinline__ void split_gemm1_tile(const unsigned char* xs, int xs
 #pragma unroll
       for (int j = 0; j < J1; ++j) mma64(fa, w.w1[tap][st][j], acc[j]);
     }
-    if (RELOAD && (!IPOKE_UNIT_SPREAD || tap >= 4)) {        // spread: taps 0, 1 behind the last two taps; the rest between the later phases
+    if (RELOAD && tap >= 4) {        // taps 0, 1 behind the last two taps; the rest between the later phases
 #pragma unroll
       for (int st = 0; st < CS; ++st)
 #pragma unroll
         for (int j = 0; j < J1; ++j) {
-          const int rt = IPOKE_UNIT_SPREAD ? tap - 4 : tap;
+          const int rt = tap - 4;
           w.w1[rt][st][j] = buf_frag<T>(rs_next, voff[j], (rt * CS + st) * 1024 + soff_bias);
         }
     }
@@ -205,7 +194,6 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_split_kernel(const
   const int b = blockIdx.x / S, s = blockIdx.x - b * S, tid = threadIdx.x;
   const int y0 = s * RY, p0 = y0 * 8;
   McfW<T> wr;
-  UNIT_STAMP_S(0);
   const int C = U.C, N2 = 2 * C, ld = U.ld;
   constexpr int K2c = UC<WIDE>::N2S * 32;
   const int xs_pitch = U.Cp * (int)sizeof(T) + kTilePad;
@@ -256,7 +244,7 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_split_kernel(const
     }
   }
   unit_load_w1<T, WIDE>(wr, U.L[0].W1, U);
-  if (IPOKE_UNIT_SPREAD) unit_load_w2<T, WIDE>(wr, U.L[0].W2, U);
+  unit_load_w2<T, WIDE>(wr, U.L[0].W2, U);
   for (int i = tid; i < (65 * xs_pitch + R * a2_pitch) / 16; i += kMcfThreads) reinterpret_cast<u32x4*>(smem)[i] = u32x4{0u, 0u, 0u, 0u};
   if (U.L[3].y && ld > C) {
     const int R2 = (ld - C) >> 1;
@@ -289,7 +277,6 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_split_kernel(const
     }
   }
   __syncthreads();
-  UNIT_STAMP_S(1);
   float ld_k[4] = {0.f, 0.f, 0.f, 0.f};        // per-thread log-det partials of the four layers, summed over the workgroup at the end
 #pragma unroll 1
   for (int k = 0; k < 4; ++k) {
@@ -311,41 +298,35 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_split_kernel(const
       const int t0 = wait ? 1 - t_dep : 0;
       Halo<1> hl;
       if (wait) halo_begin<S, 1>(hl, xg_region(U, b, k, S, s), s, nu, nd, G2, 32, xs, xs_pitch, tl);
-      split_gemm1_tile<T, WIDE, false>(xs, xs_pitch, g, a2 + t0 * 16 * a2_pitch, a2_pitch, U.H, wr, p0 + t0 * 16, lane, wave, rs1n, nks, soff_bias, rs2, n2);
+      split_gemm1_tile<T, WIDE, false>(xs, xs_pitch, g, a2 + t0 * 16 * a2_pitch, a2_pitch, U.H, wr, p0 + t0 * 16, lane, wave, rs1n, nks, soff_bias);
       __builtin_amdgcn_sched_barrier(0);
-      UNIT_STAMP_S(2 + 8 * k);
       if (wait) {
         halo_end<1>(U, hl);
         __syncthreads();
       }
       __builtin_amdgcn_sched_barrier(0);
-      UNIT_STAMP_S(3 + 8 * k);
-      if (IPOKE_UNIT_SPREAD && k > 0) reload_w2<T, WIDE, 8, 12>(wr, rs2, lane, wave, n2, 0);
+      if (k > 0) reload_w2<T, WIDE, 8, 12>(wr, rs2, lane, wave, n2, 0);
       split_gemm1_tile<T, WIDE, true>(xs, xs_pitch, g, a2 + (1 - t0) * 16 * a2_pitch, a2_pitch, U.H, wr, p0 + (1 - t0) * 16, lane, wave, rs1n, nks,
-                                      soff_bias, rs2, n2);
+                                      soff_bias);
     } else if constexpr (MT == 1) {
-      UNIT_STAMP_S(2 + 8 * k);
       if (nu + nd > 0) {
         Halo<1> hl;
         halo_begin<S, 1>(hl, xg_region(U, b, k, S, s), s, nu, nd, G2, 32, xs, xs_pitch, tl);
         halo_end<1>(U, hl);
         __syncthreads();
       }
-      UNIT_STAMP_S(3 + 8 * k);
-      if (IPOKE_UNIT_SPREAD && k > 0) reload_w2<T, WIDE, 8, 12>(wr, rs2, lane, wave, n2, 0);
-      split_gemm1_tile<T, WIDE, true>(xs, xs_pitch, g, a2, a2_pitch, U.H, wr, p0, lane, wave, rs1n, nks, soff_bias, rs2, n2);
+      if (k > 0) reload_w2<T, WIDE, 8, 12>(wr, rs2, lane, wave, n2, 0);
+      split_gemm1_tile<T, WIDE, true>(xs, xs_pitch, g, a2, a2_pitch, U.H, wr, p0, lane, wave, rs1n, nks, soff_bias);
     } else {
 #pragma unroll
       for (int t = 0; t < MT - 1; ++t)
-        split_gemm1_tile<T, WIDE, false>(xs, xs_pitch, g, a2 + t * 16 * a2_pitch, a2_pitch, U.H, wr, p0 + t * 16, lane, wave, rs1n, nks, soff_bias, rs2, n2);
+        split_gemm1_tile<T, WIDE, false>(xs, xs_pitch, g, a2 + t * 16 * a2_pitch, a2_pitch, U.H, wr, p0 + t * 16, lane, wave, rs1n, nks, soff_bias);
       split_gemm1_tile<T, WIDE, true>(xs, xs_pitch, g, a2 + (MT - 1) * 16 * a2_pitch, a2_pitch, U.H, wr, p0 + (MT - 1) * 16, lane, wave, rs1n, nks,
-                                      soff_bias, rs2, n2);
+                                      soff_bias);
     }
     __builtin_amdgcn_sched_barrier(0);
-    UNIT_STAMP_S(4 + 8 * k);
     __syncthreads();
-    UNIT_STAMP_S(5 + 8 * k);
-    if (IPOKE_UNIT_SPREAD) reload_w1<T, WIDE, 2, 3>(wr, rs1n, lane, wave, nks, soff_bias);
+    reload_w1<T, WIDE, 2, 3>(wr, rs1n, lane, wave, nks, soff_bias);
     if (Lk.a2_save) {
       constexpr int E16 = ET<T>::E16;
       const int chunks = U.K2p / E16;
@@ -356,14 +337,11 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_split_kernel(const
         *reinterpret_cast<u32x4*>(dst + (long)row * U.K2p + ch * E16) = *reinterpret_cast<const u32x4*>(a2 + row * a2_pitch + ch * 16);
       }
     }
-    UNIT_STAMP_S(6 + 8 * k);
-    if (IPOKE_UNIT_SPREAD) reload_w1<T, WIDE, 3, 4>(wr, rs1n, lane, wave, nks, soff_bias);
+    reload_w1<T, WIDE, 3, 4>(wr, rs1n, lane, wave, nks, soff_bias);
     split_gemm2<T, WIDE, MT>(a2, a2_pitch, prm, N2, prm_ld, wr, lane, wave);
     __builtin_amdgcn_sched_barrier(0);
-    if (IPOKE_UNIT_SPREAD) reload_w1<T, WIDE, 4, 5>(wr, rs1n, lane, wave, nks, soff_bias);
-    UNIT_STAMP_S(7 + 8 * k);
+    reload_w1<T, WIDE, 4, 5>(wr, rs1n, lane, wave, nks, soff_bias);
     __syncthreads();
-    UNIT_STAMP_S(8 + 8 * k);
     // affine coupling (+ ActNorm) on the own rows; rows a neighbour needs for the next layer leave as granules from here
     float ld_acc = 0.f;
     const float* bk = bias_s + k * N2;
@@ -417,13 +395,10 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_split_kernel(const
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) ld_k[q] += q == k ? ld_acc : 0.f;
-    if (IPOKE_UNIT_SPREAD) {                      // (behind the coupling's stores and hand-off granules)
-      reload_w1<T, WIDE, 5, 6>(wr, rs1n, lane, wave, nks, soff_bias);
-      reload_w2<T, WIDE, 0, 4>(wr, rs2n, lane, wave, n2, soff_bias);
-    }
+    reload_w1<T, WIDE, 5, 6>(wr, rs1n, lane, wave, nks, soff_bias);                      // (behind the coupling's stores and hand-off granules)
+    reload_w2<T, WIDE, 0, 4>(wr, rs2n, lane, wave, n2, soff_bias);
     __syncthreads();                              // the state update above is complete
-    UNIT_STAMP_S(9 + 8 * k);
-    if (IPOKE_UNIT_SPREAD) reload_w2<T, WIDE, 4, 8>(wr, rs2n, lane, wave, n2, soff_bias);
+    reload_w2<T, WIDE, 4, 8>(wr, rs2n, lane, wave, n2, soff_bias);
     if (Lk.zc) {
       const int half = Lk.zc_ld >> 1;
       T* zb = reinterpret_cast<T*>(Lk.zc) + (row0 + p0) * Lk.zc_ld;
@@ -544,7 +519,6 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_bwd_split_kernel(const
       for (int st = 0; st < HS; ++st)
         w1t[t][st] = buf_frag<T>(rs, vo_w1t, st < hs ? (t * hs + st) * 1024 : kOob);
   };
-  UNIT_STAMP_S(0);
 
   constexpr int dp_pitch = N3S * 32 * (int)sizeof(T) + kTilePad;
   constexpr int dc_pitch = HS * 32 * (int)sizeof(T) + kTilePad;
@@ -584,7 +558,6 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_bwd_split_kernel(const
   const int rows_used = rows_par < R ? rows_par : R;
   const rsrc_t rs_x = make_rsrc(U.xchg, 0x7ffffff0);              // granule stores (16 bytes = two granules, write-through)
   __syncthreads();
-  UNIT_STAMP_S(1);
 #pragma unroll 1
   for (int k = 3; k >= 0; --k) {
     const UnitLayer& Lk = U.L[k];
@@ -673,7 +646,6 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_bwd_split_kernel(const
         }
       }
     }
-    UNIT_STAMP_S(2 + 8 * (3 - k));
     __syncthreads();
     {   // column sums of the per-thread partials
       const int Q = kMcfThreads / N2;
@@ -738,9 +710,7 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_bwd_split_kernel(const
         dcs[(rowp + p) * U.Hq + c] = (T)0.f;
       }
     }
-    UNIT_STAMP_S(3 + 8 * (3 - k));
     __syncthreads();
-    UNIT_STAMP_S(4 + 8 * (3 - k));
     if (tid < N2 && Lk.dbias_part) {
       const int Q = kMcfThreads / N2;
       float t = 0.f;
@@ -779,26 +749,21 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_bwd_split_kernel(const
       Halo<4> hl;
       if (wait) halo_begin<S, 4>(hl, xg_region(U, b, k, S, s), s, nu, nd, H >> 1, 128, dc, dc_pitch, tl);
       // the next layer's (b) operands are requested BEHIND the halo sweep: the CU's vector-memory pipeline is a FIFO, and in the train
-      // step (in-situ stamps, scripts/exp/insitu_unit_stamps.py) the sweep's loads queued behind these 72 KB
+      // step (in-situ clock stamps) the sweep's loads queued behind these 72 KB
       if constexpr (MT == 2) {
         const int t_dep = s == 0 ? 1 : 0, t0 = wait ? 1 - t_dep : 0;
         if (t0 == 0) pass_c(0, acc_c[0]); else pass_c(1, acc_c[1]);
         __builtin_amdgcn_sched_barrier(0);
-        UNIT_STAMP_S(5 + 8 * (3 - k));
         if (wait) { halo_end<4>(U, hl); __syncthreads(); }
-        UNIT_STAMP_S(6 + 8 * (3 - k));
         if (k > 0) { load_w2t(U.L[k - 1]); load_cact(U.L[k - 1]); }
         if (t0 == 0) pass_c(1, acc_c[1]); else pass_c(0, acc_c[0]);
       } else {
-        UNIT_STAMP_S(5 + 8 * (3 - k));
         if (wait) { halo_end<4>(U, hl); __syncthreads(); }
-        UNIT_STAMP_S(6 + 8 * (3 - k));
         if (k > 0) { load_w2t(U.L[k - 1]); load_cact(U.L[k - 1]); }
 #pragma unroll
         for (int t = 0; t < MT; ++t) pass_c(t, acc_c[t]);
       }
       __builtin_amdgcn_sched_barrier(0);
-      UNIT_STAMP_S(7 + 8 * (3 - k));
       if (k > 0) load_w1t(U.L[k - 1]);
       if (kh == 1 && n < C) {
 #pragma unroll
@@ -826,7 +791,6 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_bwd_split_kernel(const
         }
       }
       __syncthreads();
-      UNIT_STAMP_S(8 + 8 * (3 - k));
       if (k > 0) {   // `part` aliased the dparams tile: restore the zero K padding phase (a) does not rewrite
         const int padc = N3S * 32 - N2;
         for (int e = tid; e < R * padc; e += kMcfThreads) {

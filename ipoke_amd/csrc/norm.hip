@@ -166,7 +166,7 @@ struct NormApply {
 // tensor less.  Chunk = this pass's block of positions; one pass of 256 threads over the channels (C <= 256 * E16).
 template <typename T, bool NEXT>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const NormApply a) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(NormApply)>();
+  kernarg_prefetch<(int)sizeof(NormApply)>();
   constexpr int E16 = ET<T>::E16;
   typedef typename ET<T>::frag frag_t;
   __shared__ float sscale[NEXT ? 2048 : 4096], sshift[NEXT ? 2048 : 4096];
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const NormApply a) {
 // deviations) is taken from there.  grid (C / CS, N), dynamic LDS = S * CS * sizeof(T).
 template <typename T>
 __global__ __launch_bounds__(256) void gn_fused_kernel(const NormApply a, int CS, float eps) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(NormApply)>();
+  kernarg_prefetch<(int)sizeof(NormApply)>();
   constexpr int E16 = ET<T>::E16;
   typedef typename ET<T>::frag frag_t;
   extern __shared__ __attribute__((aligned(16))) unsigned char gsm[];
@@ -573,8 +573,7 @@ extern "C" int ipoke_groupnorm(const ipoke_norm_desc* d, int dtype, void* stream
   hipStream_t s = STREAM(stream);
   {
     // small maps: one launch per norm (gn_fused_kernel).  Slab = the smallest run of whole groups that is a multiple of 16 bytes
-    // and at least 32 channels wide (64-byte rows), as long as the S x CS tile fits in LDS.  IPOKE_GN_FUSED=0: developer A/B.
-    static const bool fused_on = !(getenv("IPOKE_GN_FUSED") && atoi(getenv("IPOKE_GN_FUSED")) == 0);
+    // and at least 32 channels wide (64-byte rows), as long as the S x CS tile fits in LDS.
     const int cpg = d->C / d->G, esz = dtype == IPOKE_BF16 ? 2 : 4;
     int unit = cpg; while (unit % e16) unit += cpg;                    // lcm(cpg, e16)
     // Round 6: a LARGE tensor (>= 32 MB: the decoder's InstanceNorms over all frames of a batch) only takes this path with whole 128-byte
@@ -587,7 +586,7 @@ extern "C" int ipoke_groupnorm(const ipoke_norm_desc* d, int dtype, void* stream
     while (d->C % CS) CS += unit;
     const size_t tile = (size_t)d->S * CS * esz;
     const bool shape_ok = large ? (CS * esz >= 128 && tile <= 32 * 1024) : tile <= 128 * 1024;
-    if (fused_on && !d->y_f32 && !d->mod_gamma && CS <= 2048 && CS / e16 <= 256 && shape_ok && d->ldy % e16 == 0 &&
+    if (!d->y_f32 && !d->mod_gamma && CS <= 2048 && CS / e16 <= 256 && shape_ok && d->ldy % e16 == 0 &&
         (!d->res || d->ld_res % e16 == 0)) {
       NormApply a;
       a.x = d->x; a.ldx = d->ldx; a.y = d->y; a.ldy = d->ldy; a.y_f32 = 0; a.N = d->N; a.S = d->S; a.C = d->C; a.G = d->G;

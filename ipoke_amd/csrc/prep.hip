@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256) void relayout_kernel(const float* __restrict__
                                                        const float* __restrict__ wn_scale, const RelayoutJob* __restrict__ jobs,
                                                        int njobs, const int* __restrict__ block_job, int block_base, int nblocks) {
   __shared__ __attribute__((aligned(16))) float tile[32 * 33 * 9];   // [n_l][tap][k_l], k pitch TE+1 (>= 64*65)
-  // Grid-stride over the tiles [block_base, block_base + nblocks) so that the grid can be capped (IPOKE_RELAYOUT_BLOCKS).  Measured,
+  // Grid-stride over the tiles [block_base, block_base + nblocks) so that a huge job table fits one launch (ipoke_relayout_multi_range).  Measured with a capped grid,
   // round 3: the refresh of a slice is the worst neighbour a chain kernel can have -- a conv2 GEMM that overlaps it takes 72-170 us
   // instead of 24, a fused MaCowUnit backward 193 instead of 59 (profiles/r03_overlap_before.txt: one workgroup per tile, four per CU
   // by LDS, keeps every CU full for the ~300 us of a slice) -- and yet capping it LOSES: 62.3 ms per step uncapped against 62.8 / 63.7 /
@@ -302,11 +302,7 @@ template <bool NT> __device__ __forceinline__ void st_stream(float* q, f32x4 v) 
   if (NT) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(q));
   else *reinterpret_cast<f32x4*>(q) = v;
 }
-#ifdef IPOKE_ADAM_TEMPORAL          // developer A/B build
-static constexpr bool kNtCast = false, kNtSeg = false;
-#else
 static constexpr bool kNtCast = true, kNtSeg = true;
-#endif
 
 template <typename T>
 __global__ __launch_bounds__(256) void adam_shadow_tile_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -550,9 +546,8 @@ extern "C" int ipoke_relayout_multi_range(const float* params, void* shadow, con
   IPK_REQUIRE(params && shadow && jobs_dev && njobs > 0 && nblocks >= 0 && block_begin >= 0, "bad arguments");
   if (nblocks == 0) return IPOKE_OK;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  // optional grid cap (developer A/B, see relayout_kernel); one workgroup per tile otherwise
-  static const int cap_env = getenv("IPOKE_RELAYOUT_BLOCKS") ? atoi(getenv("IPOKE_RELAYOUT_BLOCKS")) : 0;
-  const int cap = block_begin == 0 && nblocks > 100000 ? 65536 : (cap_env > 0 ? cap_env : nblocks);
+  // one workgroup per tile (see relayout_kernel)
+  const int cap = block_begin == 0 && nblocks > 100000 ? 65536 : nblocks;
   const int grid = nblocks < cap ? nblocks : cap;
   if (dtype == IPOKE_BF16)
     hipLaunchKernelGGL(relayout_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, params, (bf16_t*)shadow, wn_scale,

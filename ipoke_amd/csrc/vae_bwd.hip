@@ -125,7 +125,7 @@ __device__ __forceinline__ float norm_dw(const NormBwd& a, long m, int c) {
 // over rows rr, rr + rows_par, ... (16-byte loads, register partial sums, one fixed-order LDS reduction).
 template <typename T>
 __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const NormBwd a) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(NormBwd)>();
+  kernarg_prefetch<(int)sizeof(NormBwd)>();
   constexpr int E16 = ET<T>::E16;
   typedef typename ET<T>::frag frag_t;
   __shared__ float sm[2][256 * E16];
@@ -235,7 +235,7 @@ __device__ __forceinline__ void gn_bwd_affine_body(const NormBwd& a, int blk, fl
 // passes 2a and 2b as ONE launch (round 5): workgroups [0, N) sum the groups of a sample, the rest the affine gradients of 16 channels --
 // two independent reductions over the same partials that used to cost two dependent launches per norm on the chain's queue
 __global__ __launch_bounds__(256) void gn_bwd_sums_kernel(const NormBwd a, float* __restrict__ dgamma, float* __restrict__ dbeta) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(NormBwd)>();
+  kernarg_prefetch<(int)sizeof(NormBwd)>();
   __shared__ float r1[256], r2[256];
   if ((int)blockIdx.x < a.N) gn_bwd_groupsum_body(a, blockIdx.x, r1, r2);
   else gn_bwd_affine_body(a, blockIdx.x - a.N, dgamma, dbeta, r1, r2);
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256) void gn_bwd_sums_kernel(const NormBwd a, float
 // go to per-block partials (blocks of rs_pos_per_block positions; fixed-order sums in rowscale_final_kernel).
 template <typename T, bool RS>
 __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const NormBwd a) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(NormBwd)>();
+  kernarg_prefetch<(int)sizeof(NormBwd)>();
   constexpr int E16 = ET<T>::E16;
   typedef typename ET<T>::frag frag_t;
   extern __shared__ float lds[];            // [8][C]: mean, rstd, gamma, beta, S1/cnt, S2/cnt, forward scale, shift  (RS: + [256 * E16] column sums + [4])
@@ -352,7 +352,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const NormBwd a) {
 // occupancy that hides the per-frame constant reload); a block is ROWS * (256 / (C / E16)) positions.
 template <typename T>
 __global__ __launch_bounds__(256) void gn_bwd_apply_frames_kernel(const NormBwd a) {
-  if (IPK_KERNARG_PREFETCH) kernarg_prefetch<(int)sizeof(NormBwd)>();
+  kernarg_prefetch<(int)sizeof(NormBwd)>();
   constexpr int E16 = ET<T>::E16, ROWS = 16 / E16;
   typedef typename ET<T>::frag frag_t;
   extern __shared__ float lds[];            // [6][C]: mean, rstd, gamma, beta, S1/cnt, S2/cnt
@@ -548,8 +548,8 @@ extern "C" int ipoke_colsum(const void* src, int ld, int64_t M, int C, int src_f
   return IPOKE_OK;
 }
 
-// positions per workgroup of the two passes (IPOKE_NORM_BWD_POS: developer A/B)
-static const int kNormBwdPos = getenv("IPOKE_NORM_BWD_POS") ? atoi(getenv("IPOKE_NORM_BWD_POS")) : 128;
+// positions per workgroup of the two passes (c4, 32 / 64 / 128 / 256 / 512 / 1024: 39.6 / 38.1 / 37.3 - 37.7 / 37.6 / 37.85 / 39.1 ms per step)
+static constexpr int kNormBwdPos = 128;
 static const int kNormRsPos = 512;          // positions per block of the pass that folds ipoke_rowscale_bwd in (that kernel's own block size)
 extern "C" int64_t ipoke_groupnorm_bwd_rs_workspace_floats(int N, int S, int C) {
   return (int64_t)N * ((S + kNormRsPos - 1) / kNormRsPos) * (C + 1);

@@ -11,7 +11,6 @@ first-stage training (L1 + KL) lives in ``ipoke_amd.first_stage_train`` and is r
 ``SpadeCondMotionModel.training_loss``.
 """
 import math
-import os
 
 import numpy as np
 import torch
@@ -106,8 +105,9 @@ class _Conv(_Cached):
                 wr = w.detach().transpose(0, 1)                                  # [cout, cin, kh, kw]
                 ops_ = {}
                 # wide layers (>= 128 input channels, >= 96 outputs): the two-tap phases as 2 x 2 windows with a zero row / column, so
-                # that they run on the halo-staged kernel like the four-tap phase (twice the multiplications at 2.4x the rate)
-                pad2 = _PHASE_PAD and self.cin >= 128 and self.cout >= 96 and ops._dt(dtype) == _lib.BF16
+                # that they run on the halo-staged kernel like the four-tap phase (twice the multiplications at 2.4x the rate; sampling
+                # 39.67 vs 39.76 ms)
+                pad2 = self.cin >= 128 and self.cout >= 96 and ops._dt(dtype) == _lib.BF16
                 for a in (0, 1):
                     for b in (0, 1):
                         wp = wr[:, :, list(self._PHASE_TAPS[a])][:, :, :, list(self._PHASE_TAPS[b])].contiguous()
@@ -134,7 +134,7 @@ class _Conv(_Cached):
         if (_CT_PHASES and self.transposed and self.dims == 2 and x is not None and self.k == (1, 3, 3) and self.stride == (1, 2, 2)
                 and self.pad == (0, 1, 1)):
             return self._run_phases(x, dtype, act, out_f32)
-        if (_DEPTH1_SLICE and self.dims == 3 and x is not None and x.dhw[0] == 1 and self.k[0] == 3 and self.pad[0] == 1
+        if (self.dims == 3 and x is not None and x.dhw[0] == 1 and self.k[0] == 3 and self.pad[0] == 1
                 and not self.transposed and not self.snorm):
             wop, kc, b = self._mid_operand(dtype)
             y = K.conv(x, wop, kc, self.cout, (1, self.k[1], self.k[2]), (1, self.stride[1], self.stride[2]), (0, self.pad[1], self.pad[2]),
@@ -166,12 +166,8 @@ class _Norm(nn.Module):
         return K.group_norm(x, self.groups, dtype, act=act, res=res, res_post=res_post, next_groups=next_groups)
 
 
-_PHASE_PAD = os.environ.get("IPOKE_NO_PHASE_PAD", "0") != "1"        # developer A/B: two-tap phases of wide up-convolutions as they are
-_RES_POST = os.environ.get("IPOKE_NO_RES_POST", "0") != "1"         # developer A/B: ResBlock's sum as its own element-wise pass
-_NEXT_STATS = os.environ.get("IPOKE_NO_NEXT_STATS", "0") != "1"     # developer A/B: the SPADE norm makes its own statistics pass
-_STEM_FOLD = os.environ.get("IPOKE_NO_STEM_FOLD", "0") != "1"      # developer A/B: conv1 of the 3-D encoder read in place
-_CT_PHASES = os.environ.get("IPOKE_NO_CT_PHASES", "0") != "1"       # developer A/B: stride-2 ConvTranspose2d as one 9-tap launch
-_DEPTH1_SLICE = os.environ.get("IPOKE_NO_DEPTH1_SLICE", "0") != "1"  # developer A/B: 3 x 3 x 3 filters on depth-1 inputs run all 27 taps
+_STEM_FOLD = True       # test hook (tests/test_encoder_kernels_gpu.py): False = conv1 of the 3-D encoder read in place
+_CT_PHASES = True       # test hook (tests/test_encoder_kernels_gpu.py): False = stride-2 ConvTranspose2d as one 9-tap launch
 
 
 # ---------------------------------------------------------------------------------------------- 3-D encoder
@@ -431,12 +427,13 @@ class ResBlock(nn.Module):
         """``next_groups``: a norm of that many groups reads the block's output next (the decoder's SPADE norm): the pass that writes
         the output leaves its chunk statistics for it."""
         rc = self.res_conv if self.convolve_res else None
-        if (_RES_POST and rc is not None and rc.norm is not None and self.conv2.norm is None and self.conv2.activation == "none"):
+        if rc is not None and rc.norm is not None and self.conv2.norm is None and self.conv2.activation == "none":
             # out = conv2(conv1(x)) + act(norm(res_conv(x))): the sum rides on the skip path's norm pass (the residual joins behind its
-            # activation) instead of being a pass of its own over three tensors of the block's output size
+            # activation) instead of being a pass of its own over three tensors of the block's output size (sampling 40.6 vs 41.3-41.5 ms);
+            # handing the chunk statistics to the SPADE norm behind the block saves its statistics pass (40.6 vs 40.8 ms)
             y2 = self.conv2.run(self.conv1.run(x, dtype), dtype)
             act = rc.act if isinstance(rc, Conv2dTransposeBlock) else ACT[rc.activation]
-            return rc.norm.run(rc.conv.run(x, dtype), dtype, act=act, res=y2, res_post=True, next_groups=next_groups if _NEXT_STATS else None)
+            return rc.norm.run(rc.conv.run(x, dtype), dtype, act=act, res=y2, res_post=True, next_groups=next_groups)
         res = rc.run(x, dtype) if rc is not None else x
         return self.conv2.run(self.conv1.run(x, dtype), dtype, res=res)
 
@@ -592,7 +589,7 @@ class SpadeCondMotionModel(nn.Module):
         # GEMMs of a useful height (c5: 63.6 -> see DESIGN.md section 7).  Chunked so that row offsets stay below 2^31 elements.
         from . import first_stage_train as FT
         seq = None
-        if FT._GRU_NATIVE and FT.gru_native_ok(self.rnn, in_rnn, m, dt):
+        if FT.gru_native_ok(self.rnn, in_rnn, m, dt):
             # the ConvGRU steps issued natively (csrc/gru.hip): one call instead of length x n_layers cells of Python launches
             weights = []
             for c in self.rnn.cells:

@@ -25,11 +25,10 @@ conv(x, W / sigma_t) = conv(x, W) / sigma_t and sigma_t is a per-frame SCALAR, s
 and the decoder runs ONCE over the (frame, clip)-ordered batch of all frames with one operand of W_orig and 1 / sigma_t as a per-image
 scale of the GEMM epilogue (ipoke_conv_desc.row_scale); the backward pass needs one weight gradient per convolution (rows pre-scaled
 by 1 / sigma_t) plus the scalars <dY_t, Y_t> for sigma_t's own gradient (ipoke_rowscale_bwd, ipoke_spectral_bwd_frames).
-IPOKE_C4_PER_FRAME=1 keeps the frame-by-frame evaluation of rounds 2-3 (same mathematics, 15 x the decoder launches).
+``_FRAME_BATCH = False`` (a test hook) keeps the frame-by-frame evaluation (same mathematics, 15 x the decoder launches).
 """
 from ctypes import byref
 
-import os
 import weakref
 
 import contextlib
@@ -65,18 +64,15 @@ def _pad_cols(t, ld, dtype):
 
 
 _OPCACHE = {}
-_SN_AHEAD = os.environ.get("IPOKE_NO_SN_AHEAD", "0") != "1"            # developer A/B: one power iteration per decoder call, at the call
-_HOIST_SPADE = os.environ.get("IPOKE_NO_SPADE_HOIST", "0") != "1"      # developer A/B: per-frame SPADE maps as the reference computes them
-_SPADE_DENSE_INPUT = os.environ.get("IPOKE_SPADE_F32_INPUT", "0") != "1"   # developer A/B: the SPADE branch reads the resized fp32 start frame in place
-_FRAME_BATCH = os.environ.get("IPOKE_C4_PER_FRAME", "0") != "1"         # all generated frames decoded as ONE batch (module docstring); 0: frame by frame
+# test hooks (tests/test_train_mode_gpu.py runs every variant against the oracle)
+_SN_AHEAD = True        # False: one power iteration per decoder call, at the call
+_HOIST_SPADE = True     # False: per-frame SPADE maps as the reference computes them
+_FRAME_BATCH = True     # all generated frames decoded as ONE batch (module docstring); False: frame by frame (c4 94.8 vs 57.2 ms)
 
 
 def clear_operand_cache():
     """Called whenever parameters change behind autograd's back (MultiTensorAdam writes through raw pointers)."""
     _OPCACHE.clear()
-
-
-_OPERAND_REFRESH = os.environ.get("IPOKE_C4_OPERAND_REFRESH", "1") != "0"      # developer A/B: 0 = operands rebuilt lazily, one launch per weight
 
 
 def take_operand_cache():
@@ -89,7 +85,7 @@ def take_operand_cache():
 def refresh_operand_cache(snap):
     """Behind an optimizer step that wrote the parameters through raw pointers (no version bump): rebuild the cached operands of every
     live PARAMETER in place -- same tensors, same cache keys -- with ONE multi-tensor launch, instead of dropping them and rebuilding
-    each lazily at its first use (c4: 101 launches of ~8 us on the chain per step).  Entries of derived weights (scoped: the per-pass
+    each lazily at its first use (c4: 101 launches of ~8 us on the chain per step, 41.96 -> 41.43 ms).  Entries of derived weights (scoped: the per-pass
     GRU gate concatenations), of other streams and of dead or re-versioned tensors are dropped as before."""
     import ctypes as ct
     cur = torch.cuda.current_stream().cuda_stream
@@ -151,10 +147,9 @@ def _build_weight_operand(w, dtype, transposed_conv, inv_scale=None):
     return out, kc
 
 
-_WGRAD_SWAP = os.environ.get("IPOKE_WGRAD_SWAP", "1") != "0"       # developer A/B: narrow-output convolutions' weight gradient with swapped roles
-_STEM_TRAIN_UNFOLDED = os.environ.get("IPOKE_STEM_TRAIN_UNFOLDED", "0") == "1"      # developer A/B: conv1 of the 3-D encoder read in place when training
-_WGRAD_HALO_WGS = int(os.environ.get("IPOKE_WGRAD_HALO_WGS", "256"))  # workgroups the halo-staged weight gradient aims for (one per CU: 158 KB of LDS)
-_WGRAD_WGS = int(os.environ.get("IPOKE_WGRAD_WGS", "512"))       # workgroups a split-M weight gradient aims for (c4: 256 / 512 / 1024 / 2048 -> 156.5 / 151.0 / 156.5 / 160.6 ms: more slabs = more fp32 partial traffic)
+_WGRAD_SWAP = True      # test hook (tests/test_vae_bwd_units_gpu.py): False = narrow-output convolutions' weight gradient without swapped roles (c4 48.5 vs 47.7 ms)
+_WGRAD_HALO_WGS = 256   # workgroups the halo-staged weight gradient aims for (one per CU: 158 KB of LDS)
+_WGRAD_WGS = 512        # workgroups a split-M weight gradient aims for (c4: 256 / 512 / 1024 / 2048 -> 156.5 / 151.0 / 156.5 / 160.6 ms: more slabs = more fp32 partial traffic)
 
 
 class _SnWeight:
@@ -175,7 +170,6 @@ class _SnFrames:
         self.frames = int(sig.shape[0])
 
 
-_CT_PHASES = os.environ.get("IPOKE_NO_CT_PHASES", "0") != "1"        # developer A/B: stride-2 ConvTranspose2d forward as one 9-tap launch
 # taps (kh * 3 + kw) of the four sub-pixel phases (output parity (a, b): rows 2 i + a, columns 2 j + b), in the tap order of the
 # stride-1 convolution that computes the phase (first_stage._Conv._phase_operands); the phases' first blocks are 0, 1, 3, 5
 _CT_PERM = (4, 5, 3, 7, 1, 8, 6, 2, 0)
@@ -200,7 +194,7 @@ def _conv_transpose_phases(x, wop, kc, cout, dt, bias, act, out_f32, row_scale=N
     return K.CL(y, N, (1, Ho, Wo), cout)
 
 
-_DG_PHASES = os.environ.get("IPOKE_NO_DGRAD_PHASES", "0") != "1"     # developer A/B: strided 3 x 3 x 3 data gradients as one 27-tap launch
+_DG_PHASES = True       # test hook (tests/test_vae_bwd_units_gpu.py): False = strided 3 x 3 x 3 data gradients as one 27-tap launch (c4 48.0 vs 46.95 ms)
 _dg_index = {}
 
 
@@ -258,8 +252,7 @@ def _dgrad_phases(gcl, w, cin, idhw, st, dt):
 # its inputs exist, and the result is parked on the parameter (``_side_grad``) instead of going through autograd's accumulation, which
 # would read it on the caller's stream.  Leaving the context orders the caller's stream behind the second one and moves the parked
 # gradients to ``.grad``.  Only leaf parameters take this path; everything else (derived weights, other trainers) is untouched.
-_WGRAD_SIDE = {"stream": None, "params": []}
-_C4_WGRAD_SIDE = os.environ.get("IPOKE_C4_WGRAD_SIDE", "1") == "1"       # FirstStageTrainer.step: c4 42.9 -> 41.8 ms
+_WGRAD_SIDE = {"stream": None, "params": []}      # FirstStageTrainer.step: c4 42.9 -> 41.8 ms
 
 
 class wgrad_side_stream:
@@ -309,7 +302,7 @@ class _ConvFn(torch.autograd.Function):
             if meta["N"] % frames or meta.get("out_f32", False):
                 raise RuntimeError("frame-batched spectral norm: the batch must hold whole frames and a dtype output")
             rs = (snf[0].view(-1)[1:], meta["N"] // frames, 2)
-        if (_CT_PHASES and meta["transposed"] and x is not None and tuple(meta["k"]) == (1, 3, 3) and tuple(meta["stride"]) == (1, 2, 2)
+        if (meta["transposed"] and x is not None and tuple(meta["k"]) == (1, 3, 3) and tuple(meta["stride"]) == (1, 2, 2)
                 and tuple(meta["pad"]) == (0, 1, 1) and tuple(meta["out_pad"]) == (0, 1, 1)):
             y = _conv_transpose_phases(x, wop, kc, meta["cout"], dt, b, meta["act"], meta.get("out_f32", False), row_scale=rs)
         else:
@@ -594,9 +587,8 @@ class _StemFn(torch.autograd.Function):
 
 
 def stem_folds(mod, x):
-    """Whether conv1 on this clip can run folded (the reference's shipped geometry; otherwise the generic in-place path)."""
-    from .first_stage import _STEM_FOLD
-    return (_STEM_FOLD and not _STEM_TRAIN_UNFOLDED and x.shape[1] == 3 and tuple(mod.k) == (3, 7, 7) and tuple(mod.stride) == (2, 2, 2)
+    """Whether conv1 on this clip can run folded (the reference's shipped geometry; otherwise the generic in-place path: c4 50.3 vs 48.45 ms)."""
+    return (FS._STEM_FOLD and x.shape[1] == 3 and tuple(mod.k) == (3, 7, 7) and tuple(mod.stride) == (2, 2, 2)
             and tuple(mod.pad) == (1, 3, 3) and x.shape[4] % 2 == 0 and mod.bias is None and not mod.snorm and not mod.transposed)
 
 
@@ -770,19 +762,16 @@ class _NormFn(torch.autograd.Function):
             dres = torch.zeros_like(x_t) if x_t.shape[1] > C else torch.empty_like(x_t)
             d.dres = dres.data_ptr(); d.lddres = dres.shape[1]
         mod_n = int(m.get("mod_samples", 0)) if has_mod else 0
-        summed = False
         if has_mod:
             # the kernel writes columns 0 .. C-1 of every row; only padding columns (ld > C) need the zero fill
             alloc = torch.zeros if mg_t.shape[1] > C else torch.empty
-            # mod_n: the frames of a clip share its maps -- the kernel walks the frames and writes the sum (_NORM_FRAMES_SUM), or writes
-            # per-frame gradients [frames][clips * S][ld] that ipoke_sum_frames adds below
-            summed = bool(mod_n) and _NORM_FRAMES_SUM and mod_n < N
-            rows_mod = x_t.shape[0] if (mod_n and not summed) else mg_t.shape[0]
-            dmg = alloc(rows_mod, mg_t.shape[1], dtype=mg_t.dtype, device=mg_t.device)
-            dmb = alloc(rows_mod, mg_t.shape[1], dtype=mg_t.dtype, device=mg_t.device)
+            # mod_n: the frames of a clip share its maps -- the kernel walks the frames and writes the sum (c4 37.3 ms against 37.9 with
+            # per-frame gradients summed in a pass of their own)
+            dmg = alloc(mg_t.shape[0], mg_t.shape[1], dtype=mg_t.dtype, device=mg_t.device)
+            dmb = alloc(mg_t.shape[0], mg_t.shape[1], dtype=mg_t.dtype, device=mg_t.device)
             d.dmod_gamma = dmg.data_ptr(); d.dmod_beta = dmb.data_ptr(); d.ld_dmod = dmg.shape[1]
             d.mod_gamma = mg_t.data_ptr(); d.ld_mod = mg_t.shape[1]; d.mod_samples = mod_n
-            d.dmod_summed = int(summed)
+            d.dmod_summed = int(bool(mod_n))
         if has_affine:
             dgamma = torch.empty(C, dtype=torch.float32, device=dy.device); dbeta = torch.empty_like(dgamma)
             d.gamma = g32.data_ptr(); d.beta = b32.data_ptr(); d.dgamma = dgamma.data_ptr(); d.dbeta = dbeta.data_ptr()
@@ -803,26 +792,15 @@ class _NormFn(torch.autograd.Function):
             d.rs_dots = rs_dots.data_ptr(); d.rs_dbias = 0 if rs_db is None else rs_db.data_ptr(); d.rs_workspace = rs_ws.data_ptr()
             pm["_prescaled"] = (dx, rs_dots, rs_db)
         check(_lib.lib().ipoke_groupnorm_bwd(byref(d), ops._dt(dt), _lib.current_stream()))
-        if mod_n and not summed:
-            frames = N // mod_n
-            outs = []
-            for t_ in (dmg, dmb):
-                red = torch.empty_like(mg_t)
-                check(_lib.lib().ipoke_sum_frames(ptr(t_), ptr(red), frames, mg_t.numel(), ops._dt(dt), _lib.current_stream()))
-                outs.append(red)
-            dmg, dmb = outs
         return dx, dgamma, dbeta, dmg, dmb, dres, None
-
-
-_NORM_RS = os.environ.get("IPOKE_NORM_ROWSCALE", "1") != "0"      # developer A/B: the convolution's own ipoke_rowscale_bwd pass instead
-_NORM_FRAMES_SUM = os.environ.get("IPOKE_NORM_FRAMES_SUM", "1") != "0"      # developer A/B: per-frame modulation gradients + ipoke_sum_frames
 
 
 def _rowscale_producer(x, mod):
     """The meta of the convolution that produced ``x`` when the norm's backward may fold its row-scale pass: a frame-batched
-    spectral-norm convolution without activation whose dtype output this norm alone reads."""
+    spectral-norm convolution without activation whose dtype output this norm alone reads (c4 37.85 ms against 38.75 with the
+    convolution's own ipoke_rowscale_bwd pass)."""
     pm = getattr(x, "conv_meta", None)
-    if not _NORM_RS or pm is None or mod is not None or pm.get("sn_frames") is None or pm["act"] != _lib.ACT_NONE or pm.get("out_f32", False):
+    if pm is None or mod is not None or pm.get("sn_frames") is None or pm["act"] != _lib.ACT_NONE or pm.get("out_f32", False):
         return None
     frames = int(pm["sn_frames"][0].shape[0])
     if x.N % frames or x.t.shape[1] != x.C or x.C > 2048:
@@ -960,11 +938,9 @@ def gru_cell(cell, x, h, dtype, gate_w=None):
     return K.CL(hn, x.N, x.dhw, Ch)
 
 
-_GRU_NATIVE = os.environ.get("IPOKE_GRU_PYTHON", "0") != "1"      # the ConvGRU unroll issued by the library (csrc/gru.hip); 0: cell by cell from Python
-
-
 def gru_native_ok(rnn, x, h, dtype):
-    """The native unroll covers the shipped ConvGRU: 3 x 3 gates, every cell as wide as its input, power-of-two maps."""
+    """The native unroll (csrc/gru.hip) covers the shipped ConvGRU: 3 x 3 gates, every cell as wide as its input, power-of-two maps
+    (c4 51.1 ms against 56.9 cell by cell from Python, which is what runs otherwise)."""
     e = K.e16(dtype)
     cells = list(rnn.cells)
     H, W = x.dhw[1], x.dhw[2]
@@ -1170,13 +1146,10 @@ def convT_block(blk, x, dtype, pit=False, frames=None):
     return norm(blk.norm, conv(blk.conv, x, dtype, w=w), dtype, act=blk.act, sole_reader=True)
 
 
-_RES_POST = os.environ.get("IPOKE_NO_RES_POST", "0") != "1"         # developer A/B: ResBlock's sum as its own element-wise pass
-
-
 def res_block(blk, x, dtype, pit=False, frames=None):
     first = convT_block if isinstance(blk.conv1, FS.Conv2dTransposeBlock) else conv_block
     rc = blk.res_conv if blk.convolve_res else None
-    if _RES_POST and rc is not None and rc.norm is not None and blk.conv2.norm is None and blk.conv2.activation == "none":
+    if rc is not None and rc.norm is not None and blk.conv2.norm is None and blk.conv2.activation == "none":
         # out = conv2(conv1(x)) + act(norm(res_conv(x))): the sum rides on the skip path's norm pass, forward (the residual joins behind
         # the activation) and backward (its gradient is dy; act' from the recomputed pre-activation value, the saved output is not read)
         y2 = conv_block(blk.conv2, first(blk.conv1, x, dtype, pit=pit, frames=frames), dtype, pit=pit, frames=frames)
@@ -1194,15 +1167,11 @@ def res_block(blk, x, dtype, pit=False, frames=None):
 def spade_modulation(sp, y_nchw, size, dtype):
     N = y_nchw.shape[0]
     ycl = K.bilinear_cl(y_nchw, size)
-    if _SPADE_DENSE_INPUT:
-        # the resized start frame as dense channels-last pixels of the compute dtype, zero padded to one 16-byte chunk: the same rounding the
-        # in-place fp32 read applies on load, but the convolution and -- above all -- its weight gradient run on the LDS-DMA kernels instead
-        # of the register-staged fp32-source ones (4 x ~400 us per c4 step for 2.3 GFLOP each)
-        x = K.CL(_pad_cols(ycl, K.e16(dtype), dtype), N, (1, size[0], size[1]), 3)
-        h = conv(sp.conv, x, dtype, act=_lib.ACT_LRELU02)
-    else:
-        st = (size[0] * size[1] * 3, 1, 0, size[1] * 3, 3)
-        h = conv(sp.conv, None, dtype, act=_lib.ACT_LRELU02, src=(ycl, N, 3, (1, size[0], size[1]), st))
+    # the resized start frame as dense channels-last pixels of the compute dtype, zero padded to one 16-byte chunk: the same rounding an
+    # in-place fp32 read applies on load, but the convolution and -- above all -- its weight gradient run on the LDS-DMA kernels instead
+    # of the register-staged fp32-source ones (4 x ~400 us per c4 step for 2.3 GFLOP each)
+    x = K.CL(_pad_cols(ycl, K.e16(dtype), dtype), N, (1, size[0], size[1]), 3)
+    h = conv(sp.conv, x, dtype, act=_lib.ACT_LRELU02)
     return conv(sp.conv_gamma, h, dtype), conv(sp.conv_beta, h, dtype)
 
 
@@ -1261,7 +1230,7 @@ def first_stage_forward_loss(model, X, eps, w_l1=10.0, w_kl=1e-7, power_iteratio
     batched = _FRAME_BATCH and mods is not None and T > 2 and B * (T - 1) * X.shape[-1] * X.shape[-2] * 64 < (1 << 31)
     sn_pre = precompute_power_iterations(model.gen, T - 1) if (pit and (_SN_AHEAD or batched)) else []
     hs = []
-    native_gru = batched and _GRU_NATIVE and gru_native_ok(model.rnn, in_rnn, m, dt)
+    native_gru = batched and gru_native_ok(model.rnn, in_rnn, m, dt)
     for t in range(0 if native_gru else T - 1):
         xin = in_rnn
         new_hidden = []
@@ -1475,19 +1444,15 @@ class FirstStageTrainer:
         loss, X_hat, mu, lv = first_stage_forward_loss(m, X, eps)
         if self.w_vgg != 0.0:
             loss = loss + self.w_vgg * self.vgg_loss(X[:, 1:].reshape(-1, *X.shape[2:]).float(), X_hat.reshape(-1, *X_hat.shape[2:]))
-        if _C4_WGRAD_SIDE:
-            if getattr(self, "_wgrad_stream", None) is None:
-                from .utils.streams import overlapping_stream
-                self._wgrad_stream = overlapping_stream()
-            with wgrad_side_stream(self._wgrad_stream):
-                loss.backward()
-        else:
+        if getattr(self, "_wgrad_stream", None) is None:
+            from .utils.streams import overlapping_stream
+            self._wgrad_stream = overlapping_stream()
+        with wgrad_side_stream(self._wgrad_stream):
             loss.backward()
         if self.grad_hook is not None:
             self.grad_hook()
-        snap = take_operand_cache() if _OPERAND_REFRESH else None
+        snap = take_operand_cache()
         self.opt.step()
         m.invalidate_operands()
-        if snap is not None:
-            refresh_operand_cache(snap)
+        refresh_operand_cache(snap)
         return loss.detach(), X_hat.detach()

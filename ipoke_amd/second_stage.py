@@ -345,7 +345,7 @@ class PokeMotionModel(nn.Module):
             sX, sP = X.clone(), poke.clone()
             sE = None if eps is None else eps.to(X.device)
             torch.cuda.synchronize()
-            side = torch.cuda.Stream() if os.environ.get("IPOKE_ENC_GRAPH_SIDE", "1") != "0" else None
+            side = torch.cuda.Stream()
             g = torch.cuda.CUDAGraph()
             with torch.no_grad(), torch.cuda.graph(g):
                 out = self._flow_input_device(sX, sP, sE, side=side)

@@ -68,14 +68,9 @@ class SecondStageTrainer:
             # one captured hipGraph, gated on the GPU side at the END of the backward pass, instead of ~200 eager launches
             if os.environ.get("IPOKE_ENC_GRAPH", "0") == "1":
                 model.set_encoder_graph(True)
-        self.enc_graph_at = os.environ.get("IPOKE_ENC_GRAPH_AT", "bwd")        # developer A/B: "fwd" = may start right behind the forward pass
-        self.prefetch_at_start = os.environ.get("IPOKE_PREFETCH_AT", "after_bwd") == "start"
-        # IPOKE_PREFETCH_AT=piece<k> (developer A/B, measured round 3, NOT adopted): the next batch's encoders are queued when the
-        # backward pass has issued its k-th piece (of IPOKE_PIECES), ordered after that point of the chain, so that they overlap the rest
-        # of the backward pass instead of following it: 60.7 (k = 11) / 61.4 (k = 6 .. 10) against 59.1 ms -- beside the backward chain and
-        # its side streams the full-chip encoder kernels cost more than the 4 ms hole they fill (the same verdict as =start)
-        at = os.environ.get("IPOKE_PREFETCH_AT", "")
-        self.prefetch_piece = int(at[5:]) if at.startswith("piece") else None
+        # The next batch's encoders are queued BEHIND the backward pass.  Measured and not adopted: queued before this step's forward
+        # (69.7 vs 63.7 ms) or when the backward pass has issued its k-th piece (60.7 at k = 11, 61.4 at k = 6 .. 10, against 59.1 ms) --
+        # beside the latency-bound chain and its side streams the full-chip encoder kernels cost more than the hole they fill
         # IPOKE_PREFETCH_THREAD=1: the next batch's encoders are queued by a second host thread while this thread is inside the engine's
         # backward call (a foreign call: the interpreter lock is free), ordered behind the forward pass on the GPU
         self.prefetch_thread = os.environ.get("IPOKE_PREFETCH_THREAD", "0") == "1"
@@ -100,11 +95,6 @@ class SecondStageTrainer:
             if "err" in box:
                 raise box["err"]
         return join
-
-    def _optimizer_step(self, fn):
-        # (Issuing the update on its own stream so that the next step's frozen encoders run underneath it was measured:
-        # 88.0 vs 87.1 ms -- both sides stream HBM, and Adam's persistent grid starves the concurrent kernels.  Not done.)
-        return fn()
 
     def _grads_ready(self, begin, end):
         """grads[begin:end] is final at the current point of ``ready_stream``: all-reduce it there (data parallel) and
@@ -162,16 +152,6 @@ class SecondStageTrainer:
         m = self.model
         m.on_train_batch_start(batch, batch_idx, 0)
         prefetch = next_batch is not None and self.prefetch_stream is not None
-        if prefetch and self.prefetch_at_start:
-            # developer switch IPOKE_PREFETCH_AT=start (measured, NOT adopted: 69.7 vs 63.7 ms): the next batch's frozen encoders
-            # queued BEFORE this step's forward, to run underneath it (no weight gradients / optimizer there) instead of behind
-            # the backward pass.  The forward chain is latency-bound; full-chip encoder kernels beside it slow it by more
-            # than the hole they leave (scripts/probe_host.py: the host needs 29 ms per step and is throttled by the queue depth,
-            # so the ~7 ms of queueing are not what costs).
-            step_start = torch.cuda.Event()
-            step_start.record()
-            m.prefetch_flow_input(next_batch, self.prefetch_stream, after=step_start)
-            prefetch = False
         loss = m.training_step(batch, batch_idx)
         if prefetch:
             fwd_done = torch.cuda.Event()
@@ -197,20 +177,9 @@ class SecondStageTrainer:
             native = self.native_opt and self._acc_count == 0 and not eng.shadow_stale
             if native:
                 self.opt.arm_native(grad_scale=1.0 / (self.world * self.accumulate_grad_batches))
-            hook_fn = None if native else self._grads_ready
-            if native and prefetch and self.prefetch_piece is not None:
-                state = {"done": False}
-
-                def hook_fn(begin, end, piece, _state=state):
-                    if not _state["done"] and piece >= self.prefetch_piece:
-                        _state["done"] = True
-                        here = torch.cuda.Event()
-                        here.record()
-                        m.prefetch_flow_input(next_batch, self.prefetch_stream, after=here)
-                hook_fn.wants_piece = True
-            eng.grad_ready_hook = (self.n_grad_buckets, self.ready_stream, hook_fn)
+            eng.grad_ready_hook = (self.n_grad_buckets, self.ready_stream, None if native else self._grads_ready)
             worker = None
-            if prefetch and self.prefetch_thread and self.prefetch_piece is None:
+            if prefetch and self.prefetch_thread:
                 worker = self._prefetch_in_thread(next_batch, fwd_done)
                 prefetch = False
             ok = False
@@ -223,15 +192,20 @@ class SecondStageTrainer:
                     self.opt.disarm_native()
                 if worker is not None:
                     worker()
-            if prefetch and not (native and self.prefetch_piece is not None and state["done"]):
+            if prefetch:
                 after = fwd_done
-                if getattr(m, "_graph_encoders", False) and self.enc_graph_at == "bwd":
+                if getattr(m, "_graph_encoders", False):
                     # a graph replay is ONE host call: the host, several ms ahead of the GPU here, would start it in the middle of the
                     # backward pass; the event holds it until the chain (and the ready stream's last slice) is done
                     after = torch.cuda.Event()
                     after.record()
                 m.prefetch_flow_input(next_batch, self.prefetch_stream, after=after)      # queued after the backward pass (host order = GPU start order)
-            self._optimizer_step(self.opt.finish_native if native else self.opt.finish_step)
+            # (Issuing the update on its own stream so that the next step's frozen encoders run underneath it was measured:
+            # 88.0 vs 87.1 ms -- both sides stream HBM, and Adam's persistent grid starves the concurrent kernels.  Not done.)
+            if native:
+                self.opt.finish_native()
+            else:
+                self.opt.finish_step()
         else:
             loss.backward()
             if prefetch:
@@ -240,7 +214,7 @@ class SecondStageTrainer:
                 m.flow.flat_grads.add_(self._acc)
             if self.world > 1:
                 D.allreduce_flat_(m.flow.flat_grads, self.n_grad_buckets)
-            self._optimizer_step(lambda: self.opt.step(grad_scale=1.0 / (self.world * k)))
+            self.opt.step(grad_scale=1.0 / (self.world * k))
         self._acc_count = 0
         m.global_step += 1
         return loss

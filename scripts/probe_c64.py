@@ -1,6 +1,5 @@
 """Developer probe: the filter-resident stride-1 convolution on huge maps (conv3x3_c64_kernel) at the decoder's 128 x 128 layers --
-64 -> 64 and the image head 64 -> 3 (fp32 output), 300 and 480 images -- per patch time; with IPOKE_LIB_PATH pointing at a
--DIPOKE_C64_ABL=n build: 1 no MFMA, 2 no epilogue, 3 no image stream."""
+64 -> 64 and the image head 64 -> 3 (fp32 output), 300 and 480 images -- per patch time."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,7 +1,5 @@
-"""Developer probe: isolated timing of the fused MaCowUnit kernels with cold (rotating) weight sets, and -- through the
-stamped probe build scripts/exp/libunit_probe.so (hipcc -DIPOKE_UNIT_STAMPS mcf_unit.hip common.cpp) -- the shader-clock
-time line of one workgroup."""
-import ctypes
+"""Developer probe: isolated timing of the fused MaCowUnit kernels with cold (rotating) weight sets, alone and next to a busy
+second stream."""
 import os
 import sys
 
@@ -74,43 +72,6 @@ def run(fn, n=240):
 
 print(f"C={C} B={B}: fused unit fwd {run(lib.ipoke_macow_unit_fwd):.1f} us  bwd {run(lib.ipoke_macow_unit_bwd):.1f} us  (per unit = 4 layers)")
 
-probe_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "exp", "libunit_probe.so")
-if os.path.exists(probe_path):
-    P = ctypes.CDLL(probe_path)
-    P.ipoke_macow_unit_fwd.argtypes = [ctypes.POINTER(_lib.McfDesc), ctypes.c_int, ctypes.c_void_p]
-    P.ipoke_macow_unit_set_stamps.argtypes = [ctypes.c_void_p]
-    st = torch.zeros(64, dtype=torch.int64, device=dev)
-    P.ipoke_macow_unit_set_stamps(ctypes.c_void_p(st.data_ptr()))
-    for u in range(NU):                                  # rotate so that the stamped launch sees cold weights
-        assert P.ipoke_macow_unit_fwd(D[u], _lib.BF16, s) == 0
-    torch.cuda.synchronize()
-    t = st.cpu().tolist()
-    names = ["entry(loads issued)", "staged"]
-    for k in range(4):
-        names += [f"L{k} gemm1", f"L{k} sync", f"L{k} a2save", f"L{k} gemm2", f"L{k} sync", f"L{k} epilogue+sum"]
-    prev = t[0]
-    for i, nme in enumerate(names):
-        print(f"  {nme:24s} +{t[i] - prev:7d} cyc   (t = {t[i] - t[0]:7d})")
-        prev = t[i]
-    P.ipoke_macow_unit_bwd.argtypes = [ctypes.POINTER(_lib.McfDesc), ctypes.c_int, ctypes.c_void_p]
-    st.zero_()
-    for u in range(NU):
-        assert P.ipoke_macow_unit_bwd(D[u], _lib.BF16, s) == 0
-    torch.cuda.synchronize()
-    t = st.cpu().tolist()
-    names = ["entry(loads issued)"]
-    for k in (3, 2, 1, 0):
-        names += [f"L{k} top", f"L{k} (a)", f"L{k} sync", f"L{k} colsum+(b)", f"L{k} sync", f"L{k} (c)+2 syncs"]
-    prev = t[0]
-    print("backward:")
-    for i, nme in enumerate(names):
-        print(f"  {nme:24s} +{t[i] - prev:7d} cyc   (t = {t[i] - t[0]:7d})")
-        prev = t[i]
-    for q, k in enumerate((3, 2, 1, 0)):
-        b = 32 + 4 * q
-        print(f"  L{k} (c) detail: sync->pass lo {t[b] - t[5 + 6 * q]}, pass hi {t[b + 1] - t[b]}, w1t issue {t[b + 2] - t[b + 1]}, "
-              f"exchange+2 syncs {t[b + 3] - t[b + 2]}")
-
 
 # ---- inverse (sampling): x = unit^-1(y), two samples per workgroup, 4 layers x 8 strips
 yinv = torch.randn(M, ld, device=dev, generator=g)
@@ -133,20 +94,6 @@ def inv_descs(u):
 DI = [inv_descs(u) for u in range(NU)]
 D, D_fb = DI, D
 print(f"C={C} B={B}: fused unit inverse {run(lib.ipoke_macow_unit_inv):.1f} us")
-if os.path.exists(probe_path):
-    P.ipoke_macow_unit_inv.argtypes = [ctypes.POINTER(_lib.McfDesc), ctypes.c_int, ctypes.c_void_p]
-    st.zero_()
-    for u in range(NU):
-        assert P.ipoke_macow_unit_inv(DI[u], _lib.BF16, s) == 0
-    torch.cuda.synchronize()
-    t = st.cpu().tolist()
-    print(f"inverse: prologue done at t = 0; layer ends at {[t[49 + q] - t[0] for q in range(4)]}")
-    names = ["top", "cond rows", "gemm1+ELU", "sync", "gemm2", "sync"]
-    for step in range(8):
-        row = [t[1 + 6 * step + q] for q in range(6)]
-        nxt = t[1 + 6 * (step + 1)] if step < 7 else t[49]
-        d = [row[q + 1] - row[q] for q in range(5)] + [nxt - row[5]]
-        print(f"  layer D strip {step}: cond rows {d[0]:5d}  gemm1+ELU {d[1]:5d}  sync {d[2]:5d}  gemm2 {d[3]:5d}  sync {d[4]:5d}  coupling+sync {d[5]:5d}   total {nxt - row[0]:6d}")
 D = D_fb
 
 

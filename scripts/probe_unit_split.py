@@ -143,33 +143,6 @@ def timing(C, B, n=240, bwd=True):
         print(f"timing C={C} B={B} split={S}: " + "  ".join(f"{t:.1f} us" for t in res) + f"  (fwd{', bwd' if bwd else ''}; timeouts {int(o['xchg'][0].item())})")
 
 
-def stamps(C, B, S):
-    import ctypes
-    probe_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "exp", "libunit_probe.so")
-    if not os.path.exists(probe_path):
-        return
-    P = ctypes.CDLL(probe_path)
-    P.ipoke_macow_unit_fwd.argtypes = [ctypes.POINTER(_lib.McfDesc), ctypes.c_int, ctypes.c_void_p]
-    P.ipoke_macow_unit_set_stamps.argtypes = [ctypes.c_void_p]
-    NU = 24
-    cs = Case(C, B, 64, NU)
-    o = cs.outputs(S)
-    st = torch.zeros(256, dtype=torch.int64, device=dev)
-    P.ipoke_macow_unit_set_stamps(ctypes.c_void_p(st.data_ptr()))
-    for u in range(NU):
-        assert P.ipoke_macow_unit_fwd(cs.descs(u, o, S), _lib.BF16, s) == 0
-    torch.cuda.synchronize()
-    t = st.cpu().view(4, 64).tolist()
-    names = ["entry", "staged"]
-    for k in range(4):
-        names += [f"L{k} tile(s) a", f"L{k} halo+sync", f"L{k} last tile", f"L{k} sync", f"L{k} a2save", f"L{k} gemm2", f"L{k} sync", f"L{k} coupling+sum"]
-    t00 = t[0][0]
-    print(f"forward stamps C={C} B={B} S={S} (cycles @100 MHz s_memtime? see ratio; columns = workgroups 0..{S - 1}: delta / absolute)")
-    for i, nme in enumerate(names):
-        row = "  ".join(f"+{t[w][i] - t[w][i - 1] if i else 0:6d} ({t[w][i] - t00:7d})" for w in range(S))
-        print(f"  {nme:18s} {row}")
-
-
 if __name__ == "__main__":
     bwd = WHAT != "fwd"
     allok = True
@@ -178,5 +151,3 @@ if __name__ == "__main__":
     print("ALL OK" if allok else "FAILURES")
     timing(CT, BT, bwd=bwd)
     timing(32, BT, bwd=bwd)
-    for S in (2, 4):
-        stamps(CT, BT, S)

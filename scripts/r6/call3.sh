@@ -6,7 +6,6 @@ import json; d=json.load(open("$O/c3_$tag.json")); print("$tag", d["ms_per_step"
 PY
 }
 b base A=1
-b at_start IPOKE_PREFETCH_AT=start
 b noprefetch IPOKE_NO_PREFETCH=1
 b chain IPOKE_PREFETCH_STREAM=chain
 cd /tmp

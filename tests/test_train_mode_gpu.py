@@ -130,8 +130,8 @@ def check_step(m, g, dtype, tag, loss, X_hat, mu, slots=1):
 def test_first_stage_train_mode_step(golden, monkeypatch, variant, dtype):
     """One clip through the c4 code path (train mode): with the default switches (round 4: ALL frames decoded as one (frame, clip)-ordered
     batch, one operand of W_orig, 1 / sigma_t in the GEMM epilogues, one weight gradient per convolution + the rank-1 sigma terms);
-    frame by frame (IPOKE_C4_PER_FRAME=1: the default of rounds 2-3); frame by frame with the power iterations at the call sites
-    (IPOKE_NO_SN_AHEAD=1: the reference's literal order of work); and with per-frame SPADE maps (IPOKE_NO_SPADE_HOIST=1).  All must
+    frame by frame (_FRAME_BATCH = False: the default of rounds 2-3); frame by frame with the power iterations at the call sites
+    (_SN_AHEAD = False: the reference's literal order of work); and with per-frame SPADE maps (_HOIST_SPADE = False).  All must
     reproduce the reference's X_hat, loss, gradients and u / v buffers."""
     from ipoke_amd import first_stage_train as FT
     g = golden("g13_first_stage_train_mode_128")
@@ -230,7 +230,7 @@ def test_spectral_sigma_multi_matches_sequential_calls():
 
 @pytest.mark.parametrize("dtype,copies", [("f32", 1), ("bf16", 4)])
 def test_weight_gradients_on_a_second_stream(golden, dtype, copies):
-    """``wgrad_side_stream`` (FirstStageTrainer.step under IPOKE_C4_WGRAD_SIDE=1): the weight-gradient half of every convolution's backward
+    """``wgrad_side_stream`` (FirstStageTrainer.step runs its backward pass inside it): the weight-gradient half of every convolution's backward
     queued on a second stream and parked on the parameter until the context ends.  Same kernels on the same data: the reference's
     reconstruction, loss and gradient checksums hold as for the plain backward (three repetitions on a fresh model each -- a missing
     ordering between the streams reads unfinished buffers), every parameter that has a gradient in the plain backward has one, and nothing

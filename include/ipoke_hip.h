@@ -815,6 +815,23 @@ long ipoke_l1_loss_partials(void);
 int ipoke_l1_loss(const float* yhat_cl, int ldy, const float* x_nchw, int N, int C, int S, int64_t x_sn, float scale,
                   float* loss_accum, float* grad_cl, int ldg, float* partials, void* stream);
 
+/* Loss of the 2-D poke / image autoencoders with a device-resident log-variance (replaces conv_poke_encoder.py:68-78 and
+ * first_stage_image_conv.py:138-149: rec_loss = |x - rec| + perc_weight * p; nll = sum(rec_loss / exp(logvar) + logvar) / N).
+ * pre_cl: the decoder's output, channels-last fp32 [N*S][ld], C channels; act: IPOKE_ACT_NONE or IPOKE_ACT_TANH (applied here).
+ * x_nchw: target fp32 [N][C][S] with sample stride x_sn; logvar: device scalar; p ([N], may be NULL) with perc_weight (device scalar):
+ * the per-sample perceptual value and its weight.  Writes
+ *   rec_cl [N*S][ld_rec] = act(pre);  out[0] = nll = (sum |x - rec| + C*S*w*sum_n p[n]) * exp(-logvar) / N + C*S*logvar,
+ *   out[1] = sum |x - rec|,  out[2] = d nll / d logvar,
+ *   grad_pre [N*S][ld_grad] (may be NULL) = sign(rec - x) * exp(-logvar) / N * act'(rec), sign(0) = 0,
+ *   grad_p [N] (may be NULL) = C*S*w*exp(-logvar) / N.
+ * Columns C .. min(ld, pitch) - 1 of rec_cl / grad_pre are written as zeros.  The sums run in double in a fixed order through
+ * `partials` (ipoke_l1_nll_partials() doubles of caller-owned scratch): no float atomics, the result is reproducible run to run.
+ * x_nchw == NULL: only rec_cl is written (the autoencoders' inference direction); logvar, out and partials may then be NULL. */
+long ipoke_l1_nll_partials(void);
+int ipoke_l1_nll(const float* pre_cl, int ld, int act, const float* x_nchw, int N, int C, int S, int64_t x_sn, const float* logvar,
+                 const float* p, const float* perc_weight, float* out, float* rec_cl, int ld_rec, float* grad_pre, int ld_grad,
+                 float* grad_p, double* partials, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * FVD evaluation (reference utils/metrics.py; host side in ipoke_amd/fvd.py).  The I3D convolutions are ipoke_conv_forward
  * with the eval-mode BatchNorm folded into weight and bias; these are the element-wise / window kernels around them.

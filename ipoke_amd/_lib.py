@@ -257,6 +257,8 @@ SIGNATURES = {
     "ipoke_reparam_bwd": (c_int, [_P, c_int, _P, _P, _P, _P, _P, c_int, c_int64, c_int, c_int, _P]),
     "ipoke_l1_loss": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int64, c_float, _P, _P, c_int, _P, _P]),
     "ipoke_l1_loss_partials": (ctypes.c_long, []),
+    "ipoke_l1_nll": (c_int, [_P, c_int, c_int, _P, c_int, c_int, c_int, c_int64, _P, _P, _P, _P, _P, c_int, _P, c_int, _P, _P, _P]),
+    "ipoke_l1_nll_partials": (ctypes.c_long, []),
     "ipoke_relayout_multi_range": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, _P]),
     "ipoke_wn_scale_multi_range": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "ipoke_flow_prepare_weights_range": (c_int, [_P, _P, _P, c_int64, c_int64, _P]),

@@ -77,6 +77,28 @@ def encoder2d_config(spatial_size=128, nf_in=2, flow_ae=True):
     return {"data": {"spatial_size": (spatial_size, spatial_size)}, "architecture": arch}
 
 
+def poke_encoder_train_config(spatial_size=128, flow_ae=True, poke_and_image=False):
+    """poke_encoder.yaml restated: the keys ``autoencoder2d.ConvPokeAE`` and ``PokeEncoderTrainer`` consume."""
+    conf = encoder2d_config(spatial_size, 2, flow_ae)
+    conf["architecture"]["poke_and_image"] = poke_and_image
+    conf["data"].update(batch_size=64, max_frames=10, n_pokes=5)
+    conf["training"] = {"lr": 1e-3, "weight_decay": 0, "n_epochs": 20, "max_batches_per_epoch": 2000, "max_val_batches": 200, "w_kl": 1,
+                        "forward_sample": True}
+    conf["logging"] = {"n_val_img_batches": 4, "log_train_prog_at": 300, "n_log_images": 8}
+    return conf
+
+
+def img_encoder_train_config(spatial_size=64):
+    """img_encoder.yaml restated: the keys ``autoencoder2d.ConvAEModel`` and ``ImageEncoderTrainer`` consume.  ``pretrain``: the first
+    epoch of the adversarial phase, which is not built (the model raises there)."""
+    conf = encoder2d_config(spatial_size, 3)
+    conf["data"].update(batch_size=128, max_frames=1, n_pokes=1)
+    conf["training"] = {"lr": 2e-4, "weight_decay": 0, "n_epochs": 20, "max_val_batches": 200, "pretrain": 2, "w_kl": 1e-6,
+                        "forward_sample": True, "gp_weight": 1.0}
+    conf["logging"] = {"n_val_img_batches": 4, "log_train_prog_at": 300, "n_log_images": 8}
+    return conf
+
+
 def second_stage_config(spatial_size=128, z_dim=64, n_frames=16, batch_size=20, n_epochs=100, arch=None):
     """second_stage.yaml restated with the architecture derived as PokeMotionModel.__init__ does."""
     return {

@@ -359,7 +359,7 @@ typedef struct {
   void* zc_out; int32_t zc_off, zc_stride, zc_cin, zc_ld;
   /* ipoke_macow_unit_fwd / _bwd only, read from d4[0]: split = 2 or 4 runs a sample's 8x8 latent on that many workgroups (grid rows
    * dealt in order; the workgroups exchange the 1-2 halo rows a masked convolution reads across the cut inside the launch).
-   * xchg = scratch of ipoke_macow_unit_xchg_bytes(B, split) bytes, zero-initialised ONCE by the caller and used by one launch at a
+   * xchg = scratch of ipoke_macow_unit_xchg_bytes(B, split) bytes (sized for a two-unit launch), zero-initialised ONCE by the caller and used by one launch at a
    * time (launches on one stream); the kernels leave it all-zero.  Its first 32-bit word counts hand-off time-outs (0 = healthy).
    * Outputs as with split = 0 / 1 (bit-identical states, saves and data gradients) except: logdet_slot[b * w + s] holds part s of
    * the layer's log-det (w >= split), and dbias_part / post_part have split rows per sample (row b * split + s). */
@@ -403,6 +403,19 @@ int ipoke_macow_unit_bwd(const ipoke_mcf_desc* d4, int dtype, void* stream);
 /*   inverse : d4[3].x = the unit's OUTPUT state, d4[0].y = the reconstructed input (distinct buffers); W1 / W2 / bias2 /
  *             post_* per layer as for the forward call; two samples per workgroup, the 4 x 8 strips of macow2.py:174-288 */
 int ipoke_macow_unit_inv(const ipoke_mcf_desc* d4, int dtype, void* stream);
+/* TWO adjacent MaCowUnits of the same width C, pitch, batch and conditioning map in one launch per direction: d8 = the eight masked-conv
+ * descriptors in forward order (d8[0..3] the lower unit, d8[4..7] the upper one), each filled as for the calls above, with "d4[3]"
+ * read as d8[7] (forward: output state, pass-through channels and zc_out; backward: dy; inverse: the input state) and d8[0] as before
+ * (x, dx, dld, split, xchg, pair: the pair attaches to the LOWER unit).  The state between the units stays on chip: d8[3].y is an
+ * optional store like every other intermediate state (it also receives the pass-through channels; the backward pass reads it as
+ * d8[4].x).  Every buffer written comes out bit-identical to two four-layer calls; each of the eight layers keeps its own log-det
+ * slot and partial-sum rows.  Forward / backward need split = 2 or 4 (the one-workgroup-per-sample kernels keep four layers).
+ * ipoke_macow_unit2_applicable: host-only, 1 where the two-unit launch of `direction` exists for this shape. */
+enum { IPOKE_UNIT2_FWD = 0, IPOKE_UNIT2_BWD = 1, IPOKE_UNIT2_INV = 2 };
+int ipoke_macow_unit2_applicable(int C, int Cc, int dtype, int split, int direction);
+int ipoke_macow_unit2_fwd(const ipoke_mcf_desc* d8, int dtype, void* stream);
+int ipoke_macow_unit2_bwd(const ipoke_mcf_desc* d8, int dtype, void* stream);
+int ipoke_macow_unit2_inv(const ipoke_mcf_desc* d8, int dtype, void* stream);
 
 /* multi-tensor weight preparation (job tables are built by the flow engine) */
 int ipoke_relayout_job_size(void);

@@ -55,6 +55,9 @@ int ipoke_spin_delay(int us, void* stream);
 int ipoke_timing_start(void);
 int ipoke_timing_start_all(void);   /* also the IPOKE_TAG_CONV_* / IPOKE_TAG_WGRAD families */
 int ipoke_timing_stop(const int* tags, int ntags, int* counts, double* mean_us);
+/* Test hook: on != 0 makes every recorded launch count ONCE -- a launch that carries several units of work (ipoke_macow_unit2_*: two
+ * MaCowUnits, which the counts above report as two) then shows as the one launch it is; 0: back to counting units. */
+int ipoke_timing_raw_launches(int on);
 /* per tag: launches, SUM of durations (us), SUM of algorithmic FLOPs and bytes -- the per-configuration rooflines of bench.py */
 int ipoke_timing_stop_ex(const int* tags, int ntags, int* counts, double* total_us, double* flops, double* bytes);
 
@@ -75,6 +78,13 @@ int ipoke_flow_test_split_pair_dgrad(ipoke_flow* f, int on);
  * ("cpl_split"; the engine sets and clears both switches around its launches while the hook is on): every state, log-det and
  * gradient must come out bit-identical (the parity test of the fused launch); 0: back to the default.  Drops the handle's captured graphs. */
 int ipoke_flow_test_split_pair_coupling(ipoke_flow* f, int on);
+
+/* Test hook: on > 0 makes the flow's forward, backward and reverse passes run every MaCowUnit in a launch of its own even where two
+ * adjacent units of equal width would share one (ipoke_macow_unit2_fwd / _bwd / _inv); on < 0 makes them share one wherever
+ * ipoke_macow_unit2_applicable says yes, also in a direction whose measured default is a launch per unit (the reverse pass): every
+ * state, log-det and gradient must come out bit-identical (the parity test of the two-unit launch); 0: back to the default.  Drops
+ * the handle's captured graphs. */
+int ipoke_flow_test_split_unit2(ipoke_flow* f, int on);
 
 /* Test hook: forward unroll of the ConvGRU as one launch (1), as launches per phase (0); < 0 goes back to the default (1) */
 int ipoke_gru_set_fused(int mode);

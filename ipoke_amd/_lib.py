@@ -204,6 +204,10 @@ SIGNATURES = {
     "ipoke_macow_unit_fwd": (c_int, [POINTER(McfDesc), c_int, _P]),
     "ipoke_macow_unit_bwd": (c_int, [POINTER(McfDesc), c_int, _P]),
     "ipoke_macow_unit_inv": (c_int, [POINTER(McfDesc), c_int, _P]),
+    "ipoke_macow_unit2_applicable": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "ipoke_macow_unit2_fwd": (c_int, [POINTER(McfDesc), c_int, _P]),
+    "ipoke_macow_unit2_bwd": (c_int, [POINTER(McfDesc), c_int, _P]),
+    "ipoke_macow_unit2_inv": (c_int, [POINTER(McfDesc), c_int, _P]),
     "ipoke_relayout_job_size": (c_int, []),
     "ipoke_wn_job_size": (c_int, []),
     "ipoke_relayout_multi": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, c_int, _P]),
@@ -303,6 +307,7 @@ SIGNATURES = {
     "ipoke_timing_start": (c_int, []),
     "ipoke_timing_start_all": (c_int, []),
     "ipoke_timing_stop": (c_int, [POINTER(c_int), c_int, POINTER(c_int), POINTER(ctypes.c_double)]),
+    "ipoke_timing_raw_launches": (c_int, [c_int]),
     "ipoke_timing_stop_ex": (c_int, [POINTER(c_int), c_int, POINTER(c_int), POINTER(ctypes.c_double), POINTER(ctypes.c_double),
                                      POINTER(ctypes.c_double)]),
     "ipoke_flow_create": (c_int, [POINTER(FlowConfig), POINTER(c_void_p)]),
@@ -313,6 +318,7 @@ SIGNATURES = {
     "ipoke_flow_test_inject_timeout": (c_int, [_P, c_int, _P]),
     "ipoke_flow_test_split_pair_dgrad": (c_int, [_P, c_int]),
     "ipoke_flow_test_split_pair_coupling": (c_int, [_P, c_int]),
+    "ipoke_flow_test_split_unit2": (c_int, [_P, c_int]),
     "ipoke_conv_wgrad_splitm": (c_int, [_P, c_int, c_int]),
     "ipoke_conv_acc_scratch_bytes": (c_int64, [c_int, c_int, c_int]),
     "ipoke_conv_acc_scratch_init": (c_int, [_P, _P]),

@@ -22,6 +22,7 @@ extern "C" int ipoke_dtype_size(int dtype) { return dtype == IPOKE_BF16 ? 2 : dt
 #include <vector>
 namespace ipoke {
 struct TimedLaunch { int tag, units; hipEvent_t e0, e1; double flops = 0.0, bytes = 0.0; };
+static bool g_timing_raw = false;   // test hook ipoke_timing_raw_launches: a launch counts once whatever its units
 static int g_timing = 0;        // 0 off, 1 the flow's tagged families (tags < IPOKE_TAG_CONV_BASE), 2 every convolution / weight gradient as well
 static std::vector<TimedLaunch> g_timed;
 static std::vector<hipEvent_t> g_pool;
@@ -33,7 +34,7 @@ static hipEvent_t pooled_event() {
 bool timing_active(int tag) { return g_timing >= (tag >= IPOKE_TAG_CONV_BASE ? 2 : 1); }
 int timing_begin(int tag, hipStream_t s, int units) {
   if (!g_timing) return -1;
-  TimedLaunch t{tag, units < 1 ? 1 : units, pooled_event(), pooled_event(), 0.0, 0.0};
+  TimedLaunch t{tag, units < 1 || g_timing_raw ? 1 : units, pooled_event(), pooled_event(), 0.0, 0.0};
   (void)hipEventRecord(t.e0, s);
   g_timed.push_back(t);
   return (int)g_timed.size() - 1;
@@ -47,6 +48,7 @@ void timing_annotate(int slot, int tag, double flops, double bytes) {
   g_timed[slot].flops = flops; g_timed[slot].bytes = bytes;
 }
 }  // namespace ipoke
+extern "C" int ipoke_timing_raw_launches(int on) { ipoke::g_timing_raw = on != 0; return IPOKE_OK; }
 extern "C" int ipoke_timing_start(void) {
   ipoke::g_timed.clear(); ipoke::g_pool_next = 0; ipoke::g_timing = 1;
   return IPOKE_OK;

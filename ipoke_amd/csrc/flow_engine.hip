@@ -131,6 +131,7 @@ struct ipoke_flow {
   void* d_acc = nullptr; int64_t acc_bytes = 0;
   bool split_pair_dgrad = false;      // test hook (ipoke_flow_test_split_pair_dgrad): conv2's and conv1's data gradients as two launches
   bool split_pair_coupling = false;   // test hook (ipoke_flow_test_split_pair_coupling): conv2 and conv3 + coupling as two launches
+  int split_unit2 = 0;                // test hook (ipoke_flow_test_split_unit2): > 0 every MaCowUnit in a launch of its own, < 0 two units per launch in every direction
   unsigned* h_tmo = nullptr; hipEvent_t pass_ev = nullptr; hipStream_t pass_stream = nullptr; bool pass_recorded = false, pass_unchecked = false;
   int64_t xchg_bytes = 0;
   // every masked-conv layer is differentiated inside a fused MaCowUnit launch, which also writes the layer's input in the matrix
@@ -1283,6 +1284,20 @@ extern "C" int ipoke_flow_test_inject_timeout(ipoke_flow* f, int which, void* st
   IPK_LAUNCH_CHECK();
   return IPOKE_OK;
 }
+// Units come in pairs of equal width (MaCowStep: units1.0, units1.1 / units2.0, units2.1 back to back, nothing in between): where the
+// heads h and h + 6 are such a pair, ONE launch per direction runs both (ipoke_macow_unit2_*: the state / gradient between them stays
+// on chip, the upper unit's weights arrive under the lower one's last layer).  kUnit2Default: the measured per-direction decision
+// (the forward and the backward pass each pay by the project's margin over noise; the reverse pass gained 0.37-0.49 ms
+// of c5, less than three times the run-to-run spread in all three blocks, and keeps a launch per unit).  Sub-batch lanes and the
+// one-workgroup-per-sample kernels keep a launch per unit.
+static const bool kUnit2Default[3] = {true, true, false};      // IPOKE_UNIT2_FWD, _BWD, _INV
+static bool unit2_at(const ipoke_flow* f, int h, int direction, size_t nlanes) {
+  if (f->split_unit2 > 0 || (!kUnit2Default[direction] && f->split_unit2 == 0) || nlanes != 1 || h < 0 || h + 11 >= (int)f->ops.size()) return false;
+  const Op& a = f->ops[h]; const Op& b = f->ops[h + 6];
+  if (!(a.unit_head && b.unit_head && a.C == b.C && a.level == b.level)) return false;
+  const int split = direction == IPOKE_UNIT2_INV ? 0 : (f->unit_split > 1 && f->d_xchg ? f->unit_split : 1);
+  return ipoke_macow_unit2_applicable(a.C, f->cfg.cond_channels, f->cfg.dtype, split, direction) != 0;
+}
 /* Test hook (include/ipoke_hip_dev.h): the two-launch form of the coupling nets' conv2 + conv1 data gradients */
 extern "C" int ipoke_flow_test_split_pair_dgrad(ipoke_flow* f, int on) {
   IPK_REQUIRE(f != nullptr, "null flow handle");
@@ -1294,6 +1309,13 @@ extern "C" int ipoke_flow_test_split_pair_dgrad(ipoke_flow* f, int on) {
 extern "C" int ipoke_flow_test_split_pair_coupling(ipoke_flow* f, int on) {
   IPK_REQUIRE(f != nullptr, "null flow handle");
   f->split_pair_coupling = on != 0;
+  drop_graphs(f);      // captured passes hold the other form
+  return IPOKE_OK;
+}
+/* Test hook (include/ipoke_hip_dev.h): the two-launch form of adjacent MaCowUnits */
+extern "C" int ipoke_flow_test_split_unit2(ipoke_flow* f, int on) {
+  IPK_REQUIRE(f != nullptr, "null flow handle");
+  f->split_unit2 = on;
   drop_graphs(f);      // captured passes hold the other form
   return IPOKE_OK;
 }
@@ -1338,32 +1360,36 @@ static int run_forward(ipoke_flow* f, const float* params, const int32_t* perm, 
   for (size_t i = 0; i < f->ops.size(); ++i) {
     const Op& op = f->ops[i];
     if (init && op.type != OP_ACTNORM && op.type != OP_LU) continue;   // zero-initialised couplings are the identity (macow_utils.py:231-250)
-    if (!init && op.unit_head) {                   // whole MaCowUnit (ops i .. i+5) in one launch
-      const int nxt = save ? (int)i + 6 : (cur ^ 1);
-      static const int lidx[4] = {0, 1, 3, 4};     // the four masked convs among the six ops
-      static const int oidx[4] = {1, 3, 4, 6};     // state index (relative to i) each of them writes when states are saved
+    if (!init && op.unit_head) {                   // whole MaCowUnit (ops i .. i+5) in one launch, or two adjacent ones (ops i .. i+11)
+      const int nl = unit2_at(f, (int)i, IPOKE_UNIT2_FWD, lanes.size()) ? 8 : 4;
+      const int nops = nl / 4 * 6;
+      const int nxt = save ? (int)i + nops : (cur ^ 1);
+      static const int lidx[8] = {0, 1, 3, 4, 6, 7, 9, 10};     // the masked convs among the six ops of a unit
+      static const int oidx[8] = {1, 3, 4, 6, 7, 9, 10, 12};    // state index (relative to i) each of them writes when states are saved
       for (const Ctx& l : lanes) {
-        ipoke_mcf_desc d4[4];
-        for (int k = 0; k < 4; ++k) {
+        ipoke_mcf_desc d4[8];
+        for (int k = 0; k < nl; ++k) {
           const Op& mk = f->ops[i + lidx[k]];
           mcf_desc(l, mk, d4[k]);
           d4[k].x = k == 0 ? l.state(cur) : nullptr;
-          d4[k].y = k == 3 ? l.state(nxt) : (save ? l.state((int)i + oidx[k]) : nullptr);
+          d4[k].y = k == nl - 1 ? l.state(nxt) : (save ? l.state((int)i + oidx[k]) : nullptr);
           d4[k].logdet_slot = l.slot(mk.slot);
           d4[k].rows_per_block = 16;               // slot width 4, as the per-layer launches
           if (mk.fuse_act >= 0) { d4[k].post_log_scale = params + f->ops[mk.fuse_act].p_ls; d4[k].post_bias = params + f->ops[mk.fuse_act].p_bias; }
           if (save) { d4[k].a2_save = l.rows(mk.ws_a, (int64_t)mk.K2p * f->esz); d4[k].scale_save = l.rowsf(mk.ws_b, mk.C); }
         }
-        if (unit_feeds(f, i + 6)) {
-          const Op& nx = f->ops[i + 6];
-          d4[3].zc_out = save ? l.rows(nx.ws_g, (int64_t)nx.Kc1 * f->esz) : l.rows(l.plan.tmp_zc, 64L * f->esz);
-          d4[3].zc_off = nx.z_off; d4[3].zc_stride = nx.z_stride; d4[3].zc_cin = nx.cin; d4[3].zc_ld = nx.Kc1;
+        if (unit_feeds(f, i + nops)) {
+          const Op& nx = f->ops[i + nops];
+          ipoke_mcf_desc& dl = d4[nl - 1];
+          dl.zc_out = save ? l.rows(nx.ws_g, (int64_t)nx.Kc1 * f->esz) : l.rows(l.plan.tmp_zc, 64L * f->esz);
+          dl.zc_off = nx.z_off; dl.zc_stride = nx.z_stride; dl.zc_cin = nx.cin; dl.zc_ld = nx.Kc1;
         }
         if (f->unit_split > 1 && f->d_xchg) { d4[0].split = f->unit_split; d4[0].xchg = f->d_xchg; }
-        rc = ipoke_macow_unit_fwd(d4, l.dtype, l.stream()); if (rc) return rc;
+        rc = nl == 8 ? ipoke_macow_unit2_fwd(d4, l.dtype, l.stream()) : ipoke_macow_unit_fwd(d4, l.dtype, l.stream());
+        if (rc) return rc;
       }
       cur = nxt;
-      i += 5;
+      i += nops - 1;
       continue;
     }
     if (!init && op.fused) continue;               // done by the preceding MCF launch, which wrote this op's output state
@@ -1504,19 +1530,21 @@ static int run_reverse(ipoke_flow* f, const float* params, const int32_t* perm, 
   int cur = 0;
   for (int i = (int)f->ops.size() - 1; i >= 0; --i) {
     const Op& op = f->ops[i];
-    if (op.unit_of >= 0 && i == op.unit_of + 5) {     // whole MaCowUnit (ops h .. h+5) inverted by one launch
-      const int h = op.unit_of;
-      static const int lidx[4] = {0, 1, 3, 4};
+    if (op.unit_of >= 0 && i == op.unit_of + 5) {     // whole MaCowUnit (ops h .. h+5) inverted by one launch, or two adjacent ones (h .. h+11)
+      const int nl = unit2_at(f, op.unit_of - 6, IPOKE_UNIT2_INV, lanes.size()) ? 8 : 4;
+      const int h = nl == 8 ? op.unit_of - 6 : op.unit_of;
+      static const int lidx[8] = {0, 1, 3, 4, 6, 7, 9, 10};
       for (const Ctx& l : lanes) {
-        ipoke_mcf_desc d4[4];
-        for (int k = 0; k < 4; ++k) {
+        ipoke_mcf_desc d4[8];
+        for (int k = 0; k < nl; ++k) {
           const Op& mk = f->ops[h + lidx[k]];
           mcf_desc(l, mk, d4[k]);
           if (mk.fuse_act >= 0) { d4[k].post_log_scale = params + f->ops[mk.fuse_act].p_ls; d4[k].post_bias = params + f->ops[mk.fuse_act].p_bias; }
         }
-        d4[3].x = l.state(cur); d4[0].y = l.state(cur ^ 1);
-        d4[0].x = d4[3].x; d4[3].y = d4[0].y;          // (the shared validator wants input / output on the first / last layer)
-        rc = ipoke_macow_unit_inv(d4, l.dtype, l.stream()); if (rc) return rc;
+        d4[nl - 1].x = l.state(cur); d4[0].y = l.state(cur ^ 1);
+        d4[0].x = d4[nl - 1].x; d4[nl - 1].y = d4[0].y;          // (the shared validator wants input / output on the first / last layer)
+        rc = nl == 8 ? ipoke_macow_unit2_inv(d4, l.dtype, l.stream()) : ipoke_macow_unit_inv(d4, l.dtype, l.stream());
+        if (rc) return rc;
       }
       cur ^= 1;
       i = h;
@@ -1815,13 +1843,14 @@ static int run_backward(ipoke_flow* f, const float* params, const int32_t* perm,
   const int64_t goff[2] = {c.plan.g0, c.plan.g1};
   for (int i = (int)f->ops.size() - 1; i >= 0; --i) {
     const Op& op = f->ops[i];
-    if (op.unit_of >= 0 && i == op.unit_of + 5) {     // whole MaCowUnit (ops h .. h+5) differentiated by one launch
-      const int h = op.unit_of;
+    if (op.unit_of >= 0 && i == op.unit_of + 5) {     // whole MaCowUnit (ops h .. h+5) differentiated by one launch, or two adjacent ones (h .. h+11)
+      const int nl = unit2_at(f, op.unit_of - 6, IPOKE_UNIT2_BWD, lanes.size()) ? 8 : 4;
+      const int h = nl == 8 ? op.unit_of - 6 : op.unit_of;
       rc = maybe_flush_nice(); if (rc) return rc;
-      static const int lidx[4] = {0, 1, 3, 4};
+      static const int lidx[8] = {0, 1, 3, 4, 6, 7, 9, 10};
       for (const Ctx& l : lanes) {
-        ipoke_mcf_desc d4[4];
-        for (int k = 0; k < 4; ++k) {
+        ipoke_mcf_desc d4[8];
+        for (int k = 0; k < nl; ++k) {
           const int j = h + lidx[k];
           const Op& mk = f->ops[j];
           mcf_desc(l, mk, d4[k]);
@@ -1837,7 +1866,7 @@ static int run_backward(ipoke_flow* f, const float* params, const int32_t* perm,
             d4[k].post_part = l.dbp(mk.fuse_act, 2 * an.Cn, f->unit_split);
           }
         }
-        d4[3].dy = l.rowsf(goff[cur], l.ld); d4[0].dx = l.rowsf(goff[cur ^ 1], l.ld); d4[0].dld = l.dld();
+        d4[nl - 1].dy = l.rowsf(goff[cur], l.ld); d4[0].dx = l.rowsf(goff[cur ^ 1], l.ld); d4[0].dld = l.dld();
         IPK_REQUIRE(f->unit_split == 1 || f->d_xchg, "row-split unit launches without exchange scratch (ensure_tables)");
         if (f->unit_split > 1) { d4[0].split = f->unit_split; d4[0].xchg = f->d_xchg; }
         ipoke_unit_pair_desc pq;
@@ -1851,9 +1880,10 @@ static int run_backward(ipoke_flow* f, const float* params, const int32_t* perm,
           pq.dx = d4[0].dx;
           d4[0].pair = &pq;
         }
-        rc = ipoke_macow_unit_bwd(d4, l.dtype, l.stream()); if (rc) return rc;
+        rc = nl == 8 ? ipoke_macow_unit2_bwd(d4, l.dtype, l.stream()) : ipoke_macow_unit_bwd(d4, l.dtype, l.stream());
+        if (rc) return rc;
       }
-      for (int k = 3; k >= 0; --k) {                 // weight gradients: deferred, batched per run of same-width layers
+      for (int k = nl - 1; k >= 0; --k) {            // weight gradients: deferred, batched per run of same-width layers
         const int j = h + lidx[k];
         const Op& mk = f->ops[j];
         if (pend_lo >= 0 && (f->ops[pend_op].C != mk.C || pend_hi - pend_lo + 1 >= 256)) { rc = flush_mcf(); if (rc) return rc; }

@@ -85,9 +85,9 @@ __device__ __forceinline__ void unit_gemm2(const unsigned char* a2, int a2_pitch
 }
 
 template <typename T, bool WIDE>
-__global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_kernel(const UnitParams U) {
+__global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_kernel(const UnitParams4 U) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unit_kernarg_prefetch();
+  unit_kernarg_prefetch<4>();
   const int b = blockIdx.x, tid = threadIdx.x;
   McfW<T> wr;
   const int C = U.C, N2 = 2 * C, ld = U.ld;
@@ -267,13 +267,13 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_kernel(const UnitP
 // (b) back through the weight-normed 1x1 conv and ELU, (c) adjoint of the shifted convolution.  Weight fragments of the
 // next (= previous in forward order) layer are requested as soon as a phase has consumed the current ones.
 template <typename T, bool WIDE>
-__global__ __launch_bounds__(kMcfThreads) void macow_unit_bwd_kernel(const UnitParams U) {
+__global__ __launch_bounds__(kMcfThreads) void macow_unit_bwd_kernel(const UnitParams4 U) {
   constexpr int J1 = UC<WIDE>::J1, N3S = UC<WIDE>::N3S, HS = UC<WIDE>::HS;
   constexpr int KS = K64<T>::value, E16 = ET<T>::E16;
   typedef typename ET<T>::frag frag_t;
   typedef typename Pack4<T>::type pack_t;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unit_kernarg_prefetch();
+  unit_kernarg_prefetch<4>();
   const int b = blockIdx.x, tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6, r = lane & 15, gq = lane >> 4;
   const int C = U.C, N2 = 2 * C, ld = U.ld, H = U.H;
@@ -604,17 +604,18 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_bwd_kernel(const UnitP
 }
 
 // ------------------------------------------------------------------------------------------------ inverse (sampling)
-// x = unit^-1(y): ActNorm2^-1, D^-1, C^-1, ActNorm1^-1, B^-1, A^-1 in one launch, two samples per workgroup (a strip of 8
+// x = unit^-1(y): ActNorm2^-1, D^-1, C^-1, ActNorm1^-1, B^-1, A^-1 in one launch (U.nl = 8: of two adjacent units, the upper one first;
+// the state between them stays in LDS), two samples per workgroup (a strip of 8
 // positions per sample fills one 16-row matrix-core tile, as in mcf_inv_kernel).  A masked conv flow is inverted strip by
 // strip (8 rows / columns, macow2.py:174-288): the conditioner of a strip only sees strips already reconstructed.  The
 // state stays in LDS for the 4 x 8 strips; the weight fragments of the next layer are requested while the last strip of the
 // current one is being processed.
-template <typename T, bool WIDE>
-__global__ __launch_bounds__(kMcfThreads) void macow_unit_inv_kernel(const UnitParams U) {
+template <typename T, bool WIDE, int NLMAX>
+__global__ __launch_bounds__(kMcfThreads) void macow_unit_inv_kernel(const UnitParamsT<NLMAX> U) {
   constexpr int KS = K64<T>::value, E16 = ET<T>::E16, J1 = UC<WIDE>::J1;
   typedef typename ET<T>::frag frag_t;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unit_kernarg_prefetch();
+  unit_kernarg_prefetch<NLMAX>();
   const int tid = threadIdx.x;
   const int b0 = blockIdx.x * 2, nb = min(2, U.B - b0);
   const int C = U.C, N2 = 2 * C, ld = U.ld, H = U.H;
@@ -625,28 +626,37 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_inv_kernel(const UnitP
   unsigned char* a2 = xs + 2 * 65 * xs_pitch;                      // T [2][16][K2c]: the strip's [hidden | cond] operand, double-buffered
   unsigned char* cs = a2 + 2 * 16 * a2_pitch;                      // T [2][64][Cc]: ELU(cond) of the two samples
   float* yf = reinterpret_cast<float*>(cs + 2 * 64 * U.Cc * (int)sizeof(T));      // [2][64][C] fp32 state: y on entry of a layer, x on exit
-  float* bias_s = yf + 2 * 64 * C;                                 // [4][2C]
-  float* post_s = bias_s + 4 * N2;                                 // [4][2][C]: exp(log_scale) + 1e-8, bias of the ActNorms
+  const int NL = NLMAX == 4 ? 4 : U.nl;
+  float* bias_s = yf + 2 * 64 * C;                                 // [NL][2C]
+  float* post_s = bias_s + NL * N2;                                // [NL][2][C]: exp(log_scale) + 1e-8, bias of the ActNorms
   const long row0 = (long)b0 * 64;
   const int G2 = C >> 1;
   const int rows = nb * 64;
   const float inv_g2 = 1.f / (float)G2, inv_cch = 1.f / (float)(U.Cc / E16);     // (index arithmetic of the strip loop: no integer-division sequences)
 
-  // prologue: small loads first (results return in issue order), then the weights of layer D
+  // prologue: small loads first (results return in issue order), then the weights of the launch's last layer (D)
+  const UnitLayer& Ltop = U.L[NL - 1];
+  const float* y_in = Ltop.x;
   f32x2 yin[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const int e = tid + i * kMcfThreads;
     const int p = e / G2, c = (e - p * G2) * 2;
-    if (e < rows * G2) yin[i] = *reinterpret_cast<const f32x2*>(U.L[3].x + (row0 + p) * ld + c);
+    if (e < rows * G2) yin[i] = *reinterpret_cast<const f32x2*>(y_in + (row0 + p) * ld + c);
   }
-  float bias_v = 0.f, post_e = 0.f, post_b = 0.f;
-  bool post_on = false;
+  float bias_v[2] = {0.f, 0.f}, post_e[2] = {0.f, 0.f}, post_b[2] = {0.f, 0.f};
+  bool post_on[2] = {false, false};
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {      // static layer index: uniform pointers (see the forward kernel)
-    if (tid >= q * N2 && tid < (q + 1) * N2) bias_v = U.L[q].bias2[tid - q * N2];
-    if (U.L[q].post_ls && tid >= q * C && tid < (q + 1) * C) {
-      post_e = U.L[q].post_ls[tid - q * C]; post_b = U.L[q].post_bias[tid - q * C]; post_on = true;
+  for (int u = 0; u < 2; ++u) {      // static layer index: uniform pointers (see the forward kernel); one round of 4 x 2C threads per unit
+    if (u * 4 < NL) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const UnitLayer& Lq = U.L[u * 4 + q < NLMAX ? u * 4 + q : q];
+        if (tid >= q * N2 && tid < (q + 1) * N2) bias_v[u] = Lq.bias2[tid - q * N2];
+        if (Lq.post_ls && tid >= q * C && tid < (q + 1) * C) {
+          post_e[u] = Lq.post_ls[tid - q * C]; post_b[u] = Lq.post_bias[tid - q * C]; post_on[u] = true;
+        }
+      }
     }
   }
   McfW<T> wr;
@@ -667,8 +677,8 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_inv_kernel(const UnitP
 #pragma unroll
     for (int st = 0; st < UC<WIDE>::N2S; ++st) wr.w2[st][0] = buf_frag<T>(rs, w2_voff, st < w2_n2 ? st * 1024 : kOob);
   };
-  unit_load_w1<T, WIDE>(wr, U.L[3].W1, U);
-  load_w2_pairs(U.L[3].W2);
+  unit_load_w1<T, WIDE>(wr, Ltop.W1, U);
+  load_w2_pairs(Ltop.W2);
   for (int i = tid; i < (2 * 65 * xs_pitch + 2 * 16 * a2_pitch) / 16; i += kMcfThreads) reinterpret_cast<u32x4*>(smem)[i] = u32x4{0u, 0u, 0u, 0u};
   {   // ELU(cond) rows of both samples
     const int cchunks = U.Cc / E16;
@@ -680,13 +690,18 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_inv_kernel(const UnitP
     const int R2 = (ld - C) >> 1;
     for (int e = tid; e < rows * R2; e += kMcfThreads) {
       const int p = e / R2, c = C + (e - p * R2) * 2;
-      *reinterpret_cast<f32x2*>(U.L[0].y + (row0 + p) * ld + c) = *reinterpret_cast<const f32x2*>(U.L[3].x + (row0 + p) * ld + c);
+      *reinterpret_cast<f32x2*>(U.L[0].y + (row0 + p) * ld + c) = *reinterpret_cast<const f32x2*>(y_in + (row0 + p) * ld + c);
     }
   }
-  if (tid < 4 * N2) bias_s[tid] = bias_v;
-  if (tid < 4 * C) {
-    post_s[(tid / C) * 2 * C + tid % C] = post_on ? __expf(post_e) + 1e-8f : 1.f;      // macow2.py:520
-    post_s[(tid / C) * 2 * C + C + tid % C] = post_b;
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    if (u * 4 < NL) {
+      if (tid < 4 * N2) bias_s[u * 4 * N2 + tid] = bias_v[u];
+      if (tid < 4 * C) {
+        post_s[(u * 4 + tid / C) * 2 * C + tid % C] = post_on[u] ? __expf(post_e[u]) + 1e-8f : 1.f;      // macow2.py:520
+        post_s[(u * 4 + tid / C) * 2 * C + C + tid % C] = post_b[u];
+      }
+    }
   }
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
@@ -696,7 +711,7 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_inv_kernel(const UnitP
   }
   __syncthreads();
 #pragma unroll 1
-  for (int k = 3; k >= 0; --k) {
+  for (int k = NL - 1; k >= 0; --k) {
     const UnitLayer& Lk = U.L[k];
     const McfGeom g = mcf_geom(Lk.order);
     int tl = tid;
@@ -826,7 +841,8 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_inv_kernel(const UnitP
   }
 }
 
-static int unit_params(UnitParams& U, const ipoke_mcf_desc* d, int dtype, bool bwd) {
+// nl = 4: one unit; 8: two adjacent units of the same width and conditioning map in forward order (d[4 .. 7] = the upper unit)
+static int unit_params(UnitParams& U, const ipoke_mcf_desc* d, int dtype, bool bwd, int nl = 4) {
   IPK_REQUIRE(d, "null descriptor array");
   IPK_REQUIRE(dtype == IPOKE_BF16, "the fused MaCowUnit kernels take bf16 matrix-core inputs; f32 runs the per-layer kernels");
   const int C = d[0].C, ld = d[0].ld, Cc = d[0].Cc, B = d[0].B;
@@ -834,12 +850,13 @@ static int unit_params(UnitParams& U, const ipoke_mcf_desc* d, int dtype, bool b
   IPK_REQUIRE(Cc % 8 == 0 && Cc <= 128 && 4 * C + Cc <= kW2Steps * 32, "conditioning width: multiple of 8, <= 128, 4C + Cc <= 384");
   IPK_REQUIRE(B >= 1 && d[0].cond, "bad batch / null cond");
   std::memset(&U, 0, sizeof(U));
+  U.nl = nl;
   U.ld = ld; U.C = C; U.B = B; U.Cc = Cc; U.cond = d[0].cond;
   U.H = 4 * C; U.Cp = round_up(C, 32); U.K1p = 6 * U.Cp; U.K2p = round_up(U.H + Cc, 32); U.K3p = round_up(2 * C, 32);
   U.Hq = round_up(U.H, 32);
-  for (int k = 0; k < 4; ++k) {
+  for (int k = 0; k < nl; ++k) {
     const ipoke_mcf_desc& s = d[k];
-    IPK_REQUIRE(s.C == C && s.ld == ld && s.Cc == Cc && s.B == B && s.cond == d[0].cond, "the four layers of a unit share C, ld, cond, B");
+    IPK_REQUIRE(s.C == C && s.ld == ld && s.Cc == Cc && s.B == B && s.cond == d[0].cond, "the layers of a launch share C, ld, cond, B");
     IPK_REQUIRE(s.order >= 0 && s.order <= 3, "order is 0..3 (A..D)");
     IPK_REQUIRE((s.post_log_scale == nullptr) == (s.post_bias == nullptr), "fused ActNorm needs log_scale and bias");
     UnitLayer& L = U.L[k];
@@ -848,15 +865,15 @@ static int unit_params(UnitParams& U, const ipoke_mcf_desc* d, int dtype, bool b
     L.x = s.x; L.y_post = s.y_post; L.post_part = s.post_part; L.dparams_save = s.dparams_save; L.dc_save = s.dc_save;
     L.dbias_part = s.dbias_part; L.order = s.order; L.x_op = bwd ? s.x_op_save : nullptr;
     L.zc = bwd ? nullptr : s.zc_out; L.zc_off = s.zc_off; L.zc_stride = s.zc_stride; L.zc_cin = s.zc_cin; L.zc_ld = s.zc_ld;
-    if (L.zc) IPK_REQUIRE(k == 3 && (s.zc_stride == 1 || s.zc_stride == 2) && s.zc_cin >= 1 && s.zc_ld >= s.zc_cin && s.zc_ld % 2 == 0 && s.zc_off >= 0 &&
-                          s.zc_off + (s.zc_cin - 1) * s.zc_stride < C, "conditioning operand: layer 3 only, stride 1 or 2, columns inside the state");
+    if (L.zc) IPK_REQUIRE(k == nl - 1 && (s.zc_stride == 1 || s.zc_stride == 2) && s.zc_cin >= 1 && s.zc_ld >= s.zc_cin && s.zc_ld % 2 == 0 && s.zc_off >= 0 &&
+                          s.zc_off + (s.zc_cin - 1) * s.zc_stride < C, "conditioning operand: the launch's last layer only, stride 1 or 2, columns inside the state");
     if (!bwd) IPK_REQUIRE(s.W1 && s.W2 && s.bias2, "null forward operand");
     else {
       IPK_REQUIRE(s.W1T && s.W2T && s.x && s.a2_save && s.scale_save && s.dparams_save && s.dc_save, "null backward operand");
       IPK_REQUIRE(!s.post_log_scale || s.y_post, "the fused ActNorm backward needs the saved output");
     }
   }
-  U.x = d[0].x; U.dy = d[3].dy; U.dld = d[0].dld; U.dx = d[0].dx;
+  U.x = d[0].x; U.dy = d[nl - 1].dy; U.dld = d[0].dld; U.dx = d[0].dx;
   U.slot_w = d[0].rows_per_block > 0 ? 64 / d[0].rows_per_block : 1;
   if (d[0].split > 1) {
     IPK_REQUIRE(d[0].split == 2 || d[0].split == 4, "split: 1 (one workgroup per sample), 2 or 4");
@@ -877,34 +894,45 @@ extern "C" int ipoke_macow_unit_supported(int C, int Cc, int dtype) {
 
 extern "C" int64_t ipoke_macow_unit_xchg_bytes(int B, int split) {
   if (split <= 1 || B < 1) return 0;
-  return 256 + (int64_t)B * 4 * split * kUnitXchgStride * 8;
+  return 256 + (int64_t)B * kUnitMaxLayers * split * kUnitXchgStride * 8;      // (a two-unit launch: eight layers, each with granules of its own)
 }
 
-extern "C" int ipoke_macow_unit_fwd(const ipoke_mcf_desc* d4, int dtype, void* stream) {
+// Host-only rule: may two adjacent units of this shape run as ONE launch in this direction?  Forward / backward: the row-split kernels
+// only (the one-workgroup-per-sample kernels keep their four layers); the inverse kernel has no split.
+extern "C" int ipoke_macow_unit2_applicable(int C, int Cc, int dtype, int split, int direction) {
+  if (!ipoke_macow_unit_supported(C, Cc, dtype)) return 0;
+  if (direction == IPOKE_UNIT2_FWD || direction == IPOKE_UNIT2_BWD) return split == 2 || split == 4;
+  return direction == IPOKE_UNIT2_INV;
+}
+
+// (a two-unit launch opens its timing scope with units = 2: ipoke_timing_stop keeps reporting launches and a mean per UNIT)
+static int unit_fwd_impl(const ipoke_mcf_desc* d4, int dtype, void* stream, int nl) {
   UnitParams U;
-  int rc = unit_params(U, d4, dtype, false); if (rc) return rc;
-  IPK_REQUIRE(U.x && U.L[3].y, "null input / output state");
+  int rc = unit_params(U, d4, dtype, false, nl); if (rc) return rc;
+  IPK_REQUIRE(U.x && U.L[nl - 1].y, "null input / output state");
+  IPK_REQUIRE(nl == 4 || ipoke_macow_unit2_applicable(U.C, U.Cc, dtype, d4[0].split, IPOKE_UNIT2_FWD), "two units per launch: row-split launches only");
   const bool wide = U.Cp > 32;
   const size_t lds = (size_t)65 * (U.Cp * 2 + kTilePad) + (size_t)64 * ((wide ? 384 : 256) * 2 + kTilePad) + (size_t)64 * (2 * U.C + 4) * 4 +
                      (size_t)64 * U.C * 4 + (size_t)(8 * U.C + 8 * U.C + 8) * 4;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  TimedScope ts(IPOKE_TAG_UNIT_FWD, s);
+  TimedScope ts(IPOKE_TAG_UNIT_FWD, s, nl / 4);
   if (d4[0].split > 1) return unit_fwd_split_launch(U, d4[0].split, s);
   if (wide) {
     rc = ensure_lds<macow_unit_fwd_kernel<bf16_t, true>>(lds); if (rc) return rc;
-    hipLaunchKernelGGL((macow_unit_fwd_kernel<bf16_t, true>), dim3(U.B), dim3(kMcfThreads), lds, s, U);
+    hipLaunchKernelGGL((macow_unit_fwd_kernel<bf16_t, true>), dim3(U.B), dim3(kMcfThreads), lds, s, unit_params_narrow(U));
   } else {
     rc = ensure_lds<macow_unit_fwd_kernel<bf16_t, false>>(lds); if (rc) return rc;
-    hipLaunchKernelGGL((macow_unit_fwd_kernel<bf16_t, false>), dim3(U.B), dim3(kMcfThreads), lds, s, U);
+    hipLaunchKernelGGL((macow_unit_fwd_kernel<bf16_t, false>), dim3(U.B), dim3(kMcfThreads), lds, s, unit_params_narrow(U));
   }
   IPK_LAUNCH_CHECK();
   return IPOKE_OK;
 }
 
-extern "C" int ipoke_macow_unit_bwd(const ipoke_mcf_desc* d4, int dtype, void* stream) {
+static int unit_bwd_impl(const ipoke_mcf_desc* d4, int dtype, void* stream, int nl) {
   UnitParams U;
-  int rc = unit_params(U, d4, dtype, true); if (rc) return rc;
+  int rc = unit_params(U, d4, dtype, true, nl); if (rc) return rc;
   IPK_REQUIRE(U.dy && U.dld && U.dx, "null gradient tensor");
+  IPK_REQUIRE(nl == 4 || ipoke_macow_unit2_applicable(U.C, U.Cc, dtype, d4[0].split, IPOKE_UNIT2_BWD), "two units per launch: row-split launches only");
   std::memset(&U.pair, 0, sizeof(U.pair));
   if (d4[0].pair) {
     const ipoke_unit_pair_desc& q = *d4[0].pair;
@@ -924,39 +952,54 @@ extern "C" int ipoke_macow_unit_bwd(const ipoke_mcf_desc* d4, int dtype, void* s
   const size_t lds = dp_bytes + (size_t)65 * ((wide ? 256 : 128) * 2 + kTilePad) + (size_t)64 * CP * 4 + (2 * 4096 + 2 * 512) * 4;
   IPK_REQUIRE((size_t)64 * CP * 4 <= dp_bytes, "tap-half partials must fit the dparams tile");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  TimedScope ts(IPOKE_TAG_UNIT_BWD, s);
+  TimedScope ts(IPOKE_TAG_UNIT_BWD, s, nl / 4);
   if (d4[0].split > 1) return unit_bwd_split_launch(U, d4[0].split, s);
   if (wide) {
     rc = ensure_lds<macow_unit_bwd_kernel<bf16_t, true>>(lds); if (rc) return rc;
-    hipLaunchKernelGGL((macow_unit_bwd_kernel<bf16_t, true>), dim3(U.B), dim3(kMcfThreads), lds, s, U);
+    hipLaunchKernelGGL((macow_unit_bwd_kernel<bf16_t, true>), dim3(U.B), dim3(kMcfThreads), lds, s, unit_params_narrow(U));
   } else {
     rc = ensure_lds<macow_unit_bwd_kernel<bf16_t, false>>(lds); if (rc) return rc;
-    hipLaunchKernelGGL((macow_unit_bwd_kernel<bf16_t, false>), dim3(U.B), dim3(kMcfThreads), lds, s, U);
+    hipLaunchKernelGGL((macow_unit_bwd_kernel<bf16_t, false>), dim3(U.B), dim3(kMcfThreads), lds, s, unit_params_narrow(U));
   }
   IPK_LAUNCH_CHECK();
   return IPOKE_OK;
 }
 
-/* d4 in forward order; d4[3].x = the unit's OUTPUT state (input of the inverse), d4[0].y = the reconstructed unit input. */
-extern "C" int ipoke_macow_unit_inv(const ipoke_mcf_desc* d4, int dtype, void* stream) {
+/* d4 in forward order; d4[nl - 1].x = the OUTPUT state of the (upper) unit (input of the inverse), d4[0].y = the reconstructed input. */
+static int unit_inv_impl(const ipoke_mcf_desc* d4, int dtype, void* stream, int nl) {
   UnitParams U;
-  int rc = unit_params(U, d4, dtype, false); if (rc) return rc;
-  IPK_REQUIRE(U.L[3].x && U.L[0].y && U.L[3].x != U.L[0].y, "null / aliased state");
+  int rc = unit_params(U, d4, dtype, false, nl); if (rc) return rc;
+  IPK_REQUIRE(U.L[nl - 1].x && U.L[0].y && U.L[nl - 1].x != U.L[0].y, "null / aliased state");
+  IPK_REQUIRE(nl == 4 || ipoke_macow_unit2_applicable(U.C, U.Cc, dtype, 0, IPOKE_UNIT2_INV), "two units per launch: not for this shape");
   const bool wide = U.Cp > 32;
   const size_t lds = (size_t)2 * 65 * (U.Cp * 2 + kTilePad) + (size_t)2 * 16 * ((wide ? 384 : 256) * 2 + kTilePad) + (size_t)2 * 64 * U.Cc * 2 +
-                     (size_t)2 * 64 * U.C * 4 + (size_t)(8 * U.C + 8 * U.C) * 4;
+                     (size_t)2 * 64 * U.C * 4 + (size_t)nl * (2 * U.C + 2 * U.C) * 4;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int grid = (U.B + 1) / 2;
-  TimedScope ts(IPOKE_TAG_UNIT_INV, s);
-  // four masked-conv flows per sample: 64 positions x (6-tap shifted conv C -> 4C, 1x1 conv (4C + Cc) -> 2C); weights once, state in + out
-  ts.annotate(0, 4.0 * U.B * 64.0 * (64.0 * U.C * U.C + 4.0 * U.Cc * U.C), 4.0 * (32.0 * U.C * U.C + 2.0 * U.Cc * U.C) * 2.0 + 2.0 * U.B * 64.0 * U.C * 4.0);
-  if (wide) {
-    rc = ensure_lds<macow_unit_inv_kernel<bf16_t, true>>(lds); if (rc) return rc;
-    hipLaunchKernelGGL((macow_unit_inv_kernel<bf16_t, true>), dim3(grid), dim3(kMcfThreads), lds, s, U);
+  TimedScope ts(IPOKE_TAG_UNIT_INV, s, nl / 4);
+  // four masked-conv flows per sample and unit: 64 positions x (6-tap shifted conv C -> 4C, 1x1 conv (4C + Cc) -> 2C); weights once, state in + out
+  ts.annotate(0, (double)nl * U.B * 64.0 * (64.0 * U.C * U.C + 4.0 * U.Cc * U.C), (double)nl * (32.0 * U.C * U.C + 2.0 * U.Cc * U.C) * 2.0 + 2.0 * U.B * 64.0 * U.C * 4.0);
+  const UnitParams4 U4 = unit_params_narrow(U);       // a one-unit launch takes the four-layer argument block
+  if (wide && nl == 4) {
+    rc = ensure_lds<macow_unit_inv_kernel<bf16_t, true, 4>>(lds); if (rc) return rc;
+    hipLaunchKernelGGL((macow_unit_inv_kernel<bf16_t, true, 4>), dim3(grid), dim3(kMcfThreads), lds, s, U4);
+  } else if (wide) {
+    rc = ensure_lds<macow_unit_inv_kernel<bf16_t, true, kUnitMaxLayers>>(lds); if (rc) return rc;
+    hipLaunchKernelGGL((macow_unit_inv_kernel<bf16_t, true, kUnitMaxLayers>), dim3(grid), dim3(kMcfThreads), lds, s, U);
+  } else if (nl == 4) {
+    rc = ensure_lds<macow_unit_inv_kernel<bf16_t, false, 4>>(lds); if (rc) return rc;
+    hipLaunchKernelGGL((macow_unit_inv_kernel<bf16_t, false, 4>), dim3(grid), dim3(kMcfThreads), lds, s, U4);
   } else {
-    rc = ensure_lds<macow_unit_inv_kernel<bf16_t, false>>(lds); if (rc) return rc;
-    hipLaunchKernelGGL((macow_unit_inv_kernel<bf16_t, false>), dim3(grid), dim3(kMcfThreads), lds, s, U);
+    rc = ensure_lds<macow_unit_inv_kernel<bf16_t, false, kUnitMaxLayers>>(lds); if (rc) return rc;
+    hipLaunchKernelGGL((macow_unit_inv_kernel<bf16_t, false, kUnitMaxLayers>), dim3(grid), dim3(kMcfThreads), lds, s, U);
   }
   IPK_LAUNCH_CHECK();
   return IPOKE_OK;
 }
+
+extern "C" int ipoke_macow_unit_fwd(const ipoke_mcf_desc* d4, int dtype, void* stream) { return unit_fwd_impl(d4, dtype, stream, 4); }
+extern "C" int ipoke_macow_unit_bwd(const ipoke_mcf_desc* d4, int dtype, void* stream) { return unit_bwd_impl(d4, dtype, stream, 4); }
+extern "C" int ipoke_macow_unit_inv(const ipoke_mcf_desc* d4, int dtype, void* stream) { return unit_inv_impl(d4, dtype, stream, 4); }
+extern "C" int ipoke_macow_unit2_fwd(const ipoke_mcf_desc* d8, int dtype, void* stream) { return unit_fwd_impl(d8, dtype, stream, kUnitMaxLayers); }
+extern "C" int ipoke_macow_unit2_bwd(const ipoke_mcf_desc* d8, int dtype, void* stream) { return unit_bwd_impl(d8, dtype, stream, kUnitMaxLayers); }
+extern "C" int ipoke_macow_unit2_inv(const ipoke_mcf_desc* d8, int dtype, void* stream) { return unit_inv_impl(d8, dtype, stream, kUnitMaxLayers); }

@@ -1,6 +1,7 @@
 // Shared device-side definitions of the fused MaCowUnit kernels (mcf_unit.hip: one workgroup per sample; mcf_unit_split.hip:
 // a sample's 8x8 latent split by rows over 2 or 4 workgroups that exchange halo rows inside the launch).
 #pragma once
+#include <cstddef>
 #include <cstring>
 #include <type_traits>
 
@@ -29,23 +30,38 @@ struct UnitPair {
   const float* x0; const float* scale; void* dparams; float* dbias_part; float* dx;
   int Cp, t_off, t_stride, ldp, on;
 };
-struct UnitParams {
-  UnitLayer L[4];
+static constexpr int kUnitMaxLayers = 8;           // one launch runs one MaCowUnit (4 layers) or two adjacent units of equal width (8)
+// NLMAX = 4: the argument block of a one-unit launch (what every launch took before the two-unit form: a four-layer launch must not
+// pay for the larger block -- measured: 200 inverse launches of c5 with the eight-layer block cost 0.27 ms); NLMAX = 8: a two-unit launch
+template <int NLMAX> struct UnitParamsT {
+  UnitLayer L[NLMAX];
+  int nl;                                          // layers of this launch: 4 or 8 (<= NLMAX)
   const float* x; const void* cond; const float* dy; const float* dld; float* dx;
   int ld, C, B, Cc, H, Cp, K1p, K2p, K3p, Hq, slot_w;
   unsigned long long* xchg; int xchg_stride;       // row-split launches (mcf_unit_split.hip): granule scratch, granules per (sample, layer, part)
   UnitPair pair;                                   // row-split backward only
 };
+typedef UnitParamsT<kUnitMaxLayers> UnitParams;    // what the host assembles
+typedef UnitParamsT<4> UnitParams4;
+inline UnitParams4 unit_params_narrow(const UnitParams& U) {       // the first four layers + everything behind the layer table
+  UnitParams4 u;
+  static_assert(sizeof(UnitParams) - offsetof(UnitParams, nl) == sizeof(UnitParams4) - offsetof(UnitParams4, nl), "same tail");
+  std::memcpy(&u, &U, 4 * sizeof(UnitLayer));
+  std::memcpy(reinterpret_cast<char*>(&u) + offsetof(UnitParams4, nl), reinterpret_cast<const char*>(&U) + offsetof(UnitParams, nl),
+              sizeof(UnitParams4) - offsetof(UnitParams4, nl));
+  return u;
+}
 
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
-// The unit kernels take ~800 bytes of arguments (four layers of pointers), which hipcc fetches lazily: an s_load next to each first
-// use, each behind an s_waitcnt.  The argument block of a launch is cold (the command processor has just written it), so that every
-// first touch of a 64-byte line is a memory round trip of ~0.3 us and the prologue was a CHAIN of a dozen of them (stamps: 8 800
-// cycles from entry to the staged tiles, no vector load waiting).  One dword of every line requested back to back at entry: one
-// round trip, after which the compiler's own loads hit the scalar cache.
+// The unit kernels take ~0.9 KB (one unit) or ~1.6 KB (two units) of arguments, layer after layer of pointers, which hipcc fetches lazily:
+// an s_load next to each first use, each behind an s_waitcnt.  The argument block of a launch is cold (the command processor has just
+// written it), so that every first touch of a 64-byte line is a memory round trip of ~0.3 us and the prologue was a CHAIN of a dozen of
+// them (stamps: 8 800 cycles from entry to the staged tiles, no vector load waiting).  One dword of every line of the layer table
+// requested back to back at entry: one round trip, after which the compiler's own loads hit the scalar cache.
+template <int NLMAX>
 __device__ __forceinline__ void unit_kernarg_prefetch() {
   const auto ka = __builtin_amdgcn_kernarg_segment_ptr();
   unsigned d0, d1, d2, d3, d4, d5, d6, d7, d8, d9, d10, d11, d12;
@@ -59,7 +75,27 @@ __device__ __forceinline__ void unit_kernarg_prefetch() {
       : "s"(ka)
       : "memory");
 }
-static_assert(sizeof(UnitParams) >= 0x304, "unit_kernarg_prefetch reads one dword of every 64-byte line up to 0x300");
+template <>
+__device__ __forceinline__ void unit_kernarg_prefetch<kUnitMaxLayers>() {
+  const auto ka = __builtin_amdgcn_kernarg_segment_ptr();
+  unsigned d0, d1, d2, d3, d4, d5, d6, d7, d8, d9, d10, d11, d12, d13, d14, d15, d16, d17, d18, d19, d20, d21, d22, d23, d24, d25;
+  asm volatile(
+      "s_load_dword %0, %26, 0x0\n\ts_load_dword %1, %26, 0x40\n\ts_load_dword %2, %26, 0x80\n\ts_load_dword %3, %26, 0xc0\n\t"
+      "s_load_dword %4, %26, 0x100\n\ts_load_dword %5, %26, 0x140\n\ts_load_dword %6, %26, 0x180\n\ts_load_dword %7, %26, 0x1c0\n\t"
+      "s_load_dword %8, %26, 0x200\n\ts_load_dword %9, %26, 0x240\n\ts_load_dword %10, %26, 0x280\n\ts_load_dword %11, %26, 0x2c0\n\t"
+      "s_load_dword %12, %26, 0x300\n\ts_load_dword %13, %26, 0x340\n\ts_load_dword %14, %26, 0x380\n\ts_load_dword %15, %26, 0x3c0\n\t"
+      "s_load_dword %16, %26, 0x400\n\ts_load_dword %17, %26, 0x440\n\ts_load_dword %18, %26, 0x480\n\ts_load_dword %19, %26, 0x4c0\n\t"
+      "s_load_dword %20, %26, 0x500\n\ts_load_dword %21, %26, 0x540\n\ts_load_dword %22, %26, 0x580\n\ts_load_dword %23, %26, 0x5c0\n\t"
+      "s_load_dword %24, %26, 0x600\n\ts_load_dword %25, %26, 0x640\n\ts_waitcnt lgkmcnt(0)"
+      : "=&s"(d0), "=&s"(d1), "=&s"(d2), "=&s"(d3), "=&s"(d4), "=&s"(d5), "=&s"(d6), "=&s"(d7), "=&s"(d8), "=&s"(d9), "=&s"(d10), "=&s"(d11),
+        "=&s"(d12), "=&s"(d13), "=&s"(d14), "=&s"(d15), "=&s"(d16), "=&s"(d17), "=&s"(d18), "=&s"(d19), "=&s"(d20), "=&s"(d21), "=&s"(d22),
+        "=&s"(d23), "=&s"(d24), "=&s"(d25)
+      : "s"(ka)
+      : "memory");
+}
+static_assert(sizeof(UnitParams4) >= 0x304, "unit_kernarg_prefetch<4> reads one dword of every 64-byte line up to 0x300");
+static_assert(sizeof(UnitParams) >= 0x644 && sizeof(UnitParams) <= 0x680,
+              "unit_kernarg_prefetch<8> reads one dword of every 64-byte line of the argument block, up to 0x640");
 
 // Weight fragments are fetched through buffer descriptors: the base lives in SGPRs, every lane needs ONE 32-bit byte offset
 // per fragment column (instead of a 64-bit address per fragment, which the compiler kept live across the layer loop and
@@ -92,8 +128,8 @@ template <bool WIDE> struct UC {
 
 // Operands are stored fragment-tiled (prep.hip: tiled_offset): fragment (row block rb, K step ks) of a matrix with nks steps
 // per row is the KB at (rb * nks + ks) KB, lane l at byte 16 l.
-template <typename T, bool WIDE>
-__device__ __forceinline__ void unit_load_w1(McfW<T>& w, const void* W1, const UnitParams& U) {
+template <typename T, bool WIDE, typename P>
+__device__ __forceinline__ void unit_load_w1(McfW<T>& w, const void* W1, const P& U) {
   constexpr int KS = K64<T>::value;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nks = U.K1p / KS;
@@ -110,8 +146,8 @@ __device__ __forceinline__ void unit_load_w1(McfW<T>& w, const void* W1, const U
       for (int j = 0; j < UC<WIDE>::J1; ++j) w.w1[tap][st][j] = buf_frag<T>(rs, voff[j], soff);
     }
 }
-template <typename T, bool WIDE>
-__device__ __forceinline__ void unit_load_w2(McfW<T>& w, const void* W2, const UnitParams& U) {
+template <typename T, bool WIDE, typename P>
+__device__ __forceinline__ void unit_load_w2(McfW<T>& w, const void* W2, const P& U) {
   constexpr int KS = K64<T>::value;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n2 = U.K2p / KS;
@@ -142,7 +178,7 @@ __device__ __forceinline__ float fast_elu(float x) { return x > 0.f ? x : __expf
 __device__ __forceinline__ float fast_scale(float s) { return __fdividef(2.f, 1.f + __expf(-s)); }
 
 // row-split launches (mcf_unit_split.hip); S = 2 or 4 workgroups per sample.  Exchange scratch: 256 bytes of header, then per
-// (sample, layer, consumer part) kUnitXchgStride 8-byte granules = [4 halo rows][8 columns][128 value pairs]
+// (sample, layer of the launch, consumer part) kUnitXchgStride 8-byte granules = [4 halo rows][8 columns][128 value pairs]
 static constexpr int kUnitXchgStride = 4 * 8 * 128;
 int unit_fwd_split_launch(const UnitParams& U, int S, hipStream_t s);
 int unit_bwd_split_launch(const UnitParams& U, int S, hipStream_t s);

@@ -36,9 +36,10 @@ static constexpr int kXchgHeader = 32;                // granules (256 B): word 
 __device__ __forceinline__ int rows_above(const McfGeom& g) { return g.oy < 0 ? -g.oy : 0; }                       // A 2, B 0, C / D 1
 __device__ __forceinline__ int rows_below(const McfGeom& g) { const int m = g.kh - 1 + g.oy; return m > 0 ? m : 0; }  // A 0, B 2, C / D 1
 
-// granules of (sample b, layer k, consumer part s): [4 halo rows: 0, 1 above / 2, 3 below the consumer][8 columns][pw pairs]
-__device__ __forceinline__ gu64* xg_region(const UnitParams& U, int b, int k, int S, int s) {
-  return reinterpret_cast<gu64*>(reinterpret_cast<unsigned long long>(U.xchg)) + kXchgHeader + (((long)b * 4 + k) * S + s) * (long)U.xchg_stride;
+// granules of (sample b, layer k of the launch's U.nl, consumer part s): [4 halo rows: 0, 1 above / 2, 3 below the consumer][8 columns][pw pairs]
+template <typename P>
+__device__ __forceinline__ gu64* xg_region(const P& U, int b, int k, int S, int s) {
+  return reinterpret_cast<gu64*>(reinterpret_cast<unsigned long long>(U.xchg)) + kXchgHeader + (((long)b * U.nl + k) * S + s) * (long)U.xchg_stride;
 }
 __device__ __forceinline__ void xg_store(gu64* g, unsigned value) {
   __hip_atomic_store(g, (1ull << 32) | value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -68,8 +69,8 @@ __device__ __forceinline__ void halo_begin(Halo<NI>& h, gu64* reg, int s, int nu
   for (int i = 0; i < NI; ++i)
     if (h.gp[i]) h.v[i] = __hip_atomic_load(h.gp[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-template <int NI>
-__device__ __forceinline__ void halo_end(const UnitParams& U, Halo<NI>& h) {
+template <int NI, typename P>
+__device__ __forceinline__ void halo_end(const P& U, Halo<NI>& h) {
   unsigned spins = 0;
   for (;;) {
     bool ok = true;
@@ -185,12 +186,12 @@ __device__ __forceinline__ void split_gemm2(const unsigned char* a2, int a2_pitc
   }
 }
 
-template <typename T, bool WIDE, int S>
-__global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_split_kernel(const UnitParams U) {
+template <typename T, bool WIDE, int S, int NLMAX>
+__global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_split_kernel(const UnitParamsT<NLMAX> U) {
   constexpr int RY = 8 / S, R = 64 / S, MT = 4 / S;
   constexpr int KS = K64<T>::value;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unit_kernarg_prefetch();
+  unit_kernarg_prefetch<NLMAX>();
   const int b = blockIdx.x / S, s = blockIdx.x - b * S, tid = threadIdx.x;
   const int y0 = s * RY, p0 = y0 * 8;
   McfW<T> wr;
@@ -203,9 +204,10 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_split_kernel(const
   const int prm_ld = N2 + 4;
   float* prm = reinterpret_cast<float*>(a2 + R * a2_pitch);        // [R][2C (+4)] raw (mu, s)
   float* xf = prm + R * prm_ld;                                    // [R][C] fp32 state of the own rows
-  float* bias_s = xf + R * C;                                      // [4][2C]
-  float* post_s = bias_s + 4 * N2;                                 // [4][2][C]
-  float* red = post_s + 8 * C;                                     // [8 waves][4 layers]
+  const int NL = NLMAX == 4 ? 4 : U.nl;                            // 4: one unit, 8: two units back to back (the second one's input never leaves LDS)
+  float* bias_s = xf + R * C;                                      // [NL][2C]
+  float* post_s = bias_s + NL * N2;                                // [NL][2][C]
+  float* red = post_s + NL * 2 * C;                                // [8 waves][NL layers]
   const long row0 = (long)b * 64;
   const int G2 = C >> 1;
   const float inv_g2 = 1.f / (float)G2;
@@ -233,31 +235,47 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_split_kernel(const
     if (e < R * cchunks) cin[i] = *reinterpret_cast<const u32x4*>(condp + (long)(e / cchunks) * U.Cc + (e % cchunks) * E16c);
   }
   // (static layer index: the pointers are uniform kernel arguments -- indexed per lane they become vector loads of the argument
-  //  block followed by s_waitcnt vmcnt(0), i.e. dependent memory round trips in front of the weight requests)
-  float bias_v = 0.f, post_e = 0.f, post_b = 0.f;
-  bool post_on = false;
+  //  block followed by s_waitcnt vmcnt(0), i.e. dependent memory round trips in front of the weight requests;
+  //  4 x 2C <= 512 threads: one round per unit of the launch)
+  float bias_v[2] = {0.f, 0.f}, post_e[2] = {0.f, 0.f}, post_b[2] = {0.f, 0.f};
+  bool post_on[2] = {false, false};
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    if (tid >= q * N2 && tid < (q + 1) * N2) bias_v = U.L[q].bias2[tid - q * N2];
-    if (U.L[q].post_ls && tid >= q * C && tid < (q + 1) * C) {
-      post_e = U.L[q].post_ls[tid - q * C]; post_b = U.L[q].post_bias[tid - q * C]; post_on = true;
+  for (int u = 0; u < 2; ++u) {
+    if (u * 4 < NL) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const UnitLayer& Lq = U.L[u * 4 + q < NLMAX ? u * 4 + q : q];
+        if (tid >= q * N2 && tid < (q + 1) * N2) bias_v[u] = Lq.bias2[tid - q * N2];
+        if (Lq.post_ls && tid >= q * C && tid < (q + 1) * C) {
+          post_e[u] = Lq.post_ls[tid - q * C]; post_b[u] = Lq.post_bias[tid - q * C]; post_on[u] = true;
+        }
+      }
     }
   }
   unit_load_w1<T, WIDE>(wr, U.L[0].W1, U);
   unit_load_w2<T, WIDE>(wr, U.L[0].W2, U);
   for (int i = tid; i < (65 * xs_pitch + R * a2_pitch) / 16; i += kMcfThreads) reinterpret_cast<u32x4*>(smem)[i] = u32x4{0u, 0u, 0u, 0u};
-  if (U.L[3].y && ld > C) {
+  if (ld > C) {                                     // pass-through channels: to every unit's output state that is stored
+    float* const yo[2] = {U.L[3].y, NL > 4 ? U.L[NLMAX - 1].y : nullptr};
     const int R2 = (ld - C) >> 1;
-    for (int e = tid; e < R * R2; e += kMcfThreads) {
-      const int p = p0 + e / R2, c = C + (e % R2) * 2;
-      *reinterpret_cast<f32x2*>(U.L[3].y + (row0 + p) * ld + c) = *reinterpret_cast<const f32x2*>(U.x + (row0 + p) * ld + c);
-    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+      if (yo[u])
+        for (int e = tid; e < R * R2; e += kMcfThreads) {
+          const int p = p0 + e / R2, c = C + (e % R2) * 2;
+          *reinterpret_cast<f32x2*>(yo[u] + (row0 + p) * ld + c) = *reinterpret_cast<const f32x2*>(U.x + (row0 + p) * ld + c);
+        }
   }
   __syncthreads();
-  if (tid < 4 * N2) bias_s[tid] = bias_v;
-  if (tid < 4 * C) {
-    post_s[(tid / C) * 2 * C + tid % C] = post_on ? __expf(post_e) : 1.f;
-    post_s[(tid / C) * 2 * C + C + tid % C] = post_b;
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    if (u * 4 < NL) {
+      if (tid < 4 * N2) bias_s[u * 4 * N2 + tid] = bias_v[u];
+      if (tid < 4 * C) {
+        post_s[(u * 4 + tid / C) * 2 * C + tid % C] = post_on[u] ? __expf(post_e[u]) : 1.f;
+        post_s[(u * 4 + tid / C) * 2 * C + C + tid % C] = post_b[u];
+      }
+    }
   }
 #pragma unroll
   for (int i = 0; i < NCI; ++i) {
@@ -277,19 +295,19 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_split_kernel(const
     }
   }
   __syncthreads();
-  float ld_k[4] = {0.f, 0.f, 0.f, 0.f};        // per-thread log-det partials of the four layers, summed over the workgroup at the end
 #pragma unroll 1
-  for (int k = 0; k < 4; ++k) {
+  for (int k = 0; k < NL; ++k) {
     const UnitLayer& Lk = U.L[k];
     const McfGeom g = mcf_geom(Lk.order);
     int tl = tid;
     asm volatile("" : "+v"(tl));
     const int lane = tl & 63, wave = tl >> 6;
-    const int kn = k < 3 ? k + 1 : 3, soff_bias = k < 3 ? 0 : kOob;
+    const bool more = k + 1 < NL;                 // "no next layer" = the LAUNCH's last layer: a second unit's weights arrive under the first one's layer D
+    const int kn = more ? k + 1 : k, soff_bias = more ? 0 : kOob;
     const rsrc_t rs1n = make_rsrc(U.L[kn].W1, ((U.H + 15) & ~15) * U.K1p * (int)sizeof(T));
     const rsrc_t rs2 = make_rsrc(Lk.W2, ((2 * C + 15) & ~15) * U.K2p * (int)sizeof(T));
     const rsrc_t rs2n = make_rsrc(U.L[kn].W2, ((2 * C + 15) & ~15) * U.K2p * (int)sizeof(T));
-    // halo rows of this layer's input that live in the neighbouring parts (layer 0: staged from global memory above)
+    // halo rows of this layer's input that live in the neighbouring parts (the launch's layer 0: staged from global memory above)
     const int nu = (k > 0 && s > 0) ? rows_above(g) : 0, nd = (k > 0 && s < S - 1) ? rows_below(g) : 0;
     if constexpr (MT == 2) {
       // the tile next to the part boundary waits for the halo, the other one runs first (S = 2: one neighbour)
@@ -347,8 +365,8 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_split_kernel(const
     const float* bk = bias_s + k * N2;
     const float* pe = post_s + k * 2 * C;
     const McfGeom gn = mcf_geom(U.L[kn].order);
-    const int to_up = (k < 3 && s > 0) ? rows_below(gn) : 0;          // the part above reads my top rows
-    const int to_dn = (k < 3 && s < S - 1) ? rows_above(gn) : 0;      // the part below reads my bottom rows
+    const int to_up = (more && s > 0) ? rows_below(gn) : 0;           // the part above reads my top rows
+    const int to_dn = (more && s < S - 1) ? rows_above(gn) : 0;       // the part below reads my bottom rows
     gu64* reg_up = xg_region(U, b, kn, S, s > 0 ? s - 1 : 0);
     gu64* reg_dn = xg_region(U, b, kn, S, s < S - 1 ? s + 1 : 0);
     {
@@ -393,8 +411,10 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_split_kernel(const
         }
       }
     }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) ld_k[q] += q == k ? ld_acc : 0.f;
+    {   // this layer's log-det: per-wave sum now, the sum over the waves once behind the loop
+      const float ws = wave_sum(ld_acc);
+      if (lane == 0) red[wave * NL + k] = ws;
+    }
     reload_w1<T, WIDE, 5, 6>(wr, rs1n, lane, wave, nks, soff_bias);                      // (behind the coupling's stores and hand-off granules)
     reload_w2<T, WIDE, 0, 4>(wr, rs2n, lane, wave, n2, soff_bias);
     __syncthreads();                              // the state update above is complete
@@ -414,19 +434,15 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_fwd_split_kernel(const
       }
     }
   }
-  // log-dets: one reduction for the four layers (off every layer's critical path)
-#pragma unroll
-  for (int q = 0; q < 4; ++q) ld_k[q] = wave_sum(ld_k[q]);
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) red[(tid >> 6) * 4 + q] = ld_k[q];
-  }
+  // log-dets: the waves' sums of every layer meet here (off every layer's critical path); one slot per layer
   __syncthreads();
-  if (tid < 4) {
+  if (tid < NL) {
     float t = 0.f;
 #pragma unroll
-    for (int w = 0; w < kMcfWaves; ++w) t += red[w * 4 + tid];
-    float* slot = tid == 0 ? U.L[0].ld_slot : tid == 1 ? U.L[1].ld_slot : tid == 2 ? U.L[2].ld_slot : U.L[3].ld_slot;
+    for (int w = 0; w < kMcfWaves; ++w) t += red[w * NL + tid];
+    float* slot = nullptr;
+#pragma unroll
+    for (int q = 0; q < NLMAX; ++q) slot = tid == q ? U.L[q].ld_slot : slot;
     if (slot) slot[(long)b * U.slot_w + s] = t;
   }
 }
@@ -436,14 +452,21 @@ static int fwd_split_launch_s(const UnitParams& U, hipStream_t s) {
   const bool wide = U.Cp > 32;
   const int R = 64 / S;
   const size_t lds = (size_t)65 * (U.Cp * 2 + kTilePad) + (size_t)R * ((wide ? 384 : 256) * 2 + kTilePad) + (size_t)R * (2 * U.C + 4) * 4 +
-                     (size_t)R * U.C * 4 + (size_t)(8 * U.C + 8 * U.C + 32) * 4;
+                     (size_t)R * U.C * 4 + (size_t)U.nl * (2 * U.C + 2 * U.C + 8) * 4;
   int rc;
-  if (wide) {
-    rc = ensure_lds<macow_unit_fwd_split_kernel<bf16_t, true, S>>(lds); if (rc) return rc;
-    hipLaunchKernelGGL((macow_unit_fwd_split_kernel<bf16_t, true, S>), dim3(U.B * S), dim3(kMcfThreads), lds, s, U);
+  const UnitParams4 U4 = unit_params_narrow(U);       // a one-unit launch takes the four-layer argument block
+  if (wide && U.nl == 4) {
+    rc = ensure_lds<macow_unit_fwd_split_kernel<bf16_t, true, S, 4>>(lds); if (rc) return rc;
+    hipLaunchKernelGGL((macow_unit_fwd_split_kernel<bf16_t, true, S, 4>), dim3(U.B * S), dim3(kMcfThreads), lds, s, U4);
+  } else if (wide) {
+    rc = ensure_lds<macow_unit_fwd_split_kernel<bf16_t, true, S, kUnitMaxLayers>>(lds); if (rc) return rc;
+    hipLaunchKernelGGL((macow_unit_fwd_split_kernel<bf16_t, true, S, kUnitMaxLayers>), dim3(U.B * S), dim3(kMcfThreads), lds, s, U);
+  } else if (U.nl == 4) {
+    rc = ensure_lds<macow_unit_fwd_split_kernel<bf16_t, false, S, 4>>(lds); if (rc) return rc;
+    hipLaunchKernelGGL((macow_unit_fwd_split_kernel<bf16_t, false, S, 4>), dim3(U.B * S), dim3(kMcfThreads), lds, s, U4);
   } else {
-    rc = ensure_lds<macow_unit_fwd_split_kernel<bf16_t, false, S>>(lds); if (rc) return rc;
-    hipLaunchKernelGGL((macow_unit_fwd_split_kernel<bf16_t, false, S>), dim3(U.B * S), dim3(kMcfThreads), lds, s, U);
+    rc = ensure_lds<macow_unit_fwd_split_kernel<bf16_t, false, S, kUnitMaxLayers>>(lds); if (rc) return rc;
+    hipLaunchKernelGGL((macow_unit_fwd_split_kernel<bf16_t, false, S, kUnitMaxLayers>), dim3(U.B * S), dim3(kMcfThreads), lds, s, U);
   }
   IPK_LAUNCH_CHECK();
   return IPOKE_OK;
@@ -451,6 +474,7 @@ static int fwd_split_launch_s(const UnitParams& U, hipStream_t s) {
 
 int unit_fwd_split_launch(const UnitParams& U, int S, hipStream_t s) {
   IPK_REQUIRE(U.xchg != nullptr && U.xchg_stride >= 4 * 8 * 32, "row-split unit launch without exchange scratch");
+  IPK_REQUIRE(U.nl == 4 || U.nl == kUnitMaxLayers, "a row-split launch runs one unit or two");
   IPK_REQUIRE(U.slot_w >= S, "log-det slot narrower than the split");
   if (S == 2) return fwd_split_launch_s<2>(U, s);
   if (S == 4) return fwd_split_launch_s<4>(U, s);
@@ -465,15 +489,15 @@ int unit_fwd_split_launch(const UnitParams& U, int S, hipStream_t s) {
 // rows a neighbour needs leave as granules from the epilogue of (b) (a lane's four hidden channels = two granules = one 16-byte
 // write-through store); (c) runs the tile that does not touch the cut first, sweeps the halo, then the tile at the cut.
 // Parameter-gradient partials: one row per part (row b * S + s of dbias_part / post_part).
-template <typename T, bool WIDE, int S>
-__global__ __launch_bounds__(kMcfThreads) void macow_unit_bwd_split_kernel(const UnitParams U) {
+template <typename T, bool WIDE, int S, int NLMAX>
+__global__ __launch_bounds__(kMcfThreads) void macow_unit_bwd_split_kernel(const UnitParamsT<NLMAX> U) {
   constexpr int RY = 8 / S, R = 64 / S, MT = 4 / S;
   constexpr int J1 = UC<WIDE>::J1, N3S = UC<WIDE>::N3S, HS = UC<WIDE>::HS;
   constexpr int KS = K64<T>::value, E16 = ET<T>::E16;
   typedef typename ET<T>::frag frag_t;
   typedef typename Pack4<T>::type pack_t;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unit_kernarg_prefetch();
+  unit_kernarg_prefetch<NLMAX>();
   const int b = blockIdx.x / S, s = blockIdx.x - b * S, tid = threadIdx.x;
   const int y0 = s * RY, p0 = y0 * 8;
   const int lane = tid & 63, wave = tid >> 6, r = lane & 15, gq = lane >> 4;
@@ -539,7 +563,8 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_bwd_split_kernel(const
     if (e < R * G2) gin[i] = *reinterpret_cast<const f32x2*>(U.dy + (rowp + p) * ld + c);
   }
   const float g_ld = U.dld[b];
-  load_w2t(U.L[3]); load_cact(U.L[3]); load_w1t(U.L[3]);
+  const int NL = NLMAX == 4 ? 4 : U.nl;                           // 4: one unit, 8: two units (the gradient between them stays in gb)
+  load_w2t(U.L[NL - 1]); load_cact(U.L[NL - 1]); load_w1t(U.L[NL - 1]);
   for (int i = tid; i < (R * dp_pitch + 65 * dc_pitch) / 16; i += kMcfThreads) reinterpret_cast<u32x4*>(smem)[i] = u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
   for (int i = 0; i < NIT; ++i) {
@@ -559,7 +584,7 @@ __global__ __launch_bounds__(kMcfThreads) void macow_unit_bwd_split_kernel(const
   const rsrc_t rs_x = make_rsrc(U.xchg, 0x7ffffff0);              // granule stores (16 bytes = two granules, write-through)
   __syncthreads();
 #pragma unroll 1
-  for (int k = 3; k >= 0; --k) {
+  for (int k = NL - 1; k >= 0; --k) {
     const UnitLayer& Lk = U.L[k];
     const McfGeom g = mcf_geom(Lk.order);
     int tl = tid;
@@ -891,12 +916,19 @@ static int bwd_split_launch_s(const UnitParams& U, hipStream_t s) {
   const size_t lds = dp_bytes + (size_t)65 * ((wide ? 256 : 128) * 2 + kTilePad) + (size_t)R * CP * 4 + (2 * 4096 + 2 * 512) * 4;
   IPK_REQUIRE((size_t)R * CP * 4 <= dp_bytes, "tap-half partials must fit the dparams tile");
   int rc;
-  if (wide) {
-    rc = ensure_lds<macow_unit_bwd_split_kernel<bf16_t, true, S>>(lds); if (rc) return rc;
-    hipLaunchKernelGGL((macow_unit_bwd_split_kernel<bf16_t, true, S>), dim3(U.B * S), dim3(kMcfThreads), lds, s, U);
+  const UnitParams4 U4 = unit_params_narrow(U);
+  if (wide && U.nl == 4) {
+    rc = ensure_lds<macow_unit_bwd_split_kernel<bf16_t, true, S, 4>>(lds); if (rc) return rc;
+    hipLaunchKernelGGL((macow_unit_bwd_split_kernel<bf16_t, true, S, 4>), dim3(U.B * S), dim3(kMcfThreads), lds, s, U4);
+  } else if (wide) {
+    rc = ensure_lds<macow_unit_bwd_split_kernel<bf16_t, true, S, kUnitMaxLayers>>(lds); if (rc) return rc;
+    hipLaunchKernelGGL((macow_unit_bwd_split_kernel<bf16_t, true, S, kUnitMaxLayers>), dim3(U.B * S), dim3(kMcfThreads), lds, s, U);
+  } else if (U.nl == 4) {
+    rc = ensure_lds<macow_unit_bwd_split_kernel<bf16_t, false, S, 4>>(lds); if (rc) return rc;
+    hipLaunchKernelGGL((macow_unit_bwd_split_kernel<bf16_t, false, S, 4>), dim3(U.B * S), dim3(kMcfThreads), lds, s, U4);
   } else {
-    rc = ensure_lds<macow_unit_bwd_split_kernel<bf16_t, false, S>>(lds); if (rc) return rc;
-    hipLaunchKernelGGL((macow_unit_bwd_split_kernel<bf16_t, false, S>), dim3(U.B * S), dim3(kMcfThreads), lds, s, U);
+    rc = ensure_lds<macow_unit_bwd_split_kernel<bf16_t, false, S, kUnitMaxLayers>>(lds); if (rc) return rc;
+    hipLaunchKernelGGL((macow_unit_bwd_split_kernel<bf16_t, false, S, kUnitMaxLayers>), dim3(U.B * S), dim3(kMcfThreads), lds, s, U);
   }
   IPK_LAUNCH_CHECK();
   return IPOKE_OK;
@@ -904,6 +936,7 @@ static int bwd_split_launch_s(const UnitParams& U, hipStream_t s) {
 
 int unit_bwd_split_launch(const UnitParams& U, int S, hipStream_t s) {
   IPK_REQUIRE(U.xchg != nullptr && U.xchg_stride >= 4 * 8 * 128, "row-split unit launch without exchange scratch");
+  IPK_REQUIRE(U.nl == 4 || U.nl == kUnitMaxLayers, "a row-split launch runs one unit or two");
   if (S == 2) return bwd_split_launch_s<2>(U, s);
   if (S == 4) return bwd_split_launch_s<4>(U, s);
   IPK_REQUIRE(false, "split must be 2 or 4");

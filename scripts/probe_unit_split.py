@@ -1,6 +1,8 @@
 """Developer probe: the row-split MaCowUnit kernels (csrc/mcf_unit_split.hip) against the one-workgroup-per-sample kernels --
 bit-identity of every output on random operands, repeated with a copy stream running beside them, and isolated timing with
-rotating (L2-cold) weight sets.  usage: probe_unit_split.py [C] [B] [fwd|both]"""
+rotating (L2-cold) weight sets.  usage: probe_unit_split.py [C] [B] [fwd|both|double]
+double: two adjacent units as two four-layer launches against one eight-layer launch (ipoke_macow_unit2_*), back to back, HIP events:
+forward and backward at split 4, the inverse at B = 32."""
 import os
 import sys
 
@@ -143,7 +145,87 @@ def timing(C, B, n=240, bwd=True):
         print(f"timing C={C} B={B} split={S}: " + "  ".join(f"{t:.1f} us" for t in res) + f"  (fwd{', bwd' if bwd else ''}; timeouts {int(o['xchg'][0].item())})")
 
 
+def double_timing(C, B, B_inv=32, S=4, n=240, rounds=5):
+    """per PAIR of units (us): two four-layer launches / one eight-layer launch; rotating weight sets; median and fastest of `rounds`"""
+    NU = 24
+
+    def pair_descs(cs, o, u, S_, inv=False):
+        """d8 of the units (u, u + 1) over 8-layer buffers `o`; its halves are the two four-layer calls"""
+        d8 = (_lib.McfDesc * 8)()
+        for k in range(8):
+            d, w = d8[k], cs.W[u + k // 4][k % 4]
+            d.ld, d.C, d.B, d.cond, d.Cc, d.order, d.rows_per_block = cs.ld, cs.C, cs.B, cs.cond.data_ptr(), 128, k % 4, 16
+            d.W1, d.W2, d.W1T, d.W2T, d.bias2 = w["W1"].data_ptr(), w["W2"].data_ptr(), w["W1T"].data_ptr(), w["W2T"].data_ptr(), cs.bias2.data_ptr()
+            d.x = (cs.x if k == 0 else o["ys"][k - 1]).data_ptr(); d.y = o["ys"][k].data_ptr()
+            d.a2_save, d.scale_save, d.logdet_slot = o["a2"][k].data_ptr(), o["sc"][k].data_ptr(), o["slot"][k].data_ptr()
+            d.dparams_save, d.dc_save, d.dbias_part, d.x_op_save = o["dps"][k].data_ptr(), o["dcs"][k].data_ptr(), o["dbp"][k].data_ptr(), o["xop"][k].data_ptr()
+            if k % 4 in (1, 3):
+                d.post_log_scale, d.post_bias, d.y_post, d.post_part = cs.pls.data_ptr(), cs.pb.data_ptr(), o["ys"][k].data_ptr(), o["pp"][k].data_ptr()
+        lo, hi = (_lib.McfDesc * 4)(*d8[0:4]), (_lib.McfDesc * 4)(*d8[4:8])
+        for d, last in ((d8, d8[7]), (lo, lo[3]), (hi, hi[3])):
+            d[0].dld = cs.dld.data_ptr()
+            if S_ > 1:
+                d[0].split, d[0].xchg = S_, o["xchg"].data_ptr()
+            if inv:
+                last.x = d[0].x = o["yin"].data_ptr(); d[0].y = last.y = (o["xmid"] if d is hi else o["xrec"]).data_ptr()
+        if inv:
+            lo[3].x = lo[0].x = o["xmid"].data_ptr()
+        else:
+            d8[7].dy = hi[3].dy = cs.dy.data_ptr(); hi[0].dx = lo[3].dy = o["gmid"].data_ptr(); d8[0].dx = lo[0].dx = o["dx"].data_ptr()
+        return d8, lo, hi
+
+    def buffers(cs, S_):
+        o = cs.outputs(max(S_, 1))
+        for nme in ("ys", "a2", "sc", "dps", "dcs", "xop", "dbp", "pp"):
+            o[nme] = o[nme] + [torch.zeros_like(t) for t in o[nme]]
+        o["slot"] = torch.zeros(8, cs.B, 4, device=dev)
+        for nme in ("gmid", "xmid", "xrec", "yin"):
+            o[nme] = torch.randn(cs.M, cs.ld, device=dev, generator=g)
+        return o
+
+    def measure(calls):
+        """calls: per pair a list of (fn, descriptors); n pairs back to back per round"""
+        for c in calls:
+            for fn, d in c:
+                check(fn(d, _lib.BF16, s))
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(rounds):
+            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(n):
+                for fn, d in calls[i % len(calls)]:
+                    check(fn(d, _lib.BF16, s))
+            e1.record(); torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) / n * 1e3)
+        ts.sort()
+        return ts[len(ts) // 2], ts[0]
+
+    for what, b, S_ in (("fwd", B, S), ("bwd", B, S), ("inv", B_inv, 0)):
+        cs = Case(C, b, 64, NU)
+        o = buffers(cs, S_)
+        P = [pair_descs(cs, o, u, S_, inv=what == "inv") for u in range(0, NU, 2)]
+        f4, f8 = {"fwd": (lib.ipoke_macow_unit_fwd, lib.ipoke_macow_unit2_fwd), "bwd": (lib.ipoke_macow_unit_bwd, lib.ipoke_macow_unit2_bwd),
+                  "inv": (lib.ipoke_macow_unit_inv, lib.ipoke_macow_unit2_inv)}[what]
+        if what == "bwd":                        # saves of a forward pass
+            for d8, lo, hi in P:
+                check(lib.ipoke_macow_unit2_fwd(d8, _lib.BF16, s))
+        order = (lambda lo, hi: [(f4, lo), (f4, hi)]) if what == "fwd" else (lambda lo, hi: [(f4, hi), (f4, lo)])
+        res = {}
+        for rep in range(2):                     # two interleaved passes over the variants
+            for name, calls in (("two launches", [order(lo, hi) for d8, lo, hi in P]), ("one launch", [[(f8, d8)] for d8, lo, hi in P])):
+                m = measure(calls)
+                if name not in res or m[0] < res[name][0]:
+                    res[name] = m
+        a, c = res["two launches"], res["one launch"]
+        print(f"double {what} C={C} B={b} split={S_}: two launches {a[0]:.2f} / {a[1]:.2f} us   one launch {c[0]:.2f} / {c[1]:.2f} us   "
+              f"saved {a[0] - c[0]:.2f} us per pair (median / fastest round; timeouts {int(o['xchg'][0].item())})")
+
+
 if __name__ == "__main__":
+    if WHAT == "double":
+        double_timing(CT, BT)
+        sys.exit(0)
     bwd = WHAT != "fwd"
     allok = True
     for (C, ld, B) in [(64, 64, 5), (60, 64, 3), (32, 64, 4), (30, 32, 3), (8, 8, 2), (64, 64, 20)]:

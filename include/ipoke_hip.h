@@ -338,8 +338,10 @@ typedef struct {
   const void* cond; int32_t Cc;   /* act(cond), dtype [B*64][Cc] */
   const void* W1; const void* W2; const float* bias2;
   int32_t order;                  /* 0..3 = A..D */
-  int32_t rows_per_block;         /* fwd only: 16/32/64, 0 = default */
-  void* a2_save; float* scale_save; float* logdet_slot;   /* fwd saves (may be NULL) */
+  int32_t rows_per_block;         /* fwd only: 16/32/64, 0 = default (32 in bf16, 16 in f32) */
+  /* fwd saves (may be NULL).  ipoke_mcf_fwd: logdet_slot[b * w + r] = log-det of rows [r * rows, (r + 1) * rows) of sample b,
+   * rows = the rows per workgroup in effect, w = 64 / rows (so w = 2 in bf16 and 4 in f32 when rows_per_block == 0) */
+  void* a2_save; float* scale_save; float* logdet_slot;
   /* backward */
   const void* W2T; const void* W1T;
   const float* dy; const float* dld; float* dx;
@@ -391,7 +393,8 @@ int ipoke_mcf_bwd(const ipoke_mcf_desc* d, int dtype, void* stream);
  *   forward : d4[0].x is the unit's input; d4[k].x (k > 0) is ignored (the state stays on chip); d4[k].y may be NULL for k < 3
  *             (intermediate states not stored; the backward pass needs them); d4[3].y also receives the pass-through channels;
  *             d4[k].logdet_slot[b * w] receives the layer's whole log-det of sample b, w = 64 / d4[0].rows_per_block (the slot
- *             width of the per-layer call with that setting; 1 when rows_per_block == 0); post_log_scale / post_bias on d4[1]
+ *             width of the per-layer call with that setting) and w = 1 when rows_per_block == 0 (NOT the per-layer call's
+ *             default width; a split launch, which needs w >= split, is rejected then); post_log_scale / post_bias on d4[1]
  *             and d4[3] are the two ActNorms.
  *   backward: d4[k].x = saved input state of layer k; d4[3].dy = incoming gradient, d4[0].dx = gradient passed on, d4[0].dld;
  *             per layer a2_save / scale_save (from forward), dparams_save / dc_save / dbias_part (outputs), and for the layers

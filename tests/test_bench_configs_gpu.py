@@ -175,7 +175,8 @@ UNIT_TOL = {"f32": 3e-5, "bf16": 3e-2}
 def test_mcf_forward_inverse_backward(golden, C, gname, order, dtype):
     """One MaskedConvFlow through ipoke_mcf_fwd / _inv / _bwd against the reference: y, log-det, inverse, and the
     gradients of 0.5*sum(y^2) - sum(logdet) with respect to x, the shifted-conv weight, weight_v, weight_g and the bias
-    (weight gradients assembled from the tensors the kernel hands to the weight-gradient GEMMs)."""
+    (weight gradients assembled from the tensors the kernel hands to the weight-gradient GEMMs).  Whole-tensor norms against the
+    fp32 golden; tests/test_mcf_kernels_gpu.py checks every element of every phase against float64."""
     g = golden(gname)
     o, sd, sh, x, h = _mcf_setup(g, C, order, dtype)
     d_ = sh["dims"]

@@ -1,7 +1,8 @@
 """Fused MaCowUnit kernels (csrc/mcf_unit.hip: conv1(A) -> conv2(B) -> actnorm1 -> conv3(C) -> conv4(D) -> actnorm2 in one
 launch per direction) against (i) the oracle's MaCowUnit (plain PyTorch fp32 restatement of macow2.py:925-995, autograd for
 the backward pass) and (ii) the chain of per-layer kernels, layer by layer, on every tensor the backward pass and the
-weight-gradient GEMMs consume."""
+weight-gradient GEMMs consume.  (tests/test_mcf_kernels_gpu.py holds the same kernels to float64 references phase by phase, every
+element; the comparisons here are whole-tensor norms.)"""
 import pytest
 import torch
 

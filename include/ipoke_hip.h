@@ -772,7 +772,9 @@ int ipoke_sum_frames(const void* src, void* dst, int frames, int64_t n, int dtyp
  * v = normalize(W^T u), u = normalize(W v) (iterate != 0; u, v updated in place, eps as in F.normalize) and
  * sigma = u^T W v with W = weight.reshape(cout, -1) (weight.transpose(0,1).reshape(cout, -1) when transposed).
  * out = {sigma, 1/sigma}; snapshot (optional, cout + cin*taps floats) receives the u | v sigma was computed with.
- * workspace: ipoke_spectral_workspace_floats() floats, zeroed once by the caller. */
+ * workspace: ipoke_spectral_workspace_floats() floats, zeroed once by the caller.  Layout: [4 reserved | tu: cout | tv: cin*taps] --
+ * the four reserved words stay zero; after a call tu holds W v (the v the call ended with) and, after an iterating call, tv holds
+ * W^T u (the u the call began with), both before normalisation: the intermediates tests/test_sn_kernels_gpu.py checks phase by phase. */
 long ipoke_spectral_workspace_floats(int cout, int cin, int taps);
 int ipoke_spectral_sigma(const float* w, int cout, int cin, int taps, int transposed, float* u, float* v, int iterate, float eps,
                          float* out, float* snapshot, float* workspace, void* stream);

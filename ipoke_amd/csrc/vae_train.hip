@@ -924,7 +924,9 @@ extern "C" int ipoke_sum_frames(const void* src, void* dst, int frames, int64_t 
 extern "C" int ipoke_adam_multi(float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* n, int count,
                                 float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, void* stream) {
   IPK_REQUIRE(p && g && m && v && n && count >= 1 && step >= 1, "bad arguments");
-  const float bc1 = 1.f - powf(beta1, (float)step), bc2s = sqrtf(1.f - powf(beta2, (float)step));
+  // the bias corrections in double, as torch.optim.Adam computes them: 1 - powf(0.999f, 2) keeps 9 of fp32's 24 bits, which put the
+  // update of step 2 some 60 ulp off
+  const float bc1 = (float)(1.0 - pow((double)beta1, (double)step)), bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
   for (int t0 = 0; t0 < count; t0 += kAdamMax) {
     const int k = count - t0 < kAdamMax ? count - t0 : kAdamMax;
     AdamPack P;

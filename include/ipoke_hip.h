@@ -889,7 +889,10 @@ int ipoke_denorm_if_negative(float* x, int64_t rows, int Wo, int pad_l, int pad_
  * validation batch, second_stage_video.py:511-512): out[0] = 10 log10((max(target) - min(target))^2 / mse), out[1] = mean SSIM map
  * (11 x 11 Gaussian window, sigma 1.5, k1 = 0.01, k2 = 0.03, data range = the larger of the two tensors' ranges) over the positions
  * whose windows lie inside the image, of `planes` fp32 planes [planes][H][W] (N * C planes of NCHW tensors); H, W >= 11.
- * workspace: ipoke_image_metrics_workspace_bytes(planes, H, W) bytes. */
+ * workspace: ipoke_image_metrics_workspace_bytes(planes, H, W) bytes.  After the call it holds every phase (the tests read it):
+ * fp32 {-min preds, max preds, -min target, max target} at byte 0, the double sum of fl32(preds - target)^2 at byte 32, and from byte 64
+ * one double per (plane, tile) -- part[plane * tiles + ty * tiles_x + tx], tiles_x = ceil((W - 10) / 32), tiles = tiles_x *
+ * ceil((H - 10) / 32) -- the sum of the SSIM map over the tile's 32 x 32 positions that lie inside the map. */
 int64_t ipoke_image_metrics_workspace_bytes(int64_t planes, int H, int W);
 int ipoke_psnr_ssim(const float* preds, const float* target, int64_t planes, int H, int W, void* workspace, float* out, void* stream);
 /* metrics.py:939-960 MaxPool3dTFPadding: ZERO padding, then MaxPool3d(ceil_mode=True), on channels-last rows of the compute dtype.
@@ -900,7 +903,8 @@ int ipoke_pool3d_same(const int* dims, const void* x, int ldx, void* y, int ldy,
  * remaining time steps as one weighted mean over a clip's rows, taken before the (linear) logits convolution. */
 int ipoke_pool_rows_weighted(const void* x, int ldx, void* y, int ldy, int64_t G, int S, int C, const float* w, int dtype, void* stream);
 /* metrics.py:733-771 (calculate_moments / calculate_activation_statistics): rows of act fp32 [n][D] without any non-NaN entry are
- * dropped, mu = mean, sigma = np.cov(rowvar=False), both float64.  workspace: (n + 1) int32. */
+ * dropped, mu = mean, sigma = np.cov(rowvar=False), both float64 (fewer than two rows left: sigma is NaN, as np.cov's; none left: mu too).
+ * workspace: (n + 1) int32 -- afterwards the number of rows kept, then one flag per row. */
 int ipoke_activation_moments(const float* act, int n, int D, double* mu, double* sigma, int* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
@@ -912,7 +916,9 @@ int ipoke_activation_moments(const float* act, int n, int D, double* mu, double*
  * per-frame mean over C and the SSIM map of pred fp32 [bs][ns][s][C][H][W] against target fp32 [bs][1][s][C][H][W], which is read in place
  * for every sample.  Same map as ipoke_psnr_ssim; the data range is per example: max(range of its ns * s predicted frames, range of its
  * s target frames), as the reference's per-example call on [ns * s, C, H, W] gives.  H, W >= 11, ns * s * C <= 65535.
- * workspace: ipoke_sample_ssim_workspace_bytes(...) bytes. */
+ * workspace: ipoke_sample_ssim_workspace_bytes(...) bytes.  After the call it holds fp32 mm[bs][4] = {-min, max} of an example's
+ * predicted frames and of its target frames at byte 0, and from byte ceil(16 bs / 64) * 64 one double per (example, plane, tile),
+ * part[(e * ns * s * C + (j * s + f) * C + c) * tiles + tile], tiles as for ipoke_psnr_ssim. */
 int64_t ipoke_sample_ssim_workspace_bytes(int bs, int ns, int s, int C, int H, int W);
 int ipoke_sample_ssim(const float* pred, const float* target, int bs, int ns, int s, int C, int H, int W, void* workspace, float* out,
                       void* stream);

@@ -11,10 +11,22 @@ using namespace ipoke;
 static int grid1(long n, int cap = 4096) { long g = (n + 255) / 256; if (g < 1) g = 1; if (g > cap) g = cap; return (int)g; }
 
 // ---------------------------------------------------------------------------------------------- clip -> padded channels-last rows
-// float minimum through integer atomics: non-negative floats order like ints, negative ones reversed as unsigned
+// float minimum through integer atomics: non-negative floats order like ints, negative ones reversed as unsigned.
+// Chosen by the SIGN BIT, not by `v >= 0`: -0.0f compares >= 0 but its bit pattern is INT_MIN, which as a signed integer replaces every
+// negative minimum already stored (*minval then ends as -0.0 and ipoke_denorm_if_negative skips a data set that has negative pixels).
+// A NaN takes no part, as before.
 __device__ __forceinline__ void atomic_min_f32(float* addr, float v) {
-  if (v >= 0.f) atomicMin(reinterpret_cast<int*>(addr), __float_as_int(v));
-  else if (v < 0.f) atomicMax(reinterpret_cast<unsigned*>(addr), __float_as_uint(v));
+  if (v != v) return;
+  if (__float_as_int(v) >= 0) atomicMin(reinterpret_cast<int*>(addr), __float_as_int(v));
+  else atomicMax(reinterpret_cast<unsigned*>(addr), __float_as_uint(v));
+}
+
+// One ROUNDED product, as ATen's source index scale * o: contracted into the subtraction that follows it (an fma -- __fmul_rn is a plain
+// product and does not prevent that), the weight would come from the exact product while the index comes from the rounded one, up to an
+// ulp of the coordinate away from F.interpolate's weight.
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
 }
 
 // Bilinear resize with align_corners=True of every frame of a strided fp32 clip tensor (frame f of clip n at
@@ -34,7 +46,7 @@ __global__ void video_to_cl_kernel(const float* __restrict__ src, long s_n, long
       if (dst) for (int c = 0; c < C; ++c) dst[i * C + c] = 0.f;
       continue;
     }
-    const float fy = oy * sy, fx = ox * sx;
+    const float fy = mul_rounded((float)oy, sy), fx = mul_rounded((float)ox, sx);
     const int y0 = min((int)fy, Hi - 1), x0 = min((int)fx, Wi - 1);
     const int y1 = min(y0 + 1, Hi - 1), x1 = min(x0 + 1, Wi - 1);
     const float wy = fy - (float)y0, wx = fx - (float)x0;
@@ -146,7 +158,9 @@ __global__ void moments_cov_kernel(const float* __restrict__ a, int n, int D, co
   const double mi = mu[i], mj = mu[j];
   double s = 0.0;
   for (int r = 0; r < n; ++r) if (valid[r]) s += ((double)a[(long)r * D + i] - mi) * ((double)a[(long)r * D + j] - mj);
-  sigma[(long)i * D + j] = s / (double)(*count - 1);
+  // np.cov clamps the degrees of freedom at 0: one valid row AND none give 0 / 0 = NaN (0 / -1 would be -0.0)
+  const int dof = *count - 1;
+  sigma[(long)i * D + j] = s / (double)(dof > 0 ? dof : 0);
 }
 // ------------------------------------------------------------------------------------------------ image metrics
 // pytorch_lightning.metrics.functional.psnr / ssim as the reference's validation logging calls them (second_stage_video.py:511-512,

@@ -497,7 +497,7 @@ int ipoke_flow_tensor_info(const ipoke_flow* f, int i, char* name, int name_cap,
 /* float buffers of the state dict (use1x1 only): element count of the table, and the caller-owned device copy the layer
  * program reads (must be set before forward / reverse / backward when the count is non-zero) */
 /* hipGraph mode: the layer program of forward / reverse / one-shot backward is captured on the second call with a given
- * set of pointer arguments and replayed afterwards (IPOKE_GRAPH=1 sets the initial state; default off: on ROCm 7.2 the replay
+ * set of pointer arguments and replayed afterwards (off until this call switches it on: on ROCm 7.2 the replay
  * of the ~1 000-node programs is 1-2 % slower than the eager launches, whose host cost is hidden behind the GPU anyway) */
 int ipoke_flow_set_graph(ipoke_flow* f, int enable);
 int64_t ipoke_flow_float_buffer_count(const ipoke_flow* f);

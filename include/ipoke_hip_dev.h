@@ -32,7 +32,7 @@ enum { IPOKE_WGRAD_KERNEL_NONE = 0, IPOKE_WGRAD_KERNEL_TN = 1, IPOKE_WGRAD_KERNE
        IPOKE_WGRAD_KERNEL_LAT8 = 4, IPOKE_WGRAD_KERNEL_HALO = 5 };
 int ipoke_last_wgrad_kernel(void);
 
-/* developer probe (IPOKE_SIDE_DELAY_US): one wave spinning for about `us` microseconds on `stream` */
+/* developer probe: one wave spinning for about `us` microseconds on `stream` */
 int ipoke_spin_delay(int us, void* stream);
 
 /* In-situ timing for the benchmark's roofline objects: between ipoke_timing_start() and ipoke_timing_stop() every launch of

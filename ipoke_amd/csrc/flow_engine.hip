@@ -100,11 +100,8 @@ struct ipoke_flow {
   std::vector<WnJobH> wjobs;
   std::vector<LsRefH> lsrefs;
   void* d_rjobs = nullptr; void* d_wjobs = nullptr; void* d_lsrefs = nullptr; void* d_rblockjob = nullptr;
-  hipStream_t side = nullptr;
-  std::vector<hipStream_t> lanes;     // extra streams for sub-batch lanes 1..kMaxLanes-1 (lane 0 = caller's stream)
-  int n_lanes = 1;
+  hipStream_t side = nullptr;         // weight gradients (lowest priority)
   std::vector<hipEvent_t> events; size_t ev_next = 0;
-  bool use_side = true;
   // hipGraph replay of the ~5000-launch layer programs: keyed by every pointer argument + batch + mode
   struct GraphEntry { std::vector<uintptr_t> key; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int state = 0; uint64_t used = 0; };
   std::vector<GraphEntry> graphs; hipStream_t cap = nullptr; bool use_graph = false; uint64_t tick = 0;
@@ -139,7 +136,8 @@ struct ipoke_flow {
   bool mcf_xop = false;
   // conv2 of every coupling net (plain 1x1, 73 % of the parameters) keeps ONLY its straight bf16 copy: the data gradient reads it
   // K-major (igemm_nn_glds, ipoke_conv_desc.w_kmajor), the optimizer writes it while it holds the updated values (adam_cast_kernel),
-  // relayout never touches those tensors (IPOKE_C2_STRAIGHT=0: transposed shadow + relayout as in rounds 1-3)
+  // relayout never touches those tensors.  A function of dtype and hidden width only; the transposed shadow + relayout of rounds 1-3
+  // remains the path of f32 and of hidden % 64 != 0 (measured on c2 where both apply: 59.4 vs 58.4 ms for the straight copy)
   bool c2_straight = false;
   // Optimizer applied by the engine itself as soon as a piece of the backward pass is final (ipoke_flow_set_native_adam): the
   // Adam-amsgrad update and the shadow refresh of the piece's parameter ranges are queued on the ready stream by finish_piece
@@ -394,8 +392,7 @@ int build(ipoke_flow& f) {
   f.n_nice = 0;
   for (auto& o : f.ops) if (o.type == OP_NICE) o.nice_idx = f.n_nice++;
   // MaCowUnit: MCF, MCF, ActNorm, MCF, MCF, ActNorm -- the ActNorm runs inside the preceding MCF kernels
-  static const bool nofuse = getenv("IPOKE_NO_ACTNORM_FUSION") != nullptr;
-  for (size_t i = 0; !nofuse && i + 1 < f.ops.size(); ++i) {
+  for (size_t i = 0; i + 1 < f.ops.size(); ++i) {
     Op& a = f.ops[i]; Op& b2 = f.ops[i + 1];
     if (a.type == OP_MCF && b2.type == OP_ACTNORM && b2.idx_fwd < 0 && b2.p_ls >= 0 && b2.c0 == 0 && b2.Cn == a.C &&
         a.C % 4 == 0 && c.z_channels % 4 == 0 && a.level == b2.level) {
@@ -404,8 +401,7 @@ int build(ipoke_flow& f) {
   }
   // MaCowUnit = MCF, MCF(+ActNorm), ActNorm, MCF, MCF(+ActNorm), ActNorm of one width: one fused launch per direction
   // (mcf_unit.hip) where the matrix-core dtype supports it
-  static const bool nounit = getenv("IPOKE_NO_UNIT_FUSION") != nullptr;
-  for (size_t i = 0; !nounit && i + 5 < f.ops.size(); ++i) {
+  for (size_t i = 0; i + 5 < f.ops.size(); ++i) {
     const Op* o = &f.ops[i];
     const bool pat = o[0].type == OP_MCF && o[1].type == OP_MCF && o[2].type == OP_ACTNORM && o[3].type == OP_MCF &&
                      o[4].type == OP_MCF && o[5].type == OP_ACTNORM && o[0].fuse_act < 0 && o[1].fuse_act == (int)i + 2 &&
@@ -418,16 +414,14 @@ int build(ipoke_flow& f) {
     }
   }
   // coupling -> ActNorm (+ Shuffle) pairs: one launch per direction (ipoke_affine_actnorm_fwd / ipoke_actnorm_affine_bwd)
-  static const bool noan = getenv("IPOKE_NO_AN_FUSION") != nullptr;     // developer A/B
-  for (size_t i = 0; !noan && i + 1 < f.ops.size(); ++i) {
+  for (size_t i = 0; i + 1 < f.ops.size(); ++i) {
     Op& a = f.ops[i]; Op& b2 = f.ops[i + 1];
     // (the pair kernels stage whole rows of a sample: ipoke_actnorm_affine_bwd needs P * ld <= 8192 floats of LDS)
     if (a.type == OP_NICE && b2.type == OP_ACTNORM && !b2.fused && b2.unit_of < 0 && b2.Cn <= 256 && f.P * c.z_channels <= 8192) {
       a.an_next = (int)i + 1; b2.an_prev = (int)i;
     }
   }
-  static const bool noxop = getenv("IPOKE_NO_MCF_XOP") != nullptr;      // developer A/B
-  f.mcf_xop = c.dtype == IPOKE_BF16 && !noxop;
+  f.mcf_xop = c.dtype == IPOKE_BF16;
   for (const Op& op : f.ops) if (op.type == OP_MCF && op.unit_of < 0) f.mcf_xop = false;
   return IPOKE_OK;
 }
@@ -435,13 +429,12 @@ int build(ipoke_flow& f) {
 // ---- workspace plan ---------------------------------------------------------------------------
 struct Plan {
   int64_t bytes = 0;
-  int64_t cond_act = 0, slots = 0, ls_const = 0, partials = 0, partials_lane = 0, dld = 0, dbias_part = 0;
+  int64_t cond_act = 0, slots = 0, ls_const = 0, partials = 0, dld = 0, dbias_part = 0;
   int64_t state0 = 0, state_stride = 0;     // saved states S[0..nops]
   int64_t g0 = 0, g1 = 0;                   // gradient ping-pong
   int64_t tmp_h1 = 0, tmp_h2 = 0, tmp_zc = 0;   // shared hidden buffers when nothing is saved
   int64_t lu = 0;                               // [W | W^-1 | wl | wu] of every LU 1x1 conv
 };
-constexpr int kMaxLanes = 4;
 constexpr int kMaxUnitSplit = 4;          // rows of dbias_part per sample
 constexpr int kDefaultUnitSplit = 4;
 int64_t take(int64_t& cur, int64_t bytes) { const int64_t o = cur; cur = align_up(cur + bytes, 256); return o; }
@@ -454,8 +447,8 @@ int max_splitk(const ipoke_flow& f, int B) {
   }
   const int tiles = ceil_div(M, 64);
   const int nkb = ceil_div(9 * f.cfg.hidden, 128 / f.esz);
-  static const int target = getenv("IPOKE_SPLITK_TARGET") ? atoi(getenv("IPOKE_SPLITK_TARGET")) : 384;   // workgroups per N tile
-  int s = (target + tiles - 1) / tiles;
+  constexpr int kSplitkTarget = 384;   // workgroups per N tile
+  int s = (kSplitkTarget + tiles - 1) / tiles;
   if (s < 1) s = 1;
   if (s > nkb) s = nkb;
   if (s > 32) s = 32;
@@ -471,8 +464,7 @@ Plan make_plan(ipoke_flow& f, int B, int mode) {
   p.slots = take(cur, (int64_t)f.nslots * B * 4 * 4);
   p.ls_const = take(cur, 256);
   p.dld = take(cur, (int64_t)B * 4);
-  p.partials_lane = align_up((int64_t)32 * M * 64 * 4, 256);   // upper bound of splitk * M_lane * 64 floats
-  p.partials = take(cur, kMaxLanes * p.partials_lane);
+  p.partials = take(cur, (int64_t)32 * M * 64 * 4);            // upper bound of splitk * M * 64 floats
   p.state_stride = align_up(M * ld * 4, 256);
   p.lu = take(cur, (int64_t)f.lujobs.size() * 4 * 64 * 64 * 4 + 256);
   if (mode == 0) {
@@ -508,33 +500,23 @@ Plan make_plan(ipoke_flow& f, int B, int mode) {
   return p;
 }
 
-// Execution context of one *lane*: a contiguous range of samples [b0, b0 + B) of the batch, processed on its own stream.
-// The flow is strictly sequential per sample, and at the shipped batch sizes every kernel on the chain is bound by its
-// fixed launch/prologue/epilogue latency rather than by throughput; independent lanes on separate streams overlap those
-// latencies.  All row-indexed workspace buffers are laid out for the full batch, a lane addresses its row range.
+// Execution context of one pass: the batch, the caller's stream (the chain), the parameter / shadow / workspace bases and the plan.
 struct Ctx {
   ipoke_flow* f; int B; int64_t M; int ld; int dtype; hipStream_t s;
   const float* params; const int32_t* perm; const unsigned char* shadow; unsigned char* ws; Plan plan;
-  int b0 = 0, Bfull = 0, lane = 0;
   const float* wn_scale() const { return reinterpret_cast<const float*>(shadow); }
   const float* wn_inv() const { return reinterpret_cast<const float*>(shadow) + align_up(f->wn_rows, 64); }
   const unsigned char* sh(int64_t elem_off) const { return shadow + shadow_base() + elem_off * f->esz; }
   int64_t shadow_base() const { return 2 * align_up(f->wn_rows, 64) * 4; }
-  int64_t row0() const { return (int64_t)b0 * f->P; }
-  float* state(int i) const { return reinterpret_cast<float*>(ws + plan.state0 + (int64_t)i * plan.state_stride) + row0() * ld; }
+  float* state(int i) const { return reinterpret_cast<float*>(ws + plan.state0 + (int64_t)i * plan.state_stride); }
   template <typename T> T* at(int64_t off) const { return reinterpret_cast<T*>(ws + off); }
-  // row-indexed buffer at byte offset `off` with `row_bytes` per position
-  void* rows(int64_t off, int64_t row_bytes) const { return ws + off + row0() * row_bytes; }
-  float* rowsf(int64_t off, int64_t row_floats) const { return reinterpret_cast<float*>(ws + off) + row0() * row_floats; }
   void* stream() const { return reinterpret_cast<void*>(s); }
-  float* slot(int k) const { return at<float>(plan.slots) + ((int64_t)k * Bfull + b0) * 4; }
-  float* partials() const { return reinterpret_cast<float*>(ws + plan.partials + (int64_t)lane * plan.partials_lane); }
-  void* cond() const { return rows(plan.cond_act, (int64_t)f->cfg.cond_channels * f->esz); }
-  float* dld() const { return at<float>(plan.dld) + b0; }
+  float* slot(int k) const { return at<float>(plan.slots) + (int64_t)k * B * 4; }
+  float* partials() const { return at<float>(plan.partials); }
+  void* cond() const { return at<void>(plan.cond_act); }
+  float* dld() const { return at<float>(plan.dld); }
   // per-sample partial sums of op op_index: `parts` rows of ldp floats per sample (fused unit launches split over workgroups)
-  float* dbp(int op_index, int ldp, int parts = 1) const {
-    return at<float>(plan.dbias_part) + (int64_t)op_index * (kMaxUnitSplit * Bfull + 1) * 128 + (int64_t)b0 * parts * ldp;
-  }
+  float* dbp(int op_index) const { return at<float>(plan.dbias_part) + (int64_t)op_index * (kMaxUnitSplit * B + 1) * 128; }
 };
 
 void set_conv8(ipoke_conv_desc& d, int B, int k, int pad) {
@@ -555,16 +537,13 @@ void set_a_dense(ipoke_conv_desc& d, const void* act, int ld, int kc) {
 int nice_splitk(const Ctx& c) { return max_splitk(*c.f, c.B); }
 // coupling `a` transforms exactly the channels coupling `b` conditions on (up -> dn pairs): a's transform also writes b's operand
 // coupling op `i` follows a fused MaCowUnit (ops i-6 .. i-1): the unit's forward kernel writes the coupling's conditioning operand
-// (IPOKE_NO_UNIT_ZC=1: a launch of ipoke_extract_cols instead, as in rounds 1-2)
 bool unit_feeds(const ipoke_flow* f, size_t i) {
-  static const int on = getenv("IPOKE_NO_UNIT_ZC") ? 0 : 1;
-  if (!(on && i >= 6 && i < f->ops.size() && f->ops[i].type == OP_NICE && f->ops[i - 6].unit_head)) return false;
+  if (!(i >= 6 && i < f->ops.size() && f->ops[i].type == OP_NICE && f->ops[i - 6].unit_head)) return false;
   const Op& nx = f->ops[i];          // the unit kernel gathers the conditioning columns from ITS state tile: they must lie inside its C channels
   return nx.z_off + (nx.cin - 1) * nx.z_stride < f->ops[i - 6].C && nx.Kc1 % 2 == 0;
 }
 bool nice_feeds(const Op& a, const Op& b) {
-  static const int on = getenv("IPOKE_NO_EXTRACT_FUSION") ? 0 : 1;
-  return on && a.type == OP_NICE && b.type == OP_NICE && b.z_off == a.t_off && b.z_stride == a.t_stride && b.cin == a.cout;
+  return a.type == OP_NICE && b.type == OP_NICE && b.z_off == a.t_off && b.z_stride == a.t_stride && b.cin == a.cout;
 }
 
 // coupling net forward: conv1 -> ELU -> conv2 -> ELU -> conv3 (split-K partials)
@@ -649,7 +628,6 @@ int lu_prepare_all(const Ctx& c) {
   ipoke_flow* f = c.f;
   if (f->lujobs.empty()) return IPOKE_OK;
   IPK_REQUIRE(f->fbuf != nullptr, "use1x1: ipoke_flow_set_float_buffers has not been called");
-  IPK_REQUIRE(f->n_lanes == 1, "use1x1 does not support sub-batch lanes");
   return ipoke_lu_prepare(c.params, f->fbuf, c.at<float>(c.plan.lu), f->d_lujobs, (int)f->lujobs.size(), c.stream());
 }
 const float* lu_mat(const Ctx& c, const Op& op, int which) {     // 0 W, 1 W^-1
@@ -734,14 +712,11 @@ std::vector<std::pair<int, int>> backward_pieces(const ipoke_flow* f, int npiece
   const int np = npieces < 1 ? 1 : (npieces > U ? U : npieces);
   // Relative sizes: all pieces equal except the last two (the lowest layers, whose gradients are ready last).  Everything behind the
   // chain's last kernel -- the last weight gradients, then the optimizer and operand refresh of the last piece -- is exposed before
-  // the next forward pass can start; a smaller last piece shortens that tail (IPOKE_PIECE_TAPER="a,b": second-to-last, last).
-  static double ta = -1, tb = -1;
-  if (ta < 0) {
-    ta = 0.5; tb = 0.25;           // measured (c2, 24 pieces): 51.14 / 51.63 ms against 51.34 / 51.99 with equal pieces; 0.3 / 0.15 the same
-    if (const char* e = getenv("IPOKE_PIECE_TAPER")) { double a = 0, b = 0; if (sscanf(e, "%lf,%lf", &a, &b) == 2 && a > 0 && b > 0) { ta = a; tb = b; } }
-  }
+  // the next forward pass can start; a smaller last piece shortens that tail.
+  // measured (c2, 24 pieces): 51.14 / 51.63 ms against 51.34 / 51.99 with equal pieces; 0.3 / 0.15 the same
+  constexpr double kTaperSecondToLast = 0.5, kTaperLast = 0.25;
   std::vector<double> w((size_t)np, 1.0);
-  if (np >= 4) { w[(size_t)np - 2] = ta; w[(size_t)np - 1] = tb; }
+  if (np >= 4) { w[(size_t)np - 2] = kTaperSecondToLast; w[(size_t)np - 1] = kTaperLast; }
   double wsum = 0; for (double x : w) wsum += x;
   int hi = U - 1;
   int64_t acc = 0; double target_acc = 0;
@@ -789,10 +764,7 @@ extern "C" int ipoke_flow_create(const ipoke_flow_config* cfg, ipoke_flow** out)
   std::unique_ptr<ipoke_flow> f(new ipoke_flow());
   f->cfg = *cfg;
   f->esz = cfg->dtype == IPOKE_BF16 ? 2 : 4; f->e16 = 16 / f->esz; f->ks = 64 / f->esz;
-  {
-    const char* cs = getenv("IPOKE_C2_STRAIGHT");
-    f->c2_straight = cfg->dtype == IPOKE_BF16 && cfg->hidden % 64 == 0 && !(cs && cs[0] == '0');
-  }
+  f->c2_straight = cfg->dtype == IPOKE_BF16 && cfg->hidden % 64 == 0;
   int rc = build(*f); if (rc) return rc;
   {   // gaps between the optimizer-fused tensors (both tables are in parameter order)
     int64_t pos = 0;
@@ -804,24 +776,19 @@ extern "C" int ipoke_flow_create(const ipoke_flow_config* cfg, ipoke_flow** out)
     if (pos < f->n_params) f->asegs.push_back({(long)pos, (long)(f->n_params - pos)});
     for (size_t k = 1; k < f->rjobs.size(); ++k) IPK_REQUIRE(f->rjobs[k].src_off > f->rjobs[k - 1].src_off, "relayout jobs must be in parameter order");
   }
-  const char* env = getenv("IPOKE_NO_SIDE_STREAM");
-  f->use_side = !(env && env[0] == '1');
-  const char* gr = getenv("IPOKE_GRAPH");
-  f->use_graph = gr && gr[0] == '1';     // opt-in: see DESIGN.md (replay is slower than eager launches on ROCm 7.2)
-  const char* ln = getenv("IPOKE_LANES");
-  f->n_lanes = ln ? atoi(ln) : 1;
-  if (f->n_lanes < 1) f->n_lanes = 1;
-  if (f->n_lanes > kMaxLanes) f->n_lanes = kMaxLanes;
-  {   // rows of a sample dealt to 2 / 4 workgroups in the fused unit launches (IPOKE_UNIT_SPLIT=1: one workgroup per sample)
+  // (use_graph starts false: replay is slower than eager launches on ROCm 7.2; ipoke_flow_set_graph switches it on)
+  {   // rows of a sample dealt to 2 / 4 workgroups in the fused unit launches (IPOKE_UNIT_SPLIT=1: one workgroup per sample).  A caller
+      // option, read here only; tests/test_flow_gpu.py::test_unit_row_split_engine_matches_one_workgroup_per_sample
+      // compares 1 against the default
     const char* us = getenv("IPOKE_UNIT_SPLIT");
     f->unit_split = us ? atoi(us) : kDefaultUnitSplit;
     if (f->unit_split != 2 && f->unit_split != 4) f->unit_split = 1;
-    if (f->n_lanes > 1 || cfg->dtype != IPOKE_BF16) f->unit_split = 1;     // (lanes would share the scratch across streams)
+    if (cfg->dtype != IPOKE_BF16) f->unit_split = 1;
   }
-  f->coupling_fuse = f->n_lanes == 1 && cfg->dtype == IPOKE_BF16 && ipoke_conv3x3_coupling_splitk(64, cfg->hidden, cfg->dtype) > 0;
-  {   // coupling -> ActNorm -> unit (MaCowStep): the pair's backward inside the unit's row-split backward launch (IPOKE_UNIT_PAIR=0: off)
-    const char* up = getenv("IPOKE_UNIT_PAIR");
-    const bool on = f->unit_split > 1 && f->n_lanes == 1 && (up ? atoi(up) != 0 : true);
+  f->coupling_fuse = cfg->dtype == IPOKE_BF16 && ipoke_conv3x3_coupling_splitk(64, cfg->hidden, cfg->dtype) > 0;
+  {   // coupling -> ActNorm -> unit (MaCowStep): the pair's backward inside the unit's row-split backward launch
+      // (51.29 ms against 51.45 with the pair in a launch of ipoke_actnorm_affine_bwd, which unit_split == 1 still uses)
+    const bool on = f->unit_split > 1;
     for (size_t h = 2; on && h < f->ops.size(); ++h) {
       const Op& u = f->ops[h]; Op& an = f->ops[h - 1]; Op& cp = f->ops[h - 2];
       if (u.unit_head && an.type == OP_ACTNORM && an.an_prev == (int)h - 2 && cp.type == OP_NICE && an.c0 == 0 && an.Cn == u.C &&
@@ -844,14 +811,11 @@ static int ensure_device(ipoke_flow* f) {
     IPK_HIP(hipMemset(f->d_xchg, 0, nb));
     f->xchg_bytes = nb;
   }
-  if (!f->d_acc) {
-    static const bool atomics = getenv("IPOKE_DGRAD_ATOMICS") != nullptr;      // developer A/B: the order-dependent atomic accumulation of rounds 1-5
-    if (!atomics) {
-      f->acc_bytes = ipoke_conv_acc_scratch_bytes(f->cfg.max_batch * f->P, 64, 32);
-      IPK_HIP(hipMalloc(&f->d_acc, (size_t)f->acc_bytes));
-      int rc = ipoke_conv_acc_scratch_init(f->d_acc, nullptr); if (rc) return rc;
-      IPK_HIP(hipDeviceSynchronize());
-    }
+  if (!f->d_acc) {     // (the fp32 atomics of rounds 1-5 instead: order-dependent rounding, 50.7 vs 49.5 ms)
+    f->acc_bytes = ipoke_conv_acc_scratch_bytes(f->cfg.max_batch * f->P, 64, 32);
+    IPK_HIP(hipMalloc(&f->d_acc, (size_t)f->acc_bytes));
+    int rc = ipoke_conv_acc_scratch_init(f->d_acc, nullptr); if (rc) return rc;
+    IPK_HIP(hipDeviceSynchronize());
   }
   if (!f->h_tmo) {
     IPK_HIP(hipHostMalloc(reinterpret_cast<void**>(&f->h_tmo), 64, hipHostMallocMapped));
@@ -909,12 +873,9 @@ static int ensure_device(ipoke_flow* f) {
   {   // weight gradients are off the critical path: lowest priority so that chain kernels get the CUs first
     int least = 0, greatest = 0;
     IPK_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    static const bool flat = getenv("IPOKE_SIDE_FLAT_PRIORITY") != nullptr;
-    IPK_HIP(hipStreamCreateWithPriority(&f->side, hipStreamNonBlocking, flat ? 0 : least));
+    IPK_HIP(hipStreamCreateWithPriority(&f->side, hipStreamNonBlocking, least));
   }
   IPK_HIP(hipStreamCreateWithFlags(&f->cap, hipStreamNonBlocking));
-  f->lanes.resize(kMaxLanes - 1);
-  for (auto& l : f->lanes) IPK_HIP(hipStreamCreateWithFlags(&l, hipStreamNonBlocking));
   f->events.resize(256);
   for (auto& e : f->events) IPK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   return IPOKE_OK;
@@ -944,7 +905,6 @@ extern "C" void ipoke_flow_destroy(ipoke_flow* f) {
   drop_graphs(f);
   if (f->side) (void)hipStreamDestroy(f->side);
   if (f->cap) (void)hipStreamDestroy(f->cap);
-  for (auto l : f->lanes) if (l) (void)hipStreamDestroy(l);
   delete f;
 }
 
@@ -1139,40 +1099,12 @@ static int adam_range(ipoke_flow* f, float* params, const float* grads, float* m
 }
 
 // ------------------------------------------------------------------------------------------------
-// Lanes: split the batch into up to n_lanes contiguous sample ranges, lane 0 on the caller's stream.
-static int make_lanes(const Ctx& full, int want, std::vector<Ctx>& lanes) {
-  ipoke_flow* f = full.f;
-  int n = want < 1 ? 1 : want;
-  if (n > kMaxLanes) n = kMaxLanes;
-  if (n > full.B) n = full.B;
-  lanes.clear();
-  int b0 = 0;
-  for (int k = 0; k < n; ++k) {
-    const int nb = (full.B - b0 + (n - k) - 1) / (n - k);
-    Ctx c = full;
-    c.b0 = b0; c.B = nb; c.M = (int64_t)nb * f->P; c.Bfull = full.B; c.lane = k;
-    c.s = k == 0 ? full.s : f->lanes[k - 1];
-    lanes.push_back(c);
-    b0 += nb;
-  }
-  return IPOKE_OK;
-}
-// lanes 1.. wait for everything queued so far on the caller's stream
-static int fork_lanes(ipoke_flow* f, hipStream_t from, const std::vector<Ctx>& lanes) {
-  if (lanes.size() < 2) return IPOKE_OK;
+// `to` waits for the work queued so far on `from` (nothing to do when they are the same stream)
+static int stream_wait(ipoke_flow* f, hipStream_t to, hipStream_t from) {
+  if (from == to) return IPOKE_OK;
   hipEvent_t e = next_event(f);
   IPK_HIP(hipEventRecord(e, from));
-  for (size_t k = 1; k < lanes.size(); ++k) IPK_HIP(hipStreamWaitEvent(lanes[k].s, e, 0));
-  return IPOKE_OK;
-}
-// `to` waits for the work queued so far on every lane (lanes that already run on `to` are skipped)
-static int join_lanes(ipoke_flow* f, const std::vector<Ctx>& lanes, hipStream_t to) {
-  for (size_t k = 0; k < lanes.size(); ++k) {
-    if (lanes[k].s == to) continue;
-    hipEvent_t e = next_event(f);
-    IPK_HIP(hipEventRecord(e, lanes[k].s));
-    IPK_HIP(hipStreamWaitEvent(to, e, 0));
-  }
+  IPK_HIP(hipStreamWaitEvent(to, e, 0));
   return IPOKE_OK;
 }
 
@@ -1288,11 +1220,11 @@ extern "C" int ipoke_flow_test_inject_timeout(ipoke_flow* f, int which, void* st
 // heads h and h + 6 are such a pair, ONE launch per direction runs both (ipoke_macow_unit2_*: the state / gradient between them stays
 // on chip, the upper unit's weights arrive under the lower one's last layer).  kUnit2Default: the measured per-direction decision
 // (the forward and the backward pass each pay by the project's margin over noise; the reverse pass gained 0.37-0.49 ms
-// of c5, less than three times the run-to-run spread in all three blocks, and keeps a launch per unit).  Sub-batch lanes and the
-// one-workgroup-per-sample kernels keep a launch per unit.
+// of c5, less than three times the run-to-run spread in all three blocks, and keeps a launch per unit).  The one-workgroup-per-sample
+// kernels keep a launch per unit.
 static const bool kUnit2Default[3] = {true, true, false};      // IPOKE_UNIT2_FWD, _BWD, _INV
-static bool unit2_at(const ipoke_flow* f, int h, int direction, size_t nlanes) {
-  if (f->split_unit2 > 0 || (!kUnit2Default[direction] && f->split_unit2 == 0) || nlanes != 1 || h < 0 || h + 11 >= (int)f->ops.size()) return false;
+static bool unit2_at(const ipoke_flow* f, int h, int direction) {
+  if (f->split_unit2 > 0 || (!kUnit2Default[direction] && f->split_unit2 == 0) || h < 0 || h + 11 >= (int)f->ops.size()) return false;
   const Op& a = f->ops[h]; const Op& b = f->ops[h + 6];
   if (!(a.unit_head && b.unit_head && a.C == b.C && a.level == b.level)) return false;
   const int split = direction == IPOKE_UNIT2_INV ? 0 : (f->unit_split > 1 && f->d_xchg ? f->unit_split : 1);
@@ -1342,7 +1274,6 @@ static int run_forward(ipoke_flow* f, const float* params, const int32_t* perm, 
   Ctx c{f, B, (int64_t)B * f->P, f->cfg.z_channels, f->cfg.dtype, reinterpret_cast<hipStream_t>(stream),
         params, perm, reinterpret_cast<const unsigned char*>(shadow), reinterpret_cast<unsigned char*>(workspace),
         make_plan(*f, B, save ? 1 : 0)};
-  c.Bfull = B;
   const int z = f->cfg.z_channels;
   rc = ipoke_nchw_to_state(x_nchw, c.state(0), B, z, f->P, c.ld, stream); if (rc) return rc;
   if (!init) {
@@ -1351,43 +1282,37 @@ static int run_forward(ipoke_flow* f, const float* params, const int32_t* perm, 
   }
   IPK_HIP(hipMemsetAsync(c.at<void>(c.plan.slots), 0, (size_t)f->nslots * B * 4 * sizeof(float), c.s));
   rc = lu_prepare_all(c); if (rc) return rc;
-  // the data-dependent ActNorm init needs whole-batch statistics: one lane
-  std::vector<Ctx> lanes;
-  rc = make_lanes(c, init ? 1 : f->n_lanes, lanes); if (rc) return rc;
-  rc = fork_lanes(f, c.s, lanes); if (rc) return rc;
-  static const int rpb = getenv("IPOKE_MCF_ROWS") ? atoi(getenv("IPOKE_MCF_ROWS")) : 16;
+  constexpr int kMcfRows = 16;          // per-layer MCF forward slice height: 4 slices per sample -> slot width 4
   int cur = 0;
   for (size_t i = 0; i < f->ops.size(); ++i) {
     const Op& op = f->ops[i];
     if (init && op.type != OP_ACTNORM && op.type != OP_LU) continue;   // zero-initialised couplings are the identity (macow_utils.py:231-250)
     if (!init && op.unit_head) {                   // whole MaCowUnit (ops i .. i+5) in one launch, or two adjacent ones (ops i .. i+11)
-      const int nl = unit2_at(f, (int)i, IPOKE_UNIT2_FWD, lanes.size()) ? 8 : 4;
+      const int nl = unit2_at(f, (int)i, IPOKE_UNIT2_FWD) ? 8 : 4;
       const int nops = nl / 4 * 6;
       const int nxt = save ? (int)i + nops : (cur ^ 1);
       static const int lidx[8] = {0, 1, 3, 4, 6, 7, 9, 10};     // the masked convs among the six ops of a unit
       static const int oidx[8] = {1, 3, 4, 6, 7, 9, 10, 12};    // state index (relative to i) each of them writes when states are saved
-      for (const Ctx& l : lanes) {
-        ipoke_mcf_desc d4[8];
-        for (int k = 0; k < nl; ++k) {
-          const Op& mk = f->ops[i + lidx[k]];
-          mcf_desc(l, mk, d4[k]);
-          d4[k].x = k == 0 ? l.state(cur) : nullptr;
-          d4[k].y = k == nl - 1 ? l.state(nxt) : (save ? l.state((int)i + oidx[k]) : nullptr);
-          d4[k].logdet_slot = l.slot(mk.slot);
-          d4[k].rows_per_block = 16;               // slot width 4, as the per-layer launches
-          if (mk.fuse_act >= 0) { d4[k].post_log_scale = params + f->ops[mk.fuse_act].p_ls; d4[k].post_bias = params + f->ops[mk.fuse_act].p_bias; }
-          if (save) { d4[k].a2_save = l.rows(mk.ws_a, (int64_t)mk.K2p * f->esz); d4[k].scale_save = l.rowsf(mk.ws_b, mk.C); }
-        }
-        if (unit_feeds(f, i + nops)) {
-          const Op& nx = f->ops[i + nops];
-          ipoke_mcf_desc& dl = d4[nl - 1];
-          dl.zc_out = save ? l.rows(nx.ws_g, (int64_t)nx.Kc1 * f->esz) : l.rows(l.plan.tmp_zc, 64L * f->esz);
-          dl.zc_off = nx.z_off; dl.zc_stride = nx.z_stride; dl.zc_cin = nx.cin; dl.zc_ld = nx.Kc1;
-        }
-        if (f->unit_split > 1 && f->d_xchg) { d4[0].split = f->unit_split; d4[0].xchg = f->d_xchg; }
-        rc = nl == 8 ? ipoke_macow_unit2_fwd(d4, l.dtype, l.stream()) : ipoke_macow_unit_fwd(d4, l.dtype, l.stream());
-        if (rc) return rc;
+      ipoke_mcf_desc d4[8];
+      for (int k = 0; k < nl; ++k) {
+        const Op& mk = f->ops[i + lidx[k]];
+        mcf_desc(c, mk, d4[k]);
+        d4[k].x = k == 0 ? c.state(cur) : nullptr;
+        d4[k].y = k == nl - 1 ? c.state(nxt) : (save ? c.state((int)i + oidx[k]) : nullptr);
+        d4[k].logdet_slot = c.slot(mk.slot);
+        d4[k].rows_per_block = 16;               // slot width 4, as the per-layer launches
+        if (mk.fuse_act >= 0) { d4[k].post_log_scale = params + f->ops[mk.fuse_act].p_ls; d4[k].post_bias = params + f->ops[mk.fuse_act].p_bias; }
+        if (save) { d4[k].a2_save = c.at<void>(mk.ws_a); d4[k].scale_save = c.at<float>(mk.ws_b); }
       }
+      if (unit_feeds(f, i + nops)) {
+        const Op& nx = f->ops[i + nops];
+        ipoke_mcf_desc& dl = d4[nl - 1];
+        dl.zc_out = c.at<void>(save ? nx.ws_g : c.plan.tmp_zc);
+        dl.zc_off = nx.z_off; dl.zc_stride = nx.z_stride; dl.zc_cin = nx.cin; dl.zc_ld = nx.Kc1;
+      }
+      if (f->unit_split > 1 && f->d_xchg) { d4[0].split = f->unit_split; d4[0].xchg = f->d_xchg; }
+      rc = nl == 8 ? ipoke_macow_unit2_fwd(d4, c.dtype, c.stream()) : ipoke_macow_unit_fwd(d4, c.dtype, c.stream());
+      if (rc) return rc;
       cur = nxt;
       i += nops - 1;
       continue;
@@ -1396,73 +1321,69 @@ static int run_forward(ipoke_flow* f, const float* params, const int32_t* perm, 
     const bool fuse = !init && op.type == OP_MCF && op.fuse_act >= 0;
     const bool with_an = !init && op.type == OP_NICE && op.an_next >= 0;       // the ActNorm behind this coupling runs in its affine launch
     const int nxt = save ? (int)i + (fuse || with_an ? 2 : 1) : (cur ^ 1);
-    for (const Ctx& l : lanes) {
-      const float* in = l.state(cur); float* out = l.state(nxt);
-      if (op.type == OP_LU) {
-        rc = ipoke_lu_apply(in, out, (int64_t)l.B * l.f->P, l.ld, op.C, lu_mat(l, op, 0), 0, l.stream());
-      } else if (op.type == OP_ACTNORM) {
-        const float* ls = op.p_ls >= 0 ? params + op.p_ls : nullptr;
-        const float* bs = op.p_bias >= 0 ? params + op.p_bias : nullptr;
-        const int32_t* idx = op.idx_fwd >= 0 ? perm + op.idx_fwd : nullptr;
-        if (init && op.p_ls >= 0) {
-          rc = ipoke_actnorm_init(in, (int)l.M, l.ld, op.c0, op.Cn, params_mut + op.p_ls, params_mut + op.p_bias, l.stream());
-          if (rc) return rc;
-        }
-        rc = ipoke_actnorm_fwd(in, out, (int)l.M, l.ld, op.c0, op.Cn, ls, bs, idx, l.stream());
-      } else if (op.type == OP_MCF) {
-        ipoke_mcf_desc d; mcf_desc(l, op, d);
-        d.x = in; d.y = out;
-        d.logdet_slot = l.slot(op.slot);
-        d.rows_per_block = rpb;   // 16: 4 slices per sample -> slot width 4
-        if (fuse) { d.post_log_scale = params + f->ops[op.fuse_act].p_ls; d.post_bias = params + f->ops[op.fuse_act].p_bias; }
-        if (save) { d.a2_save = l.rows(op.ws_a, (int64_t)op.K2p * f->esz); d.scale_save = l.rowsf(op.ws_b, op.C); }
-        rc = ipoke_mcf_fwd(&d, l.dtype, l.stream());
-      } else {
-        const int64_t hb = (int64_t)f->cfg.hidden * f->esz;
-        void* h1 = l.rows(save ? op.ws_a : l.plan.tmp_h1, hb);
-        void* h2 = l.rows(save ? op.ws_b : l.plan.tmp_h2, (int64_t)op.hidK * f->esz);
-        void* zc = save ? l.rows(op.ws_g, (int64_t)op.Kc1 * f->esz) : l.rows(l.plan.tmp_zc, 64L * f->esz);
-        const bool have_zc = (i > 0 && nice_feeds(f->ops[i - 1], op)) || (!init && unit_feeds(f, i));
-        const bool one_launch = !init && nice_fused(l, op);
-        const bool pair = one_launch && nice_pair(l, op), split = pair && f->split_pair_coupling;
-        rc = nice_net(l, op, in, h1, h2, zc, have_zc, !one_launch, pair ? (split ? 2 : 0) : 1); if (rc) return rc;
-        ipoke_affine_desc a; nice_affine_desc(l, op, a);
-        void* ext = nullptr; int ext_ld = 0;
-        if (i + 1 < f->ops.size() && nice_feeds(op, f->ops[i + 1])) {
-          const Op& nx = f->ops[i + 1];
-          ext = save ? l.rows(nx.ws_g, (int64_t)nx.Kc1 * f->esz) : l.rows(l.plan.tmp_zc, 64L * f->esz);
-          ext_ld = nx.Kc1;
-        }
-        if (one_launch) {
-          ipoke_coupling_epi e; std::memset(&e, 0, sizeof(e));
-          e.mode = with_an ? 1 : 0; e.in = in; e.scale_out = save ? l.rowsf(op.ws_c, op.cout) : nullptr;
-          e.logdet_slot = l.slot(op.slot); e.slot_stride = 4; e.xchg = f->d_cxchg;
-          if (with_an) {
-            const Op& an = f->ops[op.an_next];
-            e.out = save ? l.state((int)i + 1) : nullptr; e.out2 = out;
-            e.an_c0 = an.c0; e.an_C = an.Cn; e.an_log_scale = an.p_ls >= 0 ? params + an.p_ls : nullptr;
-            e.an_bias = an.p_bias >= 0 ? params + an.p_bias : nullptr; e.an_idx = an.idx_fwd >= 0 ? perm + an.idx_fwd : nullptr;
-          } else {
-            e.out = out; e.ext = ext; e.ext_ld = ext_ld;
-          }
-          rc = nice_coupling(l, op, pair, split, h1, h2, true, a, e);      // (h2 is stored: the backward pass reads it)
-        } else if (with_an) {
-          const Op& an = f->ops[op.an_next];
-          rc = ipoke_affine_actnorm_fwd(&a, in, save ? l.state((int)i + 1) : nullptr, out, save ? l.rowsf(op.ws_c, op.cout) : nullptr,
-                                        l.slot(op.slot), 4, l.B, an.c0, an.Cn, an.p_ls >= 0 ? params + an.p_ls : nullptr,
-                                        an.p_bias >= 0 ? params + an.p_bias : nullptr, an.idx_fwd >= 0 ? perm + an.idx_fwd : nullptr,
-                                        l.stream());
-        } else {
-          rc = ipoke_affine_fwd_ext(&a, in, out, save ? l.rowsf(op.ws_c, op.cout) : nullptr, l.slot(op.slot), 4, l.B, ext, ext_ld, l.dtype,
-                                    l.stream());
-        }
+    const float* in = c.state(cur); float* out = c.state(nxt);
+    if (op.type == OP_LU) {
+      rc = ipoke_lu_apply(in, out, c.M, c.ld, op.C, lu_mat(c, op, 0), 0, c.stream());
+    } else if (op.type == OP_ACTNORM) {
+      const float* ls = op.p_ls >= 0 ? params + op.p_ls : nullptr;
+      const float* bs = op.p_bias >= 0 ? params + op.p_bias : nullptr;
+      const int32_t* idx = op.idx_fwd >= 0 ? perm + op.idx_fwd : nullptr;
+      if (init && op.p_ls >= 0) {
+        rc = ipoke_actnorm_init(in, (int)c.M, c.ld, op.c0, op.Cn, params_mut + op.p_ls, params_mut + op.p_bias, c.stream());
+        if (rc) return rc;
       }
-      if (rc) return rc;
+      rc = ipoke_actnorm_fwd(in, out, (int)c.M, c.ld, op.c0, op.Cn, ls, bs, idx, c.stream());
+    } else if (op.type == OP_MCF) {
+      ipoke_mcf_desc d; mcf_desc(c, op, d);
+      d.x = in; d.y = out;
+      d.logdet_slot = c.slot(op.slot);
+      d.rows_per_block = kMcfRows;
+      if (fuse) { d.post_log_scale = params + f->ops[op.fuse_act].p_ls; d.post_bias = params + f->ops[op.fuse_act].p_bias; }
+      if (save) { d.a2_save = c.at<void>(op.ws_a); d.scale_save = c.at<float>(op.ws_b); }
+      rc = ipoke_mcf_fwd(&d, c.dtype, c.stream());
+    } else {
+      void* h1 = c.at<void>(save ? op.ws_a : c.plan.tmp_h1);
+      void* h2 = c.at<void>(save ? op.ws_b : c.plan.tmp_h2);
+      void* zc = c.at<void>(save ? op.ws_g : c.plan.tmp_zc);
+      const bool have_zc = (i > 0 && nice_feeds(f->ops[i - 1], op)) || (!init && unit_feeds(f, i));
+      const bool one_launch = !init && nice_fused(c, op);
+      const bool pair = one_launch && nice_pair(c, op), split = pair && f->split_pair_coupling;
+      rc = nice_net(c, op, in, h1, h2, zc, have_zc, !one_launch, pair ? (split ? 2 : 0) : 1); if (rc) return rc;
+      ipoke_affine_desc a; nice_affine_desc(c, op, a);
+      void* ext = nullptr; int ext_ld = 0;
+      if (i + 1 < f->ops.size() && nice_feeds(op, f->ops[i + 1])) {
+        const Op& nx = f->ops[i + 1];
+        ext = c.at<void>(save ? nx.ws_g : c.plan.tmp_zc);
+        ext_ld = nx.Kc1;
+      }
+      if (one_launch) {
+        ipoke_coupling_epi e; std::memset(&e, 0, sizeof(e));
+        e.mode = with_an ? 1 : 0; e.in = in; e.scale_out = save ? c.at<float>(op.ws_c) : nullptr;
+        e.logdet_slot = c.slot(op.slot); e.slot_stride = 4; e.xchg = f->d_cxchg;
+        if (with_an) {
+          const Op& an = f->ops[op.an_next];
+          e.out = save ? c.state((int)i + 1) : nullptr; e.out2 = out;
+          e.an_c0 = an.c0; e.an_C = an.Cn; e.an_log_scale = an.p_ls >= 0 ? params + an.p_ls : nullptr;
+          e.an_bias = an.p_bias >= 0 ? params + an.p_bias : nullptr; e.an_idx = an.idx_fwd >= 0 ? perm + an.idx_fwd : nullptr;
+        } else {
+          e.out = out; e.ext = ext; e.ext_ld = ext_ld;
+        }
+        rc = nice_coupling(c, op, pair, split, h1, h2, true, a, e);      // (h2 is stored: the backward pass reads it)
+      } else if (with_an) {
+        const Op& an = f->ops[op.an_next];
+        rc = ipoke_affine_actnorm_fwd(&a, in, save ? c.state((int)i + 1) : nullptr, out, save ? c.at<float>(op.ws_c) : nullptr,
+                                      c.slot(op.slot), 4, c.B, an.c0, an.Cn, an.p_ls >= 0 ? params + an.p_ls : nullptr,
+                                      an.p_bias >= 0 ? params + an.p_bias : nullptr, an.idx_fwd >= 0 ? perm + an.idx_fwd : nullptr,
+                                      c.stream());
+      } else {
+        rc = ipoke_affine_fwd_ext(&a, in, out, save ? c.at<float>(op.ws_c) : nullptr, c.slot(op.slot), 4, c.B, ext, ext_ld, c.dtype,
+                                  c.stream());
+      }
     }
+    if (rc) return rc;
     cur = nxt;
     if (with_an) ++i;                              // the ActNorm op has been executed
   }
-  rc = join_lanes(f, lanes, c.s); if (rc) return rc;
   rc = ipoke_state_to_nchw(c.state(cur), out_nchw, B, z, f->P, c.ld, stream); if (rc) return rc;
   if (logdet) {
     rc = ipoke_actnorm_logdet(params, f->d_lsrefs, (int)f->lsrefs.size(), f->P, c.at<float>(c.plan.ls_const), stream);
@@ -1510,20 +1431,15 @@ static int run_reverse(ipoke_flow* f, const float* params, const int32_t* perm, 
   Ctx c{f, B, (int64_t)B * f->P, f->cfg.z_channels, f->cfg.dtype, reinterpret_cast<hipStream_t>(stream),
         params, perm, reinterpret_cast<const unsigned char*>(shadow), reinterpret_cast<unsigned char*>(workspace),
         make_plan(*f, B, 0)};
-  c.Bfull = B;
   const int z = f->cfg.z_channels;
   rc = ipoke_nchw_to_state(z_nchw, c.state(0), B, z, f->P, c.ld, stream); if (rc) return rc;
   rc = ipoke_cond_prepare(cond_nchw, c.cond(), B, f->cfg.cond_channels, f->P, IPOKE_ACT_ELU, c.dtype, stream);
   if (rc) return rc;
   rc = lu_prepare_all(c); if (rc) return rc;
-  std::vector<Ctx> lanes;
-  rc = make_lanes(c, f->n_lanes, lanes); if (rc) return rc;
-  rc = fork_lanes(f, c.s, lanes); if (rc) return rc;
-  const int64_t hb = (int64_t)f->cfg.hidden * f->esz;
-  static const bool no_an_ext = getenv("IPOKE_NO_AN_EXT") != nullptr;       // developer A/B
   // a stand-alone ActNorm (+ Shuffle) whose inverse is directly followed by the inverse of a coupling (ops[k - 1] in this direction)
+  // (one launch less per coupling pair than ipoke_actnorm_inv + ipoke_extract_cols; nothing measurable: c5 44.70 vs 44.70, 44.42 vs 44.37 ms)
   auto actnorm_feeds = [&](int k) {
-    if (no_an_ext || k < 1 || k >= (int)f->ops.size()) return false;
+    if (k < 1 || k >= (int)f->ops.size()) return false;
     const Op& an = f->ops[k]; const Op& nx = f->ops[k - 1];
     return an.type == OP_ACTNORM && an.unit_of < 0 && nx.type == OP_NICE && nx.Kc1 - nx.cin <= c.ld && nx.Kc1 <= 64;
   };
@@ -1531,66 +1447,61 @@ static int run_reverse(ipoke_flow* f, const float* params, const int32_t* perm, 
   for (int i = (int)f->ops.size() - 1; i >= 0; --i) {
     const Op& op = f->ops[i];
     if (op.unit_of >= 0 && i == op.unit_of + 5) {     // whole MaCowUnit (ops h .. h+5) inverted by one launch, or two adjacent ones (h .. h+11)
-      const int nl = unit2_at(f, op.unit_of - 6, IPOKE_UNIT2_INV, lanes.size()) ? 8 : 4;
+      const int nl = unit2_at(f, op.unit_of - 6, IPOKE_UNIT2_INV) ? 8 : 4;
       const int h = nl == 8 ? op.unit_of - 6 : op.unit_of;
       static const int lidx[8] = {0, 1, 3, 4, 6, 7, 9, 10};
-      for (const Ctx& l : lanes) {
-        ipoke_mcf_desc d4[8];
-        for (int k = 0; k < nl; ++k) {
-          const Op& mk = f->ops[h + lidx[k]];
-          mcf_desc(l, mk, d4[k]);
-          if (mk.fuse_act >= 0) { d4[k].post_log_scale = params + f->ops[mk.fuse_act].p_ls; d4[k].post_bias = params + f->ops[mk.fuse_act].p_bias; }
-        }
-        d4[nl - 1].x = l.state(cur); d4[0].y = l.state(cur ^ 1);
-        d4[0].x = d4[nl - 1].x; d4[nl - 1].y = d4[0].y;          // (the shared validator wants input / output on the first / last layer)
-        rc = nl == 8 ? ipoke_macow_unit2_inv(d4, l.dtype, l.stream()) : ipoke_macow_unit_inv(d4, l.dtype, l.stream());
-        if (rc) return rc;
+      ipoke_mcf_desc d4[8];
+      for (int k = 0; k < nl; ++k) {
+        const Op& mk = f->ops[h + lidx[k]];
+        mcf_desc(c, mk, d4[k]);
+        if (mk.fuse_act >= 0) { d4[k].post_log_scale = params + f->ops[mk.fuse_act].p_ls; d4[k].post_bias = params + f->ops[mk.fuse_act].p_bias; }
       }
+      d4[nl - 1].x = c.state(cur); d4[0].y = c.state(cur ^ 1);
+      d4[0].x = d4[nl - 1].x; d4[nl - 1].y = d4[0].y;          // (the shared validator wants input / output on the first / last layer)
+      rc = nl == 8 ? ipoke_macow_unit2_inv(d4, c.dtype, c.stream()) : ipoke_macow_unit_inv(d4, c.dtype, c.stream());
+      if (rc) return rc;
       cur ^= 1;
       i = h;
       continue;
     }
-    for (const Ctx& l : lanes) {
-      const float* in = l.state(cur); float* out = l.state(cur ^ 1);
-      if (op.type == OP_LU) {
-        rc = ipoke_lu_apply(in, out, (int64_t)l.B * l.f->P, l.ld, op.C, lu_mat(l, op, 1), 0, l.stream());
-      } else if (op.type == OP_ACTNORM) {
-        // followed (in this direction) by a coupling: its conditioning operand is written here instead of by an extract_cols launch
-        const Op* nx = actnorm_feeds(i) ? &f->ops[i - 1] : nullptr;
-        rc = ipoke_actnorm_inv_ext(in, out, (int)l.M, l.ld, op.c0, op.Cn, op.p_ls >= 0 ? params + op.p_ls : nullptr,
-                                   op.p_bias >= 0 ? params + op.p_bias : nullptr, op.idx_bwd >= 0 ? perm + op.idx_bwd : nullptr,
-                                   nx ? l.rows(l.plan.tmp_zc, 64L * f->esz) : nullptr, nx ? nx->Kc1 : 0, nx ? nx->z_off : 0,
-                                   nx ? nx->z_stride : 1, nx ? nx->cin : 0, l.dtype, l.stream());
-      } else if (op.type == OP_MCF) {
-        ipoke_mcf_desc d; mcf_desc(l, op, d);
-        d.x = in; d.y = out;
-        rc = ipoke_mcf_inv(&d, l.dtype, l.stream());
-      } else {
-        // the conditioning channels are untouched by the coupling, so the net sees the same input as in forward
-        const bool have_zc = i + 1 < (int)f->ops.size() && (nice_feeds(f->ops[i + 1], op) || actnorm_feeds(i + 1));     // written by the layer inverted just before this one
-        const bool one_launch = nice_fused(l, op);
-        const bool pair = one_launch && nice_pair(l, op), split = pair && f->split_pair_coupling;
-        void* h1 = l.rows(l.plan.tmp_h1, hb);
-        void* h2 = l.rows(l.plan.tmp_h2, (int64_t)op.hidK * f->esz);
-        rc = nice_net(l, op, in, h1, h2, l.rows(l.plan.tmp_zc, 64L * f->esz), have_zc, !one_launch, pair ? (split ? 2 : 0) : 1);
-        if (rc) return rc;
-        ipoke_affine_desc a; nice_affine_desc(l, op, a);
-        const bool feed = i > 0 && nice_feeds(op, f->ops[i - 1]);
-        void* ext = feed ? l.rows(l.plan.tmp_zc, 64L * f->esz) : nullptr;
-        const int ext_ld = feed ? f->ops[i - 1].Kc1 : 0;
-        if (one_launch) {
-          ipoke_coupling_epi e; std::memset(&e, 0, sizeof(e));
-          e.mode = 2; e.in = in; e.out = out; e.ext = ext; e.ext_ld = ext_ld; e.xchg = f->d_cxchg;
-          rc = nice_coupling(l, op, pair, split, h1, h2, false, a, e);     // (nothing reads h2 behind this launch: not stored)
-        } else {
-          rc = ipoke_affine_inv_ext(&a, in, out, l.B, ext, ext_ld, l.dtype, l.stream());
-        }
-      }
+    const float* in = c.state(cur); float* out = c.state(cur ^ 1);
+    if (op.type == OP_LU) {
+      rc = ipoke_lu_apply(in, out, c.M, c.ld, op.C, lu_mat(c, op, 1), 0, c.stream());
+    } else if (op.type == OP_ACTNORM) {
+      // followed (in this direction) by a coupling: its conditioning operand is written here instead of by an extract_cols launch
+      const Op* nx = actnorm_feeds(i) ? &f->ops[i - 1] : nullptr;
+      rc = ipoke_actnorm_inv_ext(in, out, (int)c.M, c.ld, op.c0, op.Cn, op.p_ls >= 0 ? params + op.p_ls : nullptr,
+                                 op.p_bias >= 0 ? params + op.p_bias : nullptr, op.idx_bwd >= 0 ? perm + op.idx_bwd : nullptr,
+                                 nx ? c.at<void>(c.plan.tmp_zc) : nullptr, nx ? nx->Kc1 : 0, nx ? nx->z_off : 0,
+                                 nx ? nx->z_stride : 1, nx ? nx->cin : 0, c.dtype, c.stream());
+    } else if (op.type == OP_MCF) {
+      ipoke_mcf_desc d; mcf_desc(c, op, d);
+      d.x = in; d.y = out;
+      rc = ipoke_mcf_inv(&d, c.dtype, c.stream());
+    } else {
+      // the conditioning channels are untouched by the coupling, so the net sees the same input as in forward
+      const bool have_zc = i + 1 < (int)f->ops.size() && (nice_feeds(f->ops[i + 1], op) || actnorm_feeds(i + 1));     // written by the layer inverted just before this one
+      const bool one_launch = nice_fused(c, op);
+      const bool pair = one_launch && nice_pair(c, op), split = pair && f->split_pair_coupling;
+      void* h1 = c.at<void>(c.plan.tmp_h1);
+      void* h2 = c.at<void>(c.plan.tmp_h2);
+      rc = nice_net(c, op, in, h1, h2, c.at<void>(c.plan.tmp_zc), have_zc, !one_launch, pair ? (split ? 2 : 0) : 1);
       if (rc) return rc;
+      ipoke_affine_desc a; nice_affine_desc(c, op, a);
+      const bool feed = i > 0 && nice_feeds(op, f->ops[i - 1]);
+      void* ext = feed ? c.at<void>(c.plan.tmp_zc) : nullptr;
+      const int ext_ld = feed ? f->ops[i - 1].Kc1 : 0;
+      if (one_launch) {
+        ipoke_coupling_epi e; std::memset(&e, 0, sizeof(e));
+        e.mode = 2; e.in = in; e.out = out; e.ext = ext; e.ext_ld = ext_ld; e.xchg = f->d_cxchg;
+        rc = nice_coupling(c, op, pair, split, h1, h2, false, a, e);     // (nothing reads h2 behind this launch: not stored)
+      } else {
+        rc = ipoke_affine_inv_ext(&a, in, out, c.B, ext, ext_ld, c.dtype, c.stream());
+      }
     }
+    if (rc) return rc;
     cur ^= 1;
   }
-  rc = join_lanes(f, lanes, c.s); if (rc) return rc;
   return ipoke_state_to_nchw(c.state(cur), x_nchw, B, z, f->P, c.ld, stream);
 }
 
@@ -1619,27 +1530,14 @@ static int run_backward(ipoke_flow* f, const float* params, const int32_t* perm,
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Ctx c{f, B, (int64_t)B * f->P, f->cfg.z_channels, f->cfg.dtype, s, params, perm,
         reinterpret_cast<const unsigned char*>(shadow), reinterpret_cast<unsigned char*>(workspace), make_plan(*f, B, 1)};
-  c.Bfull = B;
   const int z = f->cfg.z_channels, hid = f->cfg.hidden;
-  const int64_t hb = (int64_t)hid * f->esz;
   rc = ipoke_nchw_to_state(d_out_nchw, c.at<float>(c.plan.g0), B, z, f->P, c.ld, stream); if (rc) return rc;
   IPK_HIP(hipMemcpyAsync(c.dld(), d_logdet, B * sizeof(float), hipMemcpyDeviceToDevice, s));
-  std::vector<Ctx> lanes;
-  rc = make_lanes(c, f->n_lanes, lanes); if (rc) return rc;
-  rc = fork_lanes(f, s, lanes); if (rc) return rc;
-  // Weight gradients reduce over the whole batch: they run on the side stream (or on lane 0 when it is disabled)
-  // after every lane has produced the operands of that layer.
-  hipStream_t ws_stream = f->use_side ? f->side : s;
-  void* wstream = reinterpret_cast<void*>(ws_stream);
-  // IPOKE_SIDE_DELAY_US (developer A/B): a one-wave spin of that many microseconds at the head of every side-stream batch, so that
-  // the chain's next kernel (a fused MaCowUnit needs whole CUs: 8 waves x 240 registers) takes its CUs before the batch's
-  // hundreds of weight-gradient workgroups are dealt onto every CU
-  static const int side_delay = getenv("IPOKE_SIDE_DELAY_US") ? atoi(getenv("IPOKE_SIDE_DELAY_US")) : 0;
-  auto wgrads_wait_lanes = [&]() -> int {
-    int r0 = join_lanes(f, lanes, ws_stream); if (r0) return r0;
-    if (side_delay > 0 && f->use_side) return ipoke_spin_delay(side_delay, wstream);
-    return IPOKE_OK;
-  };
+  // Weight gradients run on the side stream, after the chain has produced the operands of that layer (on the caller's stream
+  // instead: 116 vs 98 ms when measured; a one-wave spin at the head of every side-stream batch, so that the chain's next kernel takes
+  // its CUs first: no gain).
+  void* wstream = reinterpret_cast<void*>(f->side);
+  auto wgrads_wait_chain = [&]() -> int { return stream_wait(f, f->side, s); };
   // Every parameter gradient is written exactly once per backward (no accumulation, no memset).  The weight gradients
   // of the MCF layers are tiny GEMMs (a handful of output tiles): they are deferred and issued as batched launches,
   // one per run of same-shape layers (= one level), using the per-layer saved operands that stay in the workspace.
@@ -1649,11 +1547,10 @@ static int run_backward(ipoke_flow* f, const float* params, const int32_t* perm,
     if (pend_lo < 0) return IPOKE_OK;
     const Op& op = f->ops[pend_op];
     const int nb = pend_hi - pend_lo + 1;
-    int r = wgrads_wait_lanes(); if (r) return r;
-    static const int mcf_cap = getenv("IPOKE_TN_MAX_WGS") ? atoi(getenv("IPOKE_TN_MAX_WGS")) : 0;
+    int r = wgrads_wait_chain(); if (r) return r;
     ipoke_wgrad_desc w; std::memset(&w, 0, sizeof(w));
     w.NB = B; w.Di = 1; w.Hi = 8; w.Wi = 8; w.Do = 1; w.Ho = 8; w.Wo = 8; w.kd = w.kh = w.kw = 1; w.sd = w.sh = w.sw = 1;
-    w.max_workgroups = f->use_side ? mcf_cap : 0;
+    w.max_workgroups = 0;
     const int K2 = op.H + f->cfg.cond_channels;
     w.a_f32 = 0; w.a_sn = 64L * op.K2p; w.a_sh = 8L * op.K2p; w.a_sw = op.K2p; w.a_sc = 1; w.Kc_real = K2; w.Kc = op.K2p;
     w.ldy = op.K3p; w.Nout = 2 * op.C; w.w_sn = K2; w.w_sc = 1; w.w_st = 0;
@@ -1662,7 +1559,7 @@ static int run_backward(ipoke_flow* f, const float* params, const int32_t* perm,
     if (r) return r;
     std::memset(&w, 0, sizeof(w));
     w.NB = B; w.Di = 1; w.Hi = 8; w.Wi = 8; w.Do = 1; w.Ho = 8; w.Wo = 8; w.kd = 1; w.kh = 2; w.kw = 3; w.sd = w.sh = w.sw = 1;
-    w.max_workgroups = f->use_side ? mcf_cap : 0;
+    w.max_workgroups = 0;
     if (f->mcf_xop) {   // dtype copy [M][Cp] of every layer input, zero padded: the LDS-DMA weight-gradient GEMM
       w.a_f32 = 0; w.a_sn = 64L * op.Cp; w.a_sh = 8L * op.Cp; w.a_sw = op.Cp; w.a_sc = 1; w.Kc_real = op.Cp; w.Kc = op.Cp; w.Kc_store = op.C;
     } else {
@@ -1674,10 +1571,7 @@ static int run_backward(ipoke_flow* f, const float* params, const int32_t* perm,
     pend_lo = pend_hi = pend_op = -1;
     return r;
   };
-  if (f->use_side) {   // the side stream joins after everything already queued on the main stream
-    hipEvent_t e = next_event(f);
-    IPK_HIP(hipEventRecord(e, s)); IPK_HIP(hipStreamWaitEvent(f->side, e, 0));
-  }
+  rc = stream_wait(f, f->side, s); if (rc) return rc;      // the side stream joins after everything already queued on the main stream
   // pieces: groups of consecutive units (steps / priors), last unit first, of roughly equal parameter counts
   hipStream_t rs = ready_stream ? ready_stream : s;
   const std::vector<std::pair<int, int>> pieces = backward_pieces(f, npieces);            // (lowest unit, highest unit)
@@ -1688,10 +1582,12 @@ static int run_backward(ipoke_flow* f, const float* params, const int32_t* perm,
   // 53.2 / 53.2 ms against 49.9 / 49.8.  The launch takes 155 us instead of 53 (the same 2.8 TB/s the stand-alone kernel streams at
   // beside the chain, but on 512 workgroups that hold every CU instead of a 160-workgroup grid), the weight-gradient queue grows from
   // 11.0 to 15.0 ms per half step and the chain's kernels from 22.2 to 24.5 ms; the saved gradient round trip was served by the
-  // memory-side cache anyway.  Off by default.
-  const int wgrad_adam_mode = getenv("IPOKE_WGRAD_ADAM") ? atoi(getenv("IPOKE_WGRAD_ADAM")) : 0;
-  const bool wgrad_adam = wgrad_adam_mode != 0 && f->nadam.on && !getenv("IPOKE_PROBE_SKIP_ADAM") && f->c2_straight &&
-                          c.dtype == IPOKE_BF16 && f->use_side && lanes.size() == 1 && hid % 128 == 0 && (int)f->ajobs.size() == f->n_nice && !f->cfg.condition_nice;
+  // memory-side cache anyway.  Off by default.  A caller option, read here only;
+  // tests/test_full_gpu.py::test_adam_in_the_conv2_weight_gradient_epilogue_trains_bit_identically compares it against the default.
+  const char* wgrad_adam_env = getenv("IPOKE_WGRAD_ADAM");
+  const int wgrad_adam_mode = wgrad_adam_env ? atoi(wgrad_adam_env) : 0;
+  const bool wgrad_adam = wgrad_adam_mode != 0 && f->nadam.on && f->c2_straight && c.dtype == IPOKE_BF16 && hid % 128 == 0 &&
+                          (int)f->ajobs.size() == f->n_nice && !f->cfg.condition_nice;
   std::function<int()> flush_nice_fn = []() { return (int)IPOKE_OK; };
   auto native_adam_range = [&](int64_t b0, int64_t b1, int max_blocks) -> int {
     const ipoke_flow::NativeAdam& A = f->nadam;
@@ -1708,11 +1604,8 @@ static int run_backward(ipoke_flow* f, const float* params, const int32_t* perm,
   auto finish_piece = [&](int lvl_lo, int lvl_hi, int piece) -> int {
     int r = flush_nice_fn(); if (r) return r;
     r = flush_mcf(); if (r) return r;
-    r = join_lanes(f, lanes, rs); if (r) return r;                  // the chain up to here ...
-    if (f->use_side && f->side != rs) {                              // ... and the weight gradients of this piece
-      hipEvent_t e = next_event(f);
-      IPK_HIP(hipEventRecord(e, f->side)); IPK_HIP(hipStreamWaitEvent(rs, e, 0));
-    }
+    r = stream_wait(f, rs, s); if (r) return r;                     // the chain up to here ...
+    r = stream_wait(f, rs, f->side); if (r) return r;               // ... and the weight gradients of this piece
     void* rstream = reinterpret_cast<void*>(rs);
     // bias / ActNorm parameter gradients: multi-tensor reduction over the per-sample partial sums of the piece's layers
     const int r0 = f->red_first[f->units[lvl_lo].op_lo], r1 = f->red_first[f->units[lvl_hi].op_hi];
@@ -1739,21 +1632,14 @@ static int run_backward(ipoke_flow* f, const float* params, const int32_t* perm,
                                    rw1[kind] - rw0[kind], rstream);
       if (r) return r;
     }
-    static const bool probe_skip_adam = getenv("IPOKE_PROBE_SKIP_ADAM") != nullptr;      // developer probe: what the optimizer costs the step (parameters stay put)
     // (Moving the first k pieces' update + refresh behind the last piece's, into the step-boundary hole, was measured in round 6 and
     // removed: 50.9 / 52.3 / 54.1 ms at k = 4 / 8 / 12 against 49.5 -- profiles/r06_ab_lines.txt.)
-    if (f->nadam.on && !probe_skip_adam) {
+    // (The optimizer of all but the last three pieces on a smaller grid: 61.0 / 55.1 / 54.2 ms at 64 / 96 / 128 blocks against 54.4-54.6.)
+    if (f->nadam.on) {
       // single-GPU training: the update of the piece's ranges and the refresh of their shadows, natively, on the ready stream
-      ipoke_flow::NativeAdam A = f->nadam;
-      {   // developer A/B (IPOKE_ADAM_EARLY_BLOCKS=n, IPOKE_ADAM_LATE_PIECES=k): the optimizer of all but the last k pieces on a smaller grid --
-          // a lower, steadier HBM rate beside the chain; the last pieces (whose parameters the next forward needs first) at full rate
-        static const int early = getenv("IPOKE_ADAM_EARLY_BLOCKS") ? atoi(getenv("IPOKE_ADAM_EARLY_BLOCKS")) : 0;
-        static const int late = getenv("IPOKE_ADAM_LATE_PIECES") ? atoi(getenv("IPOKE_ADAM_LATE_PIECES")) : 3;
-        if (early > 0 && piece < (int)pieces.size() - late) A.max_blocks = early;
-      }
       for (int kind = 0; kind < 3; ++kind) {
         if (p0[kind] < 0 || p1[kind] <= p0[kind]) continue;
-        r = native_adam_range(p0[kind], p1[kind], A.max_blocks); if (r) return r;
+        r = native_adam_range(p0[kind], p1[kind], f->nadam.max_blocks); if (r) return r;
       }
     }
     if (ready)
@@ -1767,10 +1653,9 @@ static int run_backward(ipoke_flow* f, const float* params, const int32_t* perm,
   std::vector<int> pend_nice;
   auto flush_nice = [&]() -> int {
     if (pend_nice.empty()) return IPOKE_OK;
-    int rc = wgrads_wait_lanes(); if (rc) return rc;
+    int rc = wgrads_wait_chain(); if (rc) return rc;
     // cap on workgroups per weight-gradient launch (leaving CUs to the chain): measured 79.6 ms uncapped, 81.0 at 128,
-    // 88.7 at 96 -- the side stream becomes the critical path, so off by default
-    static const int tn_cap = getenv("IPOKE_TN_MAX_WGS") ? atoi(getenv("IPOKE_TN_MAX_WGS")) : 0;
+    // 88.7 at 96 -- the side stream becomes the critical path, so max_workgroups stays 0
     // The pending couplings (a pair or two pairs of one flow step: same widths) go out as three batched launches, one per
     // convolution, blockIdx.z = coupling: conv1 (48 output tiles) and conv3 (144) are latency chains of 20 reduction
     // stages that leave most of the chip idle when launched one coupling at a time.
@@ -1790,7 +1675,7 @@ static int run_backward(ipoke_flow* f, const float* params, const int32_t* perm,
         std::memset(&w, 0, sizeof(w));
         w.NB = B; w.Di = 1; w.Hi = 8; w.Wi = 8; w.Do = 1; w.Ho = 8; w.Wo = 8; w.kd = 1; w.kh = w.kw = k;
         w.sd = w.sh = w.sw = 1; w.ph = w.pw = pad;
-        w.max_workgroups = f->use_side ? tn_cap : 0;
+        w.max_workgroups = 0;
       };
       auto entries = [&](int k) {
         return reinterpret_cast<const unsigned char*>(f->d_ntab[k]) + (size_t)lo * ipoke_wgrad_batch_entry_size();
@@ -1831,12 +1716,12 @@ static int run_backward(ipoke_flow* f, const float* params, const int32_t* perm,
   flush_nice_fn = flush_nice;
   // Every flush costs the CHAIN an event record (the side stream must see the couplings' operands): a barrier packet with a completion
   // signal between two chain kernels, ~10 us of queue time each (profiles/r03_bench_trace_gaps.txt: 112 gaps of 12.8 us per step in
-  // front of the fused units).  IPOKE_NICE_FLUSH_MIN couplings are collected before the chain pays for one (the end of a piece always
+  // front of the fused units).  kNiceFlushMin couplings are collected before the chain pays for one (the end of a piece always
   // flushes: finish_piece).
   // round 6 (with the stationary-input conv1 / conv3 weight gradients: 32 workgroups per problem): four couplings per batch, 48.83 / 48.62
   // against 48.98 / 49.04 ms at two (one call); 3 / 6 / 8: 48.9 / 48.8 / 48.8
-  static const int flush_min = getenv("IPOKE_NICE_FLUSH_MIN") ? atoi(getenv("IPOKE_NICE_FLUSH_MIN")) : 4;
-  auto maybe_flush_nice = [&]() -> int { return (int)pend_nice.size() >= flush_min ? flush_nice() : (int)IPOKE_OK; };
+  constexpr int kNiceFlushMin = 4;
+  auto maybe_flush_nice = [&]() -> int { return (int)pend_nice.size() >= kNiceFlushMin ? flush_nice() : (int)IPOKE_OK; };
   size_t pk = 0;
   int cur = 0;
   int pending_an = -1;              // ActNorm op whose backward is carried by the next (lower) coupling's launch
@@ -1844,45 +1729,43 @@ static int run_backward(ipoke_flow* f, const float* params, const int32_t* perm,
   for (int i = (int)f->ops.size() - 1; i >= 0; --i) {
     const Op& op = f->ops[i];
     if (op.unit_of >= 0 && i == op.unit_of + 5) {     // whole MaCowUnit (ops h .. h+5) differentiated by one launch, or two adjacent ones (h .. h+11)
-      const int nl = unit2_at(f, op.unit_of - 6, IPOKE_UNIT2_BWD, lanes.size()) ? 8 : 4;
+      const int nl = unit2_at(f, op.unit_of - 6, IPOKE_UNIT2_BWD) ? 8 : 4;
       const int h = nl == 8 ? op.unit_of - 6 : op.unit_of;
       rc = maybe_flush_nice(); if (rc) return rc;
       static const int lidx[8] = {0, 1, 3, 4, 6, 7, 9, 10};
-      for (const Ctx& l : lanes) {
-        ipoke_mcf_desc d4[8];
-        for (int k = 0; k < nl; ++k) {
-          const int j = h + lidx[k];
-          const Op& mk = f->ops[j];
-          mcf_desc(l, mk, d4[k]);
-          d4[k].x = l.state(j);
-          d4[k].a2_save = l.rows(mk.ws_a, (int64_t)mk.K2p * f->esz); d4[k].scale_save = l.rowsf(mk.ws_b, mk.C);
-          d4[k].dparams_save = l.rows(mk.ws_c, (int64_t)mk.K3p * f->esz); d4[k].dc_save = l.rows(mk.ws_d, (int64_t)mk.Hq * f->esz);
-          if (f->mcf_xop) d4[k].x_op_save = l.rows(mk.ws_e, (int64_t)mk.Cp * f->esz);
-          d4[k].dbias_part = l.dbp(j, 2 * mk.C, f->unit_split);
-          if (mk.fuse_act >= 0) {
-            const Op& an = f->ops[mk.fuse_act];
-            d4[k].post_log_scale = params + an.p_ls; d4[k].post_bias = params + an.p_bias;
-            d4[k].y_post = l.state(j + 2);
-            d4[k].post_part = l.dbp(mk.fuse_act, 2 * an.Cn, f->unit_split);
-          }
+      ipoke_mcf_desc d4[8];
+      for (int k = 0; k < nl; ++k) {
+        const int j = h + lidx[k];
+        const Op& mk = f->ops[j];
+        mcf_desc(c, mk, d4[k]);
+        d4[k].x = c.state(j);
+        d4[k].a2_save = c.at<void>(mk.ws_a); d4[k].scale_save = c.at<float>(mk.ws_b);
+        d4[k].dparams_save = c.at<void>(mk.ws_c); d4[k].dc_save = c.at<void>(mk.ws_d);
+        if (f->mcf_xop) d4[k].x_op_save = c.at<void>(mk.ws_e);
+        d4[k].dbias_part = c.dbp(j);
+        if (mk.fuse_act >= 0) {
+          const Op& an = f->ops[mk.fuse_act];
+          d4[k].post_log_scale = params + an.p_ls; d4[k].post_bias = params + an.p_bias;
+          d4[k].y_post = c.state(j + 2);
+          d4[k].post_part = c.dbp(mk.fuse_act);
         }
-        d4[nl - 1].dy = l.rowsf(goff[cur], l.ld); d4[0].dx = l.rowsf(goff[cur ^ 1], l.ld); d4[0].dld = l.dld();
-        IPK_REQUIRE(f->unit_split == 1 || f->d_xchg, "row-split unit launches without exchange scratch (ensure_tables)");
-        if (f->unit_split > 1) { d4[0].split = f->unit_split; d4[0].xchg = f->d_xchg; }
-        ipoke_unit_pair_desc pq;
-        if (h >= 2 && f->ops[h - 1].pair_unit == h) {     // the (coupling, ActNorm) pair in front of the unit rides along
-          const Op& an = f->ops[h - 1]; const Op& cp = f->ops[h - 2];
-          std::memset(&pq, 0, sizeof(pq));
-          pq.an_log_scale = an.p_ls >= 0 ? params + an.p_ls : nullptr; pq.an_idx = an.idx_fwd >= 0 ? perm + an.idx_fwd : nullptr;
-          pq.an_x = l.state(h - 1); pq.an_part = an.p_ls >= 0 ? l.dbp(h - 1, 2 * an.Cn, f->unit_split) : nullptr;
-          pq.Cp = cp.cout; pq.t_off = cp.t_off; pq.t_stride = cp.t_stride; pq.x0 = l.state(h - 2); pq.scale = l.rowsf(cp.ws_c, cp.cout);
-          pq.dparams = l.rows(cp.ws_d, (int64_t)cp.Kc3 * f->esz); pq.ldp = cp.Kc3; pq.dbias_part = l.dbp(h - 2, 2 * cp.cout, f->unit_split);
-          pq.dx = d4[0].dx;
-          d4[0].pair = &pq;
-        }
-        rc = nl == 8 ? ipoke_macow_unit2_bwd(d4, l.dtype, l.stream()) : ipoke_macow_unit_bwd(d4, l.dtype, l.stream());
-        if (rc) return rc;
       }
+      d4[nl - 1].dy = c.at<float>(goff[cur]); d4[0].dx = c.at<float>(goff[cur ^ 1]); d4[0].dld = c.dld();
+      IPK_REQUIRE(f->unit_split == 1 || f->d_xchg, "row-split unit launches without exchange scratch (ensure_tables)");
+      if (f->unit_split > 1) { d4[0].split = f->unit_split; d4[0].xchg = f->d_xchg; }
+      ipoke_unit_pair_desc pq;
+      if (h >= 2 && f->ops[h - 1].pair_unit == h) {     // the (coupling, ActNorm) pair in front of the unit rides along
+        const Op& an = f->ops[h - 1]; const Op& cp = f->ops[h - 2];
+        std::memset(&pq, 0, sizeof(pq));
+        pq.an_log_scale = an.p_ls >= 0 ? params + an.p_ls : nullptr; pq.an_idx = an.idx_fwd >= 0 ? perm + an.idx_fwd : nullptr;
+        pq.an_x = c.state(h - 1); pq.an_part = an.p_ls >= 0 ? c.dbp(h - 1) : nullptr;
+        pq.Cp = cp.cout; pq.t_off = cp.t_off; pq.t_stride = cp.t_stride; pq.x0 = c.state(h - 2); pq.scale = c.at<float>(cp.ws_c);
+        pq.dparams = c.at<void>(cp.ws_d); pq.ldp = cp.Kc3; pq.dbias_part = c.dbp(h - 2);
+        pq.dx = d4[0].dx;
+        d4[0].pair = &pq;
+      }
+      rc = nl == 8 ? ipoke_macow_unit2_bwd(d4, c.dtype, c.stream()) : ipoke_macow_unit_bwd(d4, c.dtype, c.stream());
+      if (rc) return rc;
       for (int k = nl - 1; k >= 0; --k) {            // weight gradients: deferred, batched per run of same-width layers
         const int j = h + lidx[k];
         const Op& mk = f->ops[j];
@@ -1906,86 +1789,82 @@ static int run_backward(ipoke_flow* f, const float* params, const int32_t* perm,
     }
     if (op.type == OP_ACTNORM && op.an_prev >= 0 && i != f->units[pieces[pk].first].op_lo) { pending_an = i; continue; }
     if (op.type != OP_NICE) { rc = maybe_flush_nice(); if (rc) return rc; }
-    for (const Ctx& l : lanes) {
-      const bool by_unit = op.type == OP_NICE && op.pair_unit >= 0;      // dx / dparams / partials of this coupling were written by a unit's launch
-      const float* gin = l.rowsf(goff[cur], l.ld); float* gout = l.rowsf(goff[by_unit ? cur : cur ^ 1], l.ld);
-      const float* xin = l.state(i);                 // saved input of op i
-      if (op.type == OP_LU) {
-        // dx = dy W (W^T applied per position); parameter gradients straight into the flat buffer (the forward pass of
-        // this step left [W | W^-1 | wl | wu] in the workspace)
-        rc = ipoke_lu_apply(gin, gout, (int64_t)l.B * l.f->P, l.ld, op.C, lu_mat(l, op, 0), 1, l.stream()); if (rc) return rc;
-        rc = ipoke_lu_wgrad(gin, xin, l.B, f->P, l.ld, params, f->fbuf, l.at<float>(l.plan.lu),
-                            reinterpret_cast<const unsigned char*>(f->d_lujobs) + (size_t)op.lu_idx * sizeof(LuJobH), l.dld(), grads,
-                            l.stream());
-        if (rc) return rc;
-      } else if (op.type == OP_ACTNORM) {
-        rc = ipoke_actnorm_bwd(gin, xin, gout, (int)l.M, l.ld, op.c0, op.Cn, op.p_ls >= 0 ? params + op.p_ls : nullptr,
-                               op.idx_fwd >= 0 ? perm + op.idx_fwd : nullptr, l.dld(), l.B, f->P, l.dbp(i, 2 * op.Cn), l.stream());
-        if (rc) return rc;
-      } else if (op.type == OP_MCF) {
-        ipoke_mcf_desc d; mcf_desc(l, op, d);
-        d.x = xin; d.dy = gin; d.dx = gout; d.dld = l.dld();
-        d.a2_save = l.rows(op.ws_a, (int64_t)op.K2p * f->esz); d.scale_save = l.rowsf(op.ws_b, op.C);
-        d.dparams_save = l.rows(op.ws_c, (int64_t)op.K3p * f->esz); d.dc_save = l.rows(op.ws_d, (int64_t)op.Hq * f->esz);
-        d.dbias_part = l.dbp(i, 2 * op.C);
-        d.y = gout;   // unused by the backward kernel, must be non-null for the shared validator
-        if (op.fuse_act >= 0) {
-          const Op& an = f->ops[op.fuse_act];
-          d.post_log_scale = params + an.p_ls; d.post_bias = params + an.p_bias;
-          d.y_post = l.state(i + 2);                 // saved output of the fused pair
-          d.post_part = l.dbp(op.fuse_act, 2 * an.Cn);
-        }
-        rc = ipoke_mcf_bwd(&d, l.dtype, l.stream()); if (rc) return rc;
+    const bool by_unit = op.type == OP_NICE && op.pair_unit >= 0;      // dx / dparams / partials of this coupling were written by a unit's launch
+    const float* gin = c.at<float>(goff[cur]); float* gout = c.at<float>(goff[by_unit ? cur : cur ^ 1]);
+    const float* xin = c.state(i);                 // saved input of op i
+    if (op.type == OP_LU) {
+      // dx = dy W (W^T applied per position); parameter gradients straight into the flat buffer (the forward pass of
+      // this step left [W | W^-1 | wl | wu] in the workspace)
+      rc = ipoke_lu_apply(gin, gout, c.M, c.ld, op.C, lu_mat(c, op, 0), 1, c.stream()); if (rc) return rc;
+      rc = ipoke_lu_wgrad(gin, xin, c.B, f->P, c.ld, params, f->fbuf, c.at<float>(c.plan.lu),
+                          reinterpret_cast<const unsigned char*>(f->d_lujobs) + (size_t)op.lu_idx * sizeof(LuJobH), c.dld(), grads,
+                          c.stream());
+      if (rc) return rc;
+    } else if (op.type == OP_ACTNORM) {
+      rc = ipoke_actnorm_bwd(gin, xin, gout, (int)c.M, c.ld, op.c0, op.Cn, op.p_ls >= 0 ? params + op.p_ls : nullptr,
+                             op.idx_fwd >= 0 ? perm + op.idx_fwd : nullptr, c.dld(), c.B, f->P, c.dbp(i), c.stream());
+      if (rc) return rc;
+    } else if (op.type == OP_MCF) {
+      ipoke_mcf_desc d; mcf_desc(c, op, d);
+      d.x = xin; d.dy = gin; d.dx = gout; d.dld = c.dld();
+      d.a2_save = c.at<void>(op.ws_a); d.scale_save = c.at<float>(op.ws_b);
+      d.dparams_save = c.at<void>(op.ws_c); d.dc_save = c.at<void>(op.ws_d);
+      d.dbias_part = c.dbp(i);
+      d.y = gout;   // unused by the backward kernel, must be non-null for the shared validator
+      if (op.fuse_act >= 0) {
+        const Op& an = f->ops[op.fuse_act];
+        d.post_log_scale = params + an.p_ls; d.post_bias = params + an.p_bias;
+        d.y_post = c.state(i + 2);                 // saved output of the fused pair
+        d.post_part = c.dbp(op.fuse_act);
+      }
+      rc = ipoke_mcf_bwd(&d, c.dtype, c.stream()); if (rc) return rc;
+    } else {
+      const void* h1 = c.at<void>(op.ws_a); const void* h2 = c.at<void>(op.ws_b);
+      void* dprm = c.at<void>(op.ws_d); void* dp2 = c.at<void>(op.ws_e); void* dp1 = c.at<void>(op.ws_f);
+      if (by_unit) {
+        rc = IPOKE_OK;
+      } else if (pending_an == i + 1) {
+        const Op& an = f->ops[i + 1];
+        rc = ipoke_actnorm_affine_bwd(an.c0, an.Cn, an.p_ls >= 0 ? params + an.p_ls : nullptr, an.idx_fwd >= 0 ? perm + an.idx_fwd : nullptr,
+                                      gin, c.state(i + 1), an.p_ls >= 0 ? c.dbp(i + 1) : nullptr, op.cout, op.t_off, op.t_stride,
+                                      f->P, c.ld, xin, c.at<float>(op.ws_c), c.dld(), gout, dprm, op.Kc3, c.dbp(i), c.B,
+                                      c.dtype, c.stream());
       } else {
-        const void* h1 = l.rows(op.ws_a, hb); const void* h2 = l.rows(op.ws_b, (int64_t)op.hidK * f->esz);
-        void* dprm = l.rows(op.ws_d, (int64_t)op.Kc3 * f->esz); void* dp2 = l.rows(op.ws_e, hb); void* dp1 = l.rows(op.ws_f, hb);
-        if (by_unit) {
-          rc = IPOKE_OK;
-        } else if (pending_an == i + 1) {
-          const Op& an = f->ops[i + 1];
-          rc = ipoke_actnorm_affine_bwd(an.c0, an.Cn, an.p_ls >= 0 ? params + an.p_ls : nullptr, an.idx_fwd >= 0 ? perm + an.idx_fwd : nullptr,
-                                        gin, l.state(i + 1), an.p_ls >= 0 ? l.dbp(i + 1, 2 * an.Cn) : nullptr, op.cout, op.t_off, op.t_stride,
-                                        f->P, l.ld, xin, l.rowsf(op.ws_c, op.cout), l.dld(), gout, dprm, op.Kc3, l.dbp(i, 2 * op.cout), l.B,
-                                        l.dtype, l.stream());
-        } else {
-          rc = ipoke_affine_bwd(op.cout, op.t_off, op.t_stride, f->P, l.ld, gin, xin, l.rowsf(op.ws_c, op.cout), l.dld(), gout, dprm,
-                                op.Kc3, l.dbp(i, 2 * op.cout), l.B, l.dtype, l.stream());
-        }
-        if (rc) return rc;
-        ipoke_conv_desc d;
-        // conv3 data gradient, times ELU'(h2)
-        set_conv8(d, l.B, 3, 1); d.transposed = 1;
-        set_a_dense(d, dprm, op.Kc3, op.Kc3);
-        d.W = l.sh(op.sh_c3t); d.ldw = 9 * op.Kc3; d.Nout = hid; d.dact = h2; d.ld_dact = op.hidK; d.dact_act = IPOKE_ACT_ELU;
-        d.C = dp2; d.ldc = hid;
-        rc = ipoke_conv_forward(&d, l.dtype, l.stream()); if (rc) return rc;
-        // conv2 data gradient, times ELU'(h1), and conv1 data gradient accumulated into the conditioning channels
-        ipoke_conv_desc d1;
-        set_conv8(d, l.B, 1, 0);
-        set_a_dense(d, dp2, hid, hid);
-        if (f->c2_straight) { d.W = l.sh(op.sh_c2); d.w_kmajor = 1; }      // W2[out][in] read K-major: no transposed copy exists
-        else d.W = l.sh(op.sh_c2t);
-        d.ldw = hid; d.Nout = hid; d.dact = h1; d.ld_dact = hid; d.dact_act = IPOKE_ACT_ELU;
-        d.C = dp1; d.ldc = hid;
-        set_conv8(d1, l.B, 3, 1); d1.transposed = 1;
-        set_a_dense(d1, dp1, hid, hid);
-        d1.W = l.sh(op.sh_c1t); d1.ldw = 9 * hid; d1.Nout = op.cin; d1.C = gout; d1.c_f32 = 1; d1.c_accumulate = 1; d1.ldc = l.ld;
-        d1.c_coff = op.z_off; d1.c_cstride = op.z_stride; d1.splitk = nice_splitk(l);
-        // the K slices meet in the engine's scratch and are summed in a fixed order (bit-reproducible steps); sub-batch lanes
-        // (developer switch) run several of these launches at once and keep the atomic form
-        if (lanes.size() == 1 && op.cin <= 64) { d1.acc_scratch = f->d_acc; d1.acc_scratch_bytes = f->acc_bytes; }
-        // one launch where the pair kernel takes the shape (c2: B <= 32 at hidden 2048, cin <= 32): conv1's slices are the GEMM's column tiles
-        if (lanes.size() == 1 && f->c2_straight && f->d_acc && !f->cfg.condition_nice &&
-            ipoke_conv_pair_dgrad_applicable((int)l.M, hid, op.cin, l.dtype, f->acc_bytes)) {
-          if (!f->split_pair_dgrad) {
-            rc = ipoke_conv_pair_dgrad(&d, &d1, l.dtype, l.stream()); if (rc) return rc;
-            continue;
-          }
-          d1.splitk = hid / 128;      // test hook: the two launches with the pair kernel's slices, i.e. the same sums in the same order
-        }
-        rc = ipoke_conv_forward(&d, l.dtype, l.stream()); if (rc) return rc;
+        rc = ipoke_affine_bwd(op.cout, op.t_off, op.t_stride, f->P, c.ld, gin, xin, c.at<float>(op.ws_c), c.dld(), gout, dprm,
+                              op.Kc3, c.dbp(i), c.B, c.dtype, c.stream());
+      }
+      if (rc) return rc;
+      ipoke_conv_desc d;
+      // conv3 data gradient, times ELU'(h2)
+      set_conv8(d, c.B, 3, 1); d.transposed = 1;
+      set_a_dense(d, dprm, op.Kc3, op.Kc3);
+      d.W = c.sh(op.sh_c3t); d.ldw = 9 * op.Kc3; d.Nout = hid; d.dact = h2; d.ld_dact = op.hidK; d.dact_act = IPOKE_ACT_ELU;
+      d.C = dp2; d.ldc = hid;
+      rc = ipoke_conv_forward(&d, c.dtype, c.stream()); if (rc) return rc;
+      // conv2 data gradient, times ELU'(h1), and conv1 data gradient accumulated into the conditioning channels
+      ipoke_conv_desc d1;
+      set_conv8(d, c.B, 1, 0);
+      set_a_dense(d, dp2, hid, hid);
+      if (f->c2_straight) { d.W = c.sh(op.sh_c2); d.w_kmajor = 1; }      // W2[out][in] read K-major: no transposed copy exists
+      else d.W = c.sh(op.sh_c2t);
+      d.ldw = hid; d.Nout = hid; d.dact = h1; d.ld_dact = hid; d.dact_act = IPOKE_ACT_ELU;
+      d.C = dp1; d.ldc = hid;
+      set_conv8(d1, c.B, 3, 1); d1.transposed = 1;
+      set_a_dense(d1, dp1, hid, hid);
+      d1.W = c.sh(op.sh_c1t); d1.ldw = 9 * hid; d1.Nout = op.cin; d1.C = gout; d1.c_f32 = 1; d1.c_accumulate = 1; d1.ldc = c.ld;
+      d1.c_coff = op.z_off; d1.c_cstride = op.z_stride; d1.splitk = nice_splitk(c);
+      // the K slices meet in the engine's scratch and are summed in a fixed order (bit-reproducible steps); wider inputs keep the atomic form
+      if (op.cin <= 64) { d1.acc_scratch = f->d_acc; d1.acc_scratch_bytes = f->acc_bytes; }
+      // one launch where the pair kernel takes the shape (c2: B <= 32 at hidden 2048, cin <= 32): conv1's slices are the GEMM's column tiles
+      const bool pair_dgrad = f->c2_straight && !f->cfg.condition_nice &&
+                              ipoke_conv_pair_dgrad_applicable((int)c.M, hid, op.cin, c.dtype, f->acc_bytes);
+      if (pair_dgrad && !f->split_pair_dgrad) {
+        rc = ipoke_conv_pair_dgrad(&d, &d1, c.dtype, c.stream()); if (rc) return rc;
+      } else {
+        if (pair_dgrad) d1.splitk = hid / 128;      // test hook: the two launches with the pair kernel's slices, i.e. the same sums in the same order
+        rc = ipoke_conv_forward(&d, c.dtype, c.stream()); if (rc) return rc;
         d = d1;
-        rc = ipoke_conv_forward(&d, l.dtype, l.stream()); if (rc) return rc;
+        rc = ipoke_conv_forward(&d, c.dtype, c.stream()); if (rc) return rc;
       }
     }
     if (op.type == OP_MCF) {
@@ -2003,12 +1882,10 @@ static int run_backward(ipoke_flow* f, const float* params, const int32_t* perm,
       ++pk;
     }
   }
-  static const bool probe_no_join = getenv("IPOKE_PROBE_NO_READY_JOIN") != nullptr;      // developer probe (WRONG results): the caller's stream does not wait for the ready stream
-  if (rs != s && !probe_no_join) {        // later work on the caller's stream (optimizer step) sees every gradient
-    hipEvent_t e = next_event(f);
-    IPK_HIP(hipEventRecord(e, rs)); IPK_HIP(hipStreamWaitEvent(s, e, 0));
-  }
-  if (dx_nchw) { rc = ipoke_state_to_nchw(c.rowsf(goff[cur], c.ld), dx_nchw, B, z, f->P, c.ld, stream); if (rc) return rc; }
+  // later work on the caller's stream (optimizer step) sees every gradient (this wait costs the next forward pass 0.25 ms; the
+  // engine-issued optimizer and operand refresh as a whole 6.4 of 50.9 ms)
+  rc = stream_wait(f, s, rs); if (rc) return rc;
+  if (dx_nchw) { rc = ipoke_state_to_nchw(c.at<float>(goff[cur]), dx_nchw, B, z, f->P, c.ld, stream); if (rc) return rc; }
   return IPOKE_OK;
 }
 

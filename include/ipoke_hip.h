@@ -71,7 +71,12 @@ typedef struct {
   int32_t Nout;
   /* epilogue */
   const float* bias;       /* [Nout] or NULL                                                       */
-  int32_t act;             /* IPOKE_ACT_* applied after bias                                        */
+  int32_t act;             /* IPOKE_ACT_* applied after bias.  Contract (tests/test_conv_real_gpu.py): with c_f32 = 1 the
+                              activation is accurate to a few fp32 ulps of its value whatever the compute dtype (expm1f, tanhf,
+                              expf -- ELU keeps its relative accuracy for |x| -> 0).  Only a bf16 store of a bf16 launch may take
+                              ELU as exp(x) - 1, whose error is absolute (about 2^-24, below half a bf16 ulp of the result for
+                              |x| >= 2^-15).  The pre-activation value is within 4 - 6 fp32 ulps of |s| sum |x w| + |b| in both
+                              dtypes ("Real-valued operands").                                                */
   const void* dact;        /* optional [M][ld_dact] dtype: multiply by act'(saved output) (dgrad)  */
   int32_t ld_dact, dact_act;
   void* C;                 /* output                                                                */

@@ -150,6 +150,12 @@ template <typename T> struct Pack4;     // 4 consecutive outputs of the compute 
 template <> struct Pack4<bf16_t> { typedef __attribute__((ext_vector_type(4))) __bf16 type; };
 template <> struct Pack4<float> { typedef f32x4 type; };
 
+// Contract (tests/test_conv_real_gpu.py): an fp32 store carries every activation to a few fp32 ulps of its value, whatever the
+// compute dtype (act_apply: expm1f, tanhf, expf).  Only the bf16 STORE of a bf16 launch may take ELU as exp(x) - 1: that form cancels
+// for small |x| and its error is absolute, about 2^-24 -- below half a bf16 ulp of the result for |x| >= 2^-15 and never more than
+// four times what fl32(exp32(x)) - 1 loses on the host, which is what the tests allow it.  fast_act is that bf16-store form: the
+// general sweep of nt_epilogue branches to expm1f for an fp32 store, and the halo / halo16 / c64 kernels, whose sweeps call
+// fast_act unconditionally, are not dispatched for an ELU launch that stores fp32 (elu_f32_store below).
 template <typename T>
 __device__ __forceinline__ float fast_act(int act, float x) {
   // bf16 outputs carry 8 mantissa bits: the hardware exp is more than accurate enough for ELU there
@@ -369,7 +375,11 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[MREP
       if (full) v += *reinterpret_cast<const f32x4*>(p.bias + n);
       else for (int r = 0; r < 4; ++r) if (n + r < p.Nout) v[r] += p.bias[n + r];
     }
-    if (p.act != IPOKE_ACT_NONE) {
+    if (sizeof(T) == 2 && p.c_f32 && p.act == IPOKE_ACT_ELU) {
+      // fp32 store of a bf16 launch: expm1f, not fast_act's exp(x) - 1 (one copy of it: this sweep is not the hot path)
+#pragma nounroll
+      for (int r = 0; r < 4; ++r) { const float x = v[r]; v[r] = x > 0.f ? x : expm1f(x); }
+    } else if (p.act != IPOKE_ACT_NONE) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[r] = fast_act<T>(p.act, v[r]);
     }
@@ -413,6 +423,30 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[MREP
           if (n + r < p.n_pad) Cp[r] = ET<T>::from_f32(v[r]);
       }
     }
+  }
+}
+
+// f32 launches: v_mfma_f32_16x16x4_f32 is a k-ordered fmaf chain that rounds once per product, so one accumulator over the whole
+// reduction loses several ulp32 of sum |x w| (4.6 measured at K = 288, tests/test_conv_real_gpu.py).  The f32 instantiations of the
+// two implicit-GEMM kernels therefore close the chain after every pass of their K loop (32 or 64 elements) and add it to a second
+// accumulator: the chain the rounding errors grow along is K / 32 long instead of K (about 1 ulp32 of sum |x w|).  bf16 launches
+// round once per 32-element matrix-core step already and keep the single accumulator.
+template <typename T, int MREP, int NREP>
+__device__ __forceinline__ void fold_chain(f32x4 (&tot)[sizeof(T) == 4 ? MREP : 1][sizeof(T) == 4 ? NREP : 1], f32x4 (&acc)[MREP][NREP]) {
+  if constexpr (sizeof(T) == 4) {
+#pragma unroll
+    for (int i = 0; i < MREP; ++i)
+#pragma unroll
+      for (int j = 0; j < NREP; ++j) { tot[i][j] += acc[i][j]; acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  }
+}
+template <typename T, int MREP, int NREP>
+__device__ __forceinline__ void take_chain(f32x4 (&tot)[sizeof(T) == 4 ? MREP : 1][sizeof(T) == 4 ? NREP : 1], f32x4 (&acc)[MREP][NREP]) {
+  if constexpr (sizeof(T) == 4) {
+#pragma unroll
+    for (int i = 0; i < MREP; ++i)
+#pragma unroll
+      for (int j = 0; j < NREP; ++j) acc[i][j] = tot[i][j];
   }
 }
 
@@ -524,6 +558,11 @@ __global__ __launch_bounds__(256) void igemm_nt_kernel(const NtParams p) {
 #pragma unroll
     for (int j = 0; j < NREP; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  f32x4 tot[sizeof(T) == 4 ? MREP : 1][sizeof(T) == 4 ? NREP : 1];
+#pragma unroll
+  for (int i = 0; i < (sizeof(T) == 4 ? MREP : 1); ++i)
+#pragma unroll
+    for (int j = 0; j < (sizeof(T) == 4 ? NREP : 1); ++j) tot[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (kb_begin < kb_end) {
     load_stage();
     store_stage(0);
@@ -546,10 +585,12 @@ __global__ __launch_bounds__(256) void igemm_nt_kernel(const NtParams p) {
 #pragma unroll
           for (int j = 0; j < NREP; ++j) mma64(fa[i], fb[j], acc[i][j]);
       }
+      fold_chain<T, MREP, NREP>(tot, acc);
       if (more) store_stage(buf ^ 1);
       __syncthreads();
     }
   }
+  take_chain<T, MREP, NREP>(tot, acc);
 
   nt_epilogue<T, WM, WN, MREP, NREP, WM * WN * 64, NtDet<WM, WN, MREP, NREP>::value>(p, acc, smem, m0, n0, wm, wn, z);
 }
@@ -711,6 +752,11 @@ __global__ __launch_bounds__(WM * WN * WK * 64) void igemm_nt_glds_kernel(const 
 #pragma unroll
     for (int j = 0; j < NREP; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  f32x4 tot[sizeof(T) == 4 ? MREP : 1][sizeof(T) == 4 ? NREP : 1];
+#pragma unroll
+  for (int i = 0; i < (sizeof(T) == 4 ? MREP : 1); ++i)
+#pragma unroll
+    for (int j = 0; j < (sizeof(T) == 4 ? NREP : 1); ++j) tot[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   // loop-invariant LDS offsets of this lane's fragments (XOR swizzle folded in)
   int a_rd[MREP][2], b_rd[NREP][2];
 #pragma unroll
@@ -792,7 +838,9 @@ __global__ __launch_bounds__(WM * WN * WK * 64) void igemm_nt_glds_kernel(const 
         }
       }
     }
+    fold_chain<T, MREP, NREP>(tot, acc);
   }
+  take_chain<T, MREP, NREP>(tot, acc);
   wait_vmcnt<0>();                         // only padding DMAs (to the dummy zone) can still be in flight
   if constexpr (WK > 1) {                  // the two K halves meet: group 1 hands its partial sums to group 0 through LDS
     constexpr int EP = BN * 4 + 16;
@@ -2459,11 +2507,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 static std::atomic<int> g_c64_mode{1}, g_halo16_mode{1}, g_nn128_mode{1}, g_nt128_mode{1};
 static std::atomic<int> g_cpl_split{0};      // "cpl_split": K slices of ipoke_conv3x3_coupling where they fit (0: the rule of coupling_splits)
 
+// an ELU launch that stores fp32: the sweeps of the c64 / halo16 / halo kernels take ELU through fast_act (exp(x) - 1, the bf16-store
+// form); such a launch goes to the implicit GEMM, whose general sweep uses expm1f for fp32 stores
+static bool elu_f32_store(const NtParams& p) { return p.c_f32 && p.act == IPOKE_ACT_ELU; }
+
 static bool c64_applicable(const NtParams& p) {
   // mode 1 (default): at >= 512 patches (two per CU)
   const int mode = g_c64_mode.load(std::memory_order_relaxed);
   const GeomDev& g = p.g;
-  if (!mode) return false;
+  if (!mode || elu_f32_store(p)) return false;
   // window offsets a - ph (forward) / ph - a (data gradient) must lie within the one-pixel halo
   const int kh = g.kw > 0 ? g.khw / g.kw : 0;
   const int lo_y = g.transposed ? g.ph - (kh - 1) : -g.ph, hi_y = g.transposed ? g.ph : kh - 1 - g.ph;
@@ -2495,7 +2547,7 @@ static bool halo16_applicable(const NtParams& p) {
   // the four-tap sub-pixel phase of a stride-2 ConvTranspose2d (2 x 2 window, no padding, scattered output rows)
   const bool phase4 = g.taps == 4 && g.khw == 4 && g.kw == 2 && g.ph == 0 && g.pw == 0 && !g.transposed && g.Di == 1 && g.Do == 1 && g.pd == 0 &&
                       g.sd == 1 && p.c_scatter && !p.dact;
-  if (!mode || p.a_f32) return false;
+  if (!mode || p.a_f32 || elu_f32_store(p)) return false;
   if (!phase4 && (p.c_scatter || !(g.taps == 9 || g.taps == 27) || g.khw != 9 || g.kw != 3)) return false;
   const bool flat = phase4 || (g.taps == 9 && g.Di == 1 && g.Do == 1 && g.pd == 0 && g.sd == 1);
   const bool deep = !phase4 && g.taps == 27 && g.pd == 1 && (p.a_sd & 7) == 0 && (g.sd == 1 ? g.Di == g.Do : (!g.transposed && g.sd == 2));
@@ -2531,7 +2583,7 @@ static bool halo_applicable(const NtParams& p) {
   const GeomDev& g = p.g;
   const bool flat = g.taps == 9 && g.Di == 1 && g.Do == 1 && g.pd == 0;
   const bool deep = g.taps == 27 && g.Di == g.Do && g.pd == 1 && (p.a_sd & 7) == 0;
-  if (!(flat || deep) || p.c_scatter || kLdsHalo > device_max_lds()) return false;
+  if (!(flat || deep) || p.c_scatter || elu_f32_store(p) || kLdsHalo > device_max_lds()) return false;
   if (deep) {     // measured against the 27-tap implicit GEMM (B = 20): 64 channels 16x64x64: 670 vs 997 us, 12x32x32: 126 vs 185 us; but 128
                   // channels 8x32x32: 271 vs 230, 256 channels 4x16x16: 141 vs 101, 512 channels: 255 vs 177 -> 64 input channels only
     if (p.Kc > 64) return false;

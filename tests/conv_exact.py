@@ -646,3 +646,379 @@ def wgrad_desc(NB, dhw, k, p, Kc, Nout, dtype, lda=None, ldy=None, y_coff=0, spl
     d.splitm = splitm
     d.split_stride = split_stride
     return d
+
+
+# ====================================================================== the real-valued family
+# The integer family above cannot see arithmetic: operands of at most 7 significant bits, power-of-two row scales, activations at
+# integers and saved outputs whose derivative is a power of two make every product, sum and scale exact whatever the kernel rounds on
+# the way.  The cases below put real values through the same descriptors (same buffers, sentinels and reference functions):
+#
+# * operands: A = randn (rounded to bf16 for bf16 launches; full-mantissa fp32 with a_f32 -- the value computed with is then its RNE
+#   bf16, A_eff -- and in every f32 launch), W = randn * 1.5 / sqrt(taps * Kc_real) in the launch dtype (zero in the padding channels,
+#   beyond live_c and in zero_taps), bias = randn, row scales uniform in [0.3, 3] and never a power of two, old values under
+#   c_accumulate 8 * randn, saved outputs over the activation's own range in the storage dtype (both signs and both zeros for ReLU /
+#   leaky ReLU), dY = 0.1 * randn in the launch dtype.
+# * reference: float64 throughout.  S is the sum of the magnitudes of an output's terms: |s| sum |x||w| + |b| + |c_old| forward,
+#   sum_m |dY||A| + |dW_old| for the weight gradient.  The error of a contraction is counted in ulp32(S) and bounded by
+#   real_bound(key) = max(4 x yardstick, 4); the yardstick is the worst error of the fp32 restatement ``block_restatement`` (exact dot
+#   products over one matrix-core step of the reduction, rounded to fp32 and added in order in fp32) of the case's own reduction on
+#   the case's own descriptor and operand rules, measured by test_conv_real_cpu.py (every row where the CPU can afford it, evenly
+#   spaced rows otherwise) and recorded per case in REAL_YARDSTICK -- never from a kernel's output.
+# * behind the contraction: every activation has slope <= 1, so the pre-activation allowance carries over; the activation's own error
+#   is real_bound("act_*") fp32 ulps of its value (yardstick: torch's fp32 expm1 / tanh / sigmoid on the CPU); the derivative mask
+#   multiplies the allowance by |act'(saved)| and adds real_bound("dact") ulps of |act| * (magnitude of the terms of act'); a bf16 store
+#   adds one bf16 ulp of the expected value.  The bf16-store ELU of a bf16 launch is by contract exp(x) - 1: its allowance is absolute,
+#   four times the worst error of fl32(exp32(x)) - 1 on the CPU over the case's own arguments.  Every element is compared.
+REAL_YARDSTICK = {
+    # worst error of the block restatement of each case's own reduction on its own operands, in ulp32(S), rounded up to a tenth
+    # (test_conv_real_cpu.py: measure_conv_case / measure_wgrad_case; a few thousand to 10^6 outputs per case, and the tail is long: the
+    # root-mean-square is 0.1).  Forward cases of tests/test_conv_real_gpu.py and, as cpu_*, of test_conv_real_cpu.py:
+    "fwd": {
+        "s8_k256_n32_b5": 0.6, "s8_k512_n60_b3": 0.7, "s8_k2048_n64_b7": 0.8, "s8_transposed_k512_n64_b5": 0.6,
+        "s8_splitk_slabs_k1024_n48_b20": 0.7, "s8_splitk_acc_dgrad_k512_n32_b20": 0.7, "s8_outside_k192": 0.6,
+        "s8_outside_n72": 0.7, "k64_k8_n256_b3": 1.2, "k64_k32_n2048_b3": 0.9, "k64_k40_n256_b20": 1.1, "k64_k32_n2048_b20": 1.0,
+        "k64_outside_b40_n2048": 1.1, "k64_outside_n248": 0.8, "k8_cin3_n16_m65536": 1.5, "k8_cin8_n48_m65536": 1.4,
+        "k8_cin8_n64_m65536_transposed": 1.4, "k8_cin3_n64_transposed": 1.5, "k8_outside_m49152": 1.4, "k8_outside_bias": 1.4,
+        "k8_outside_n72": 1.5, "c64_k64_n64_default_rule": 0.8, "c64_outside_k128_9tap": 0.8, "c64_k64_n40_relu_bias": 0.8,
+        "c64_transposed_k64_n32": 0.7, "c64_phase00_1tap": 1.0, "c64_phase01_2tap": 0.8, "c64_phase10_2tap": 0.9,
+        "c64_phase11_4tap": 1.0, "c64_phase11_4tap_k128_n56": 0.5, "c64_outside_n72": 0.8, "c64_outside_h24": 0.9,
+        "halo16_k128_n96": 0.7, "halo16_k128_n128_elu": 0.7, "halo16_k256_n200": 0.8, "halo16_3d_k64_n96": 0.9,
+        "halo16_3d_depth_stride2_k64_n128": 0.7, "halo16_phase11_4tap": 0.7, "halo16_phase01_padded_2x2_16": 0.6,
+        "halo16_phase10_padded_2x2_16": 0.6, "halo16_phase01_padded_2x2_32": 0.8, "halo16_outside_h24": 1.0,
+        "halo16_outside_k96": 0.9, "halo_k64_128x128_n3_f32out_tanh": 0.6, "halo_k64_n64_elu_channel_range": 0.8,
+        "halo_k512_16x16_n256": 0.8, "halo_3d_k64_n64": 0.8, "halo_outside_w24": 0.8, "halo_outside_m1024": 0.7,
+        "igemm_1x1_k128_n192": 0.7, "igemm_stem_3x7x7_a_f32": 1.0, "igemm_stem_3x7x7_f32": 1.3, "igemm_patchgan_4x4_s2_lrelu": 1.1,
+        "igemm_strided_dgrad_dact_elu": 0.8, "igemm_row_scale_bias": 1.0, "igemm_channel_range_k40": 0.7, "igemm_f32_3x3_acc": 0.9,
+        "igemm_f32_3x3_bias_elu": 0.9, "igemm_f32_dtype_out_transposed": 0.9, "igemm_f32_8x8_k512_n64": 0.8,
+        "igemm_3d_scatter_with_depth": 0.7, "upconv8_phase00_1tap": 0.8, "upconv8_phase01_padded_2x2": 0.9,
+        "upconv8_phase10_padded_2x2": 0.7, "upconv8_phase11_4tap": 0.7, "igemm_dgrad_dact_tanh": 0.7,
+        "igemm_dgrad_dact_sigmoid": 0.8, "igemm_dgrad_dact_relu": 0.7, "igemm_dgrad_dact_lrelu": 0.7,
+        "igemm_sigmoid_bf16_store": 0.6, "igemm_sigmoid_f32_store": 0.8, "igemm_tanh_bf16_store": 0.7, "igemm_tanh_f32_store": 0.7,
+        "igemm_elu_bf16_compute_f32_store": 0.9, "halo_outside_elu_f32_store": 0.5, "halo16_outside_elu_f32_store": 1.0,
+        "c64_outside_elu_f32_store": 0.8, "halo_small_elu_f32_store": 0.6, "s8_splitk_acc_atomic_k512_n32_b20": 0.5,
+        "small_elu_fast_path_bf16_store": 0.8, "small_elu_general_f32_store": 0.6, "small_elu_f32_launch": 1.0, "cpu_f32_k576": 0.6,
+        "cpu_f32_elu_k324": 0.7, "cpu_bf16_elu_bf16_store": 0.4, "cpu_bf16_tanh_f32_store": 0.4,
+        "cpu_bf16_sigmoid_channel_range": 0.4, "cpu_bf16_row_scale_f32_store": 0.5, "cpu_bf16_a_f32_stem": 0.4, "cpu_f32_acc": 0.3,
+        "cpu_bf16_slabs": 0.6, "cpu_bf16_dgrad_dact_tanh": 0.5, "cpu_bf16_dgrad_dact_lrelu": 0.5, "cpu_small_elu_bf16_store": 0.4,
+        "cpu_small_elu_f32_store": 0.4, "cpu_small_elu_f32_launch": 0.5,
+    },
+    # weight gradients (blocks of 32 output rows)
+    "wgrad": {
+        "wgrad_halo_k64_n128_64x64": 0.6, "wgrad_halo_slabs_k128_n64_32x32": 0.7, "wgrad_halo_3d_k64_n64": 0.7,
+        "wgrad_halo_outside_m4096": 0.6, "wgrad_tn_1x1_k128_n256": 0.5, "wgrad_tn_3x3_k48_n40_ragged": 0.6,
+        "wgrad_tn_3x3_k24_n32_4x8_map": 0.7, "wgrad_tn_f32_3x3_k36_n20": 0.7, "wgrad_tn_f32_1x1_split_atomic": 0.5,
+        "wgrad_stem_3x7x7_a_f32_kc_store": 0.5, "wgrad_tn_3x3_k48_n40_accumulate": 0.6, "batched_b20_k512_n64_3x3": 0.6,
+        "batched_b7_k320_n136_3x3": 0.7, "batched_b3_k64_n48_3x3": 0.6, "batched_b20_k512_n48_1x1": 0.4,
+        "batched_b5_k256_n256_1x1": 0.5, "cpu_f32": 0.5, "cpu_acc": 0.6, "cpu_slabs": 0.5,
+    },
+    # torch's fp32 activation on the CPU against float64, in fp32 ulps of the value; the derivative from the saved output
+    # (measured 0.52, 0.57, 1.94, 0, 0.6 and 0.5)
+    "act_elu": 0.6, "act_tanh": 0.6, "act_sigmoid": 2.0, "act_relu": 0.5, "act_lrelu": 0.7, "dact": 0.5,
+}
+ACT_KEY = {_lib.ACT_ELU: "act_elu", _lib.ACT_TANH: "act_tanh", _lib.ACT_SIGMOID: "act_sigmoid", _lib.ACT_RELU: "act_relu",
+           _lib.ACT_LRELU02: "act_lrelu"}
+
+
+def dtype_name(dtype):
+    return "bf16" if dtype == _lib.BF16 else "f32"
+
+
+def real_bound(key):
+    """key: ("fwd" | "wgrad", case name) or the name of an activation entry"""
+    y = REAL_YARDSTICK[key[0]][key[1]] if isinstance(key, tuple) else REAL_YARDSTICK[key]
+    return max(4.0 * y, 4.0)
+
+
+def ulp32(v):
+    """fp32 unit in the last place of |v| (float64 tensor); the subnormal spacing below 2^-126"""
+    a = v.abs().clamp(min=2.0 ** -126)
+    return torch.pow(2.0, torch.floor(torch.log2(a)) - 23)
+
+
+def block_restatement(x64, w64, block):
+    """[R, K] x [K, N] float64 operands: dot products over `block` consecutive elements of K taken exactly and rounded to fp32, the
+    blocks added in order in fp32 (one matrix-core step at a time).  Returns float32 [R, N]."""
+    R, K = x64.shape
+    acc = torch.zeros(R, w64.shape[1], dtype=torch.float32, device=x64.device)
+    for k0 in range(0, K, block):
+        acc = acc + (x64[:, k0:k0 + block] @ w64[k0:k0 + block]).to(torch.float32)
+    return acc
+
+
+def k_block(dtype):
+    """elements of K per matrix-core step: 32 bf16 (v_mfma_f32_16x16x32_bf16) or 16 f32 (four v_mfma_f32_16x16x4_f32)"""
+    return 32 if dtype == _lib.BF16 else 16
+
+
+def not_representable(x, bits):
+    """fraction of the non-zero values of x (fp32 / float64 values) whose significand needs more than `bits` bits"""
+    v = x.to(torch.float64).reshape(-1)
+    v = v[v != 0]
+    if v.numel() == 0:
+        return 0.0
+    q = torch.pow(2.0, torch.floor(torch.log2(v.abs())) - (bits - 1))
+    return float((torch.remainder(v, q) != 0).to(torch.float64).mean())
+
+
+def real_operand(shape, dtype, gen, scale=1.0):
+    """scale * randn in the launch dtype, as float64"""
+    v = torch.randn(shape, generator=gen, device=gen.device, dtype=torch.float32) * scale
+    return v.to(tdtype(dtype)).to(torch.float64)
+
+
+def act_grad_mag64(act, y):
+    """sum of the magnitudes of the terms of act'(y) as the kernel evaluates it from the saved output"""
+    if act == _lib.ACT_ELU:
+        return torch.where(y > 0, torch.ones_like(y), y.abs() + 1)
+    if act == _lib.ACT_TANH:
+        return 1 + y * y
+    if act == _lib.ACT_SIGMOID:
+        return y.abs() * (1 + y.abs())
+    return act_grad_from_out64(act, y).abs()
+
+
+def saved_outputs(act, shape, t, gen):
+    """saved activation outputs over the activation's own range, in the storage dtype"""
+    dev = gen.device
+    u = torch.rand(shape, generator=gen, device=dev, dtype=torch.float32)
+    if act == _lib.ACT_ELU:
+        v = 4 * u - 1
+    elif act == _lib.ACT_TANH:
+        v = 2 * u - 1
+    elif act == _lib.ACT_SIGMOID:
+        v = u
+    else:
+        v = torch.randn(shape, generator=gen, device=dev, dtype=torch.float32)
+        z = torch.rand(shape, generator=gen, device=dev)
+        v = torch.where(z < 0.1, torch.zeros_like(v), v)
+        v = torch.where(z < 0.05, -torch.zeros_like(v), v)
+    return v.to(t)
+
+
+class RealConvCase(ConvCase):
+    """ConvCase with real-valued operands written over the integer ones (same buffers, same pointers, same sentinels), a float64
+    expectation with a per-element allowance, and run_twice() for the bit-reproducibility of the launches that take no atomics."""
+
+    def __init__(self, d, dtype, device, key, seed=0, acc_scratch=None, live_c=None, zero_taps=(), w_exp=0, **kw):
+        """key: the case's name in REAL_YARDSTICK["fwd"]"""
+        super().__init__(d, dtype, device, seed=seed, acc_scratch=acc_scratch, live_c=live_c, zero_taps=zero_taps, **kw)
+        d = self.d
+        gen = torch.Generator(device=device).manual_seed(seed + 7919)
+        T = taps_of(d)
+        # ---- A
+        idx = (pixel_offsets(d).to(device).unsqueeze(1) + torch.arange(d.Kc_real, device=device) * d.a_sc).reshape(-1)
+        full = bool(d.a_f32) or dtype == _lib.F32
+        vals = torch.randn(idx.numel(), generator=gen, device=device, dtype=torch.float32)
+        if not full:
+            vals = vals.to(torch.bfloat16).to(torch.float32)
+        if live_c is not None:
+            vals = vals.view(-1, d.Kc_real).clone()
+            vals[:, live_c:] = 0
+            vals = vals.reshape(-1)
+        self.A[idx] = vals.to(self.A.dtype)
+        self.A_eff = (self.A.to(torch.bfloat16) if (d.a_f32 and dtype == _lib.BF16) else self.A).to(torch.float64)
+        # ---- W: real values where the structure (padding channels, live_c, zero_taps) allows a weight
+        wscale = 1.5 / (T * d.Kc_real) ** 0.5 * 2.0 ** w_exp
+        live = d.Kc_real if live_c is None else live_c
+        if d.w_kmajor:
+            Wv = torch.zeros(T, d.Kc, d.ldw, dtype=torch.float64, device=device)
+            Wv[:, :live, : d.Nout] = real_operand((T, live, d.Nout), dtype, gen, wscale)
+            for t in zero_taps:
+                Wv[t] = 0
+        else:
+            Wv = torch.zeros(d.Nout, d.ldw, dtype=torch.float64, device=device)
+            w3 = torch.zeros(d.Nout, T, d.Kc, dtype=torch.float64, device=device)
+            w3[:, :, :live] = real_operand((d.Nout, T, live), dtype, gen, wscale)
+            for t in zero_taps:
+                w3[:, t] = 0
+            Wv[:, : T * d.Kc] = w3.reshape(d.Nout, T * d.Kc)
+        self.W.copy_(Wv.reshape(-1).to(self.W.dtype))
+        # ---- epilogue operands
+        if self.bias is not None:
+            self.bias.copy_(torch.randn(d.Nout, generator=gen, device=device, dtype=torch.float32))
+        if self.row_scale is not None:
+            rs = max(1, d.rs_stride)
+            n = self.row_scale[::rs].numel()
+            s = 0.3 + 2.7 * torch.rand(n, generator=gen, device=device, dtype=torch.float32)
+            assert not bool((torch.frexp(s)[0] == 0.5).any()), "a row scale is a power of two"
+            self.row_scale[::rs] = s
+        if self.dact is not None:
+            self.dact.copy_(saved_outputs(d.dact_act, tuple(self.dact.shape), self.dact.dtype, gen))
+        if d.c_accumulate:
+            self.C0[: self.c_rows] = (8 * torch.randn(self.c_rows, d.ldc, generator=gen, device=device, dtype=torch.float32)).to(self.c_t)
+        self.C.copy_(self.C0)
+        self.fwd_key = ("fwd", key)
+        self.atomic = self.splitk > 1 and bool(d.c_accumulate) and acc_scratch is None
+
+    def _check_bound(self, ktot):          # (the integer operands the base class drew are replaced: nothing to hold exact)
+        self.max_abs_sum = None
+
+    def elu_fast(self):
+        """the bf16-store ELU of a bf16 launch: exp(x) - 1 by contract"""
+        return self.dtype == _lib.BF16 and self.d.act == _lib.ACT_ELU and not self.d.c_f32
+
+    def expected_real(self):
+        """(E, tol, written): float64 expectation of the whole C buffer, the allowance of every element and the mask of the elements a
+        launch writes (everything else must keep its bits).  Split-K slabs: E / tol hold the slab sum in rows [0, M)."""
+        d = self.d
+        dev = self.device
+        M = rows_of(d)
+        y = conv_sums(d, self.A_eff, self.W)
+        S = conv_sums(d, self.A_eff, self.W, absolute=True)
+        B = real_bound(self.fwd_key)
+        E = self.C0.to(torch.float64)
+        tol = torch.zeros_like(E)
+        written = torch.zeros(E.shape, dtype=torch.bool, device=dev)
+        if self.splitk > 1 and not d.c_accumulate:
+            self.slab = True
+            E[:M, : d.Nout] = y
+            tol[:M, : d.Nout] = B * ulp32(S)
+            return E, tol, written
+        self.slab = False
+        v = y
+        if self.row_scale is not None:
+            s = self._scale_per_row(M).view(-1, 1)
+            v, S = v * s, S * s.abs()
+        if self.bias is not None:
+            b = self.bias.to(torch.float64)
+            v, S = v + b, S + b.abs()
+        rows = out_row_index(d, torch.arange(M, device=dev))
+        cols = d.c_coff + torch.arange(d.Nout, device=dev) * max(1, d.c_cstride)
+        old = None
+        if d.c_accumulate:
+            old = E[rows][:, cols]
+            S = S + old.abs()
+        t = B * ulp32(S)
+        self.pre = v
+        if d.act != _lib.ACT_NONE:
+            a = act64(d.act, v)
+            if self.elu_fast():
+                neg = v[v <= 0].cpu()
+                x32 = neg.to(torch.float32)
+                worst = float(((torch.exp(x32) - 1).to(torch.float64) - torch.expm1(x32.to(torch.float64))).abs().max()) if neg.numel() else 0.0
+                self.elu_allowance = 4 * worst
+                t = t + torch.where(v <= 0, torch.full_like(v, self.elu_allowance), torch.zeros_like(v))
+            else:
+                t = t + real_bound(ACT_KEY[d.act]) * ulp32(a)
+            v = a
+        if self.dact is not None:
+            saved = self.dact.to(torch.float64)[:M, : d.Nout]
+            g = act_grad_from_out64(d.dact_act, saved)
+            t = t * g.abs() + real_bound("dact") * ulp32(v.abs() * act_grad_mag64(d.dact_act, saved))
+            v = v * g
+        if old is not None:
+            v = old + v
+        if self.c_t == torch.bfloat16:
+            t = t + ulp(v, torch.bfloat16)
+        E[rows.view(-1, 1), cols.view(1, -1)] = v
+        tol[rows.view(-1, 1), cols.view(1, -1)] = t
+        written[rows.view(-1, 1), cols.view(1, -1)] = True
+        if not d.c_f32 and self.splitk == 1:
+            n_pad = min(round_up(d.Nout, e16(self.dtype)), d.ldc - d.c_coff)
+            if n_pad > d.Nout:
+                pc = (d.c_coff + torch.arange(d.Nout, n_pad, device=dev)).view(1, -1)
+                E[rows.view(-1, 1), pc] = 0.0
+                written[rows.view(-1, 1), pc] = True
+        return E, tol, written
+
+    def compare(self, what="", got=None):
+        """got (default: the case's C) against the expectation; returns the worst error in units of the allowance / bound (the worst
+        contraction error in ulp32(S) for slabs and launches with no activation), raises naming the first element that misses"""
+        E, tol, written = self.expected_real()
+        got = self.C if got is None else got
+        d = self.d
+        g = got.to(torch.float64)
+        if self.slab:
+            M = rows_of(d)
+            sl = g[: self.splitk * M].view(self.splitk, M, d.ldc)
+            assert bool((g[self.splitk * M:] == SENT).all()), f"{what}: write past the last split-K slab"
+            G = E.clone()
+            G[:M, : d.Nout] = sl[:, :, : d.Nout].sum(0)
+            g = G
+            written[:M, : d.Nout] = True
+        keep = (g == self.C0.to(torch.float64)) | written
+        if not bool(keep.all()):
+            flat = int(torch.nonzero(~keep.reshape(-1))[0])
+            row, col = divmod(flat, g.shape[1])
+            raise AssertionError(f"{what}: store outside the written region at {describe_position(d, row, col)}: {float(g[row, col])}")
+        err = (g - E).abs()
+        bad = written & (~(err <= tol))
+        rel = torch.where(written & (tol > 0), err / tol.clamp(min=2.0 ** -1000), torch.zeros_like(err))
+        self.worst = float(rel.max()) if rel.numel() else 0.0
+        if bool(bad.any()):
+            flat = int(torch.nonzero(bad.reshape(-1))[0])
+            row, col = divmod(flat, g.shape[1])
+            raise AssertionError(f"{what}: {int(bad.sum())} elements beyond their allowance (worst {self.worst:.2f} x the allowance); first at "
+                                 f"{describe_position(d, row, col)}: got {float(g[row, col])!r}, expected {float(E[row, col])!r}, "
+                                 f"allowance {float(tol[row, col]):.3e}")
+        return self.worst
+
+    def run_twice(self):
+        """two launches on fresh copies of the output; returns (kernel, bit-identical?)"""
+        k = self.run()
+        first = self.C.clone()
+        self.C.copy_(self.C0)
+        self.run()
+        same = torch.equal(first.view(torch.uint8), self.C.view(torch.uint8))
+        return k, same
+
+
+class RealWgradCase(WgradCase):
+    """WgradCase with real operands: A = randn, dY = 0.1 * randn in the launch dtype (fp32 A with a_f32: the value used is its RNE bf16
+    in a bf16 launch), real old values under `accumulate`; slabs summed in float64 and compared in ulp32 of sum_m |dY||A| + |dW_old|."""
+
+    def __init__(self, d, dtype, device, key, seed=0):
+        """key: the case's name in REAL_YARDSTICK["wgrad"]"""
+        super().__init__(d, dtype, device, seed=seed)
+        d = self.d
+        gen = torch.Generator(device=device).manual_seed(seed + 7919)
+        idx = (pixel_offsets(d).to(device).unsqueeze(1) + torch.arange(d.Kc_real, device=device) * d.a_sc).reshape(-1)
+        vals = torch.randn(idx.numel(), generator=gen, device=device, dtype=torch.float32)
+        self.A[idx] = vals.to(self.A.dtype)
+        self.A_eff = (self.A.to(torch.bfloat16) if (d.a_f32 and dtype == _lib.BF16) else self.A).to(torch.float64)
+        M = rows_of(d)
+        self.dY[:M, d.y_coff:d.y_coff + d.Nout] = (0.1 * torch.randn(M, d.Nout, generator=gen, device=device, dtype=torch.float32)).to(self.dY.dtype)
+        if d.accumulate:
+            pos = self._positions(0).to(device)
+            self.W0[pos] = torch.randn(pos.numel(), generator=gen, device=device, dtype=torch.float32)
+        self.dW.copy_(self.W0)
+        self.key = ("wgrad", key)
+        self.atomic = d.splitm > 1 and d.split_stride == 0
+
+    def compare(self, what="", got=None):
+        """returns the worst error in ulp32(S); raises naming the first element beyond real_bound(key)"""
+        d = self.d
+        dev = self.device
+        ref = wgrad_sums(d, self.A_eff, self.dY)[:, :, : self.kst]
+        S = wgrad_sums(d, self.A_eff.abs(), self.dY.abs())[:, :, : self.kst]
+        g = (self.dW if got is None else got).to(torch.float64)
+        W0 = self.W0.to(torch.float64)
+        written = torch.zeros(g.shape, dtype=torch.bool, device=dev)
+        for z in range(self.nsplit):
+            written[self._positions(z).to(dev)] = True
+        assert bool((g[~written] == W0[~written]).all()), f"{what}: weight-gradient store outside its (n, c, tap) positions"
+        pos = self._positions(0).to(dev)
+        s = sum(g[self._positions(z).to(dev)] for z in range(self.nsplit))
+        exp = ref.permute(0, 2, 1).reshape(-1)
+        S = S.permute(0, 2, 1).reshape(-1)
+        if d.accumulate:
+            exp = exp + W0[pos]
+            S = S + W0[pos].abs()
+        e = (s - exp).abs() / ulp32(S)
+        B = real_bound(self.key)
+        self.worst = float(e.max())
+        bad = ~(e <= B)
+        if bool(bad.any()):
+            i = int(torch.nonzero(bad)[0])
+            nn_, rem = divmod(i, self.kst * taps_of(d))
+            c, t = divmod(rem, taps_of(d))
+            raise AssertionError(f"{what}: {int(bad.sum())} weight-gradient elements beyond {B} ulp32(S) (worst {self.worst:.2f}); first at "
+                                 f"(n={nn_}, c={c}, tap={t}): got {float(s[i])!r}, expected {float(exp[i])!r}")
+        return self.worst
+
+    def run_twice(self):
+        k = self.run()
+        first = self.dW.clone()
+        self.dW.copy_(self.W0)
+        self.run()
+        return k, torch.equal(first.view(torch.uint8), self.dW.view(torch.uint8))

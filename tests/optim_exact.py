@@ -286,6 +286,102 @@ def wn_bwd_ref(v, g, dw, inv):
     return dot * inv, a[:, None] * dw - b[:, None] * v
 
 
+# ------------------------------------------------------------------ weight norm on real rows
+# The exact rows above have a power-of-two norm and at most 2304 elements.  The real family: rows of 0.05 * randn with real gains and
+# real dW, the present lengths plus 4608 and 18432 (2048 channels x 9 taps, the flow's longest row) at all four alignments; in every
+# job one row with a norm near 1e-3, one near 1e3 and one nearly radial gradient dW = 3 v + 1e-3 * randn, where a dW - bcoef v cancels.
+# References: wn_scale_ref / wn_bwd_ref in float64, the backward teacher-forced on the fp32 inv_norm it is handed.  Units: the fp32
+# ulp of the result for scale and inv_norm (a sum of squares does not cancel); for dg the ulp of inv sum |dw||v|, for dv[k] the ulp of
+# |g| inv |dw_k| + |g| inv^3 sum |dw||v| |v_k|.  Bound: max(4 x WN_YARDSTICK, 4); the yardstick is the worst error of the fp32
+# restatement below, which follows the kernel's per-lane strides, over the GPU test's own operands (test_optim_exact_cpu.py).
+WN_REAL_K = [1, 3, 6, 64, 160, 764, 768, 772, 1728, 2304, 4608, 18432]
+WN_YARDSTICK = {"scale": 1.5, "inv_norm": 1.8, "dg": 2.4, "dv": 3.3}       # measured 1.48, 1.73, 2.37 and 3.24
+
+
+def wn_bound(key):
+    return max(4.0 * WN_YARDSTICK[key], 4.0)
+
+
+def wn_real_case(seed):
+    """48 jobs (every K of WN_REAL_K at v_off = 0, 1, 2, 3 mod 4), 5..8 rows each, laid out as the exact case is: gains and directions
+    apart in the flat buffer with sentinel gaps, per-job output rows apart by two sentinel rows.  Returns (jobs, total_rows, nout,
+    params, grads, vals) with vals = [(g, v, dW)] in float32."""
+    gen = torch.Generator().manual_seed(seed)
+    specs, vals, off, out = [], [], 16, 0
+    for i, (K, mod) in enumerate((K, mod) for K in WN_REAL_K for mod in range(4)):
+        rows = 5 + i % 4
+        g_off = off
+        v_off = g_off + rows + 3
+        v_off += (mod - v_off) % 4
+        specs.append((v_off, g_off, out, rows, K))
+        v = 0.05 * torch.randn(rows, K, generator=gen)
+        nrm = v.norm(dim=1, keepdim=True).clamp(min=1e-6)
+        v[0] = v[0] / nrm[0] * 1.1e-3
+        v[1] = v[1] / nrm[1] * 0.9e3
+        dw = torch.randn(rows, K, generator=gen)
+        dw[2] = 3 * v[2] + 1e-3 * torch.randn(K, generator=gen)
+        vals.append((torch.randn(rows, generator=gen), v, dw))
+        off = v_off + rows * K + 5
+        out += rows + 2
+    jobs, total_rows = wn_table(specs)
+    n = off + 16
+    params = torch.full((n,), SENT)
+    grads = torch.full((n,), SENT)
+    for j, (g, v, dw) in zip(jobs, vals):
+        params[j.g_off:j.g_off + j.rows] = g
+        params[j.v_off:j.v_off + j.rows * j.K] = v.reshape(-1)
+        grads[j.v_off:j.v_off + j.rows * j.K] = dw.reshape(-1)
+    return jobs, total_rows, out + 8, params, grads, vals
+
+
+def wn_bwd_mags(v, g, dw, inv):
+    """(unit of dg, unit of dv): the sums of the magnitudes of the terms each is made of (float64)"""
+    v, g, dw, inv = v.to(F64), g.to(F64), dw.to(F64), inv.to(F64)
+    sabs = (v * dw).abs().sum(1)
+    return inv * sabs, (g.abs() * inv)[:, None] * dw.abs() + (g.abs() * inv ** 3 * sabs)[:, None] * v.abs()
+
+
+def _lane_sum32(prod, vec):
+    """fp32 sum of the products [rows, K] the way a wave takes it: lane l owns the elements (vec: the 4-groups) l, l + 64, ... and adds
+    them in order; the 64 partial sums then meet in a butterfly"""
+    rows, K = prod.shape
+    w = 4 if vec else 1
+    n = -(-K // (64 * w))
+    p = torch.zeros(rows, n * 64 * w, dtype=torch.float32)
+    p[:, :K] = prod
+    p = p.view(rows, n, 64, w).permute(0, 2, 1, 3).reshape(rows, 64, n * w)
+    s = torch.zeros(rows, 64, dtype=torch.float32)
+    for i in range(n * w):
+        s = s + p[:, :, i]
+    while s.shape[1] > 1:
+        h = s.shape[1] // 2
+        s = s[:, :h] + s[:, h:]
+    return s[:, 0]
+
+
+def wn_scale_restate(v, g, v_off):
+    """fp32 restatement of wn_scale_kernel on float32 operands: (scale, inv_norm)"""
+    vec = v.shape[1] % 4 == 0 and v_off % 4 == 0
+    nrm = torch.sqrt(_lane_sum32(v * v, vec))
+    return g / nrm, 1.0 / nrm
+
+
+def wn_bwd_restate(v, g, dw, inv32, v_off):
+    """fp32 restatement of wn_bwd_kernel on float32 operands and the fp32 inv_norm it is handed: (dg, dv)"""
+    vec = v.shape[1] % 4 == 0 and v_off % 4 == 0
+    dot = _lane_sum32(dw * v, vec)
+    a, b = g * inv32, g * dot * inv32 * inv32 * inv32
+    return dot * inv32, a[:, None] * dw - b[:, None] * v
+
+
+def units(got, ref64, mag64):
+    """worst |got - ref| in fp32 ulps of mag (float64 tensors; 0 for empty input)"""
+    if ref64.numel() == 0:
+        return 0.0
+    u = torch.pow(2.0, torch.floor(torch.log2(mag64.abs().clamp(min=2.0 ** -126))) - 23)
+    return float(((got.to(F64) - ref64).abs() / u).max())
+
+
 def assert_exactly_representable(x, what):
     """every float64 value of x is a float32 value (the operand classes promise exact results; a failure here is a generator bug)"""
     bad = rn(x) != x

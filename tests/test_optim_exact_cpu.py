@@ -387,3 +387,71 @@ def test_comparator_rejects_wn_bwd_without_its_projection():
     no_proj = (g.double() * inv)[:, None] * dw.double()
     with pytest.raises(AssertionError):
         X.assert_same(no_proj.float(), dv, "dv without the projection term")
+
+
+# ------------------------------------------------------------------ weight norm on real rows
+def test_weight_norm_references_match_float64_autograd():
+    """wn_scale_ref / wn_bwd_ref against float64 autograd through torch._weight_norm (w = g v / ||v|| per output row)"""
+    gen = torch.Generator().manual_seed(11)
+    for K in (1, 3, 160, 4608):
+        v = (0.05 * torch.randn(6, K, generator=gen)).to(F64).requires_grad_()
+        g = torch.randn(6, 1, generator=gen).to(F64).requires_grad_()
+        dw = torch.randn(6, K, generator=gen).to(F64)
+        w = torch._weight_norm(v, g, 0)
+        w.backward(dw)
+        sc, inv = X.wn_scale_ref(v.detach(), g.detach()[:, 0])
+        assert torch.allclose(w.detach(), sc[:, None] * v.detach(), rtol=1e-13, atol=0)
+        dg, dv = X.wn_bwd_ref(v.detach(), g.detach()[:, 0], dw, inv)
+        sabs = (v.detach() * dw).abs().sum(1)
+        assert bool(((dg - g.grad[:, 0]).abs() <= 1e-13 * inv * sabs).all()), K
+        mag = X.wn_bwd_mags(v.detach(), g.detach()[:, 0], dw, inv)[1]
+        assert bool(((dv - v.grad).abs() <= 1e-13 * mag).all()), K
+
+
+def test_weight_norm_real_case_operands_and_yardsticks():
+    """the operands of the GPU tests (seeds 410 / 510) hold what they promise, and the fp32 restatement that follows the kernel's
+    per-lane strides stays within the recorded yardsticks, in the units the GPU tests use"""
+    worst = dict(scale=0.0, inv_norm=0.0, dg=0.0, dv=0.0)
+    for seed in (410, 510):
+        jobs, total_rows, nout, params, grads, vals = X.wn_real_case(seed)
+        assert sorted({j.K for j in jobs}) == sorted(X.WN_REAL_K) and {j.v_off % 4 for j in jobs if j.K == 18432} == {0, 1, 2, 3}
+        for j, (g, v, dw) in zip(jobs, vals):
+            nrm = v.to(F64).norm(dim=1)
+            assert 0.9e-3 < float(nrm[0]) < 1.3e-3 and 0.7e3 < float(nrm[1]) < 1.1e3
+            sc, inv = X.wn_scale_ref(v, g)
+            inv32 = inv.float()
+            dg, dv = X.wn_bwd_ref(v, g, dw, inv32)
+            mdg, mdv = X.wn_bwd_mags(v, g, dw, inv32)
+            if j.K >= 64:
+                # the radial row cancels: the result is far below its terms
+                assert float(dv[2].abs().max()) < 0.05 * float(mdv[2].max())
+                assert 0.5 < float(nrm[3] / (0.05 * j.K ** 0.5)) < 1.5
+            r_sc, r_inv = X.wn_scale_restate(v, g, j.v_off)
+            r_dg, r_dv = X.wn_bwd_restate(v, g, dw, inv32, j.v_off)          # (teacher-forced, as the GPU test is)
+            worst["scale"] = max(worst["scale"], X.units(r_sc, sc, sc))
+            worst["inv_norm"] = max(worst["inv_norm"], X.units(r_inv, inv, inv))
+            worst["dg"] = max(worst["dg"], X.units(r_dg, dg, mdg))
+            worst["dv"] = max(worst["dv"], X.units(r_dv, dv, mdv))
+    print("weight-norm restatement, worst units:", worst)
+    for k, e in worst.items():
+        assert e <= X.WN_YARDSTICK[k], (k, e)
+
+
+def test_weight_norm_real_comparator_has_teeth():
+    """a norm accumulated in bf16-rounded squares, and a dot product that drops its last 4-group, exceed the bounds"""
+    jobs, total_rows, nout, params, grads, vals = X.wn_real_case(410)
+    j, (g, v, dw) = next((j, x) for j, x in zip(jobs, vals) if j.K == 4608 and j.v_off % 4 == 0)
+    sc, inv = X.wn_scale_ref(v, g)
+    bad_inv = 1.0 / torch.sqrt(((v * v).bfloat16().float()).sum(1))
+    assert X.units(bad_inv, inv, inv) > X.wn_bound("inv_norm")
+    inv32 = inv.float()
+    dg, dv = X.wn_bwd_ref(v, g, dw, inv32)
+    mdg, mdv = X.wn_bwd_mags(v, g, dw, inv32)
+    v_short = v.clone()
+    v_short[:, -4:] = 0
+    b_dg, b_dv = X.wn_bwd_restate(v_short, g, dw, inv32, j.v_off)
+    assert X.units(b_dg, dg, mdg) > X.wn_bound("dg")
+    # bcoef with inv^2 instead of inv^3
+    dot = (dw * v).sum(1)
+    wrong = (g * inv32)[:, None] * dw - (g * dot * inv32 * inv32)[:, None] * v
+    assert X.units(wrong, dv, mdv) > X.wn_bound("dv")

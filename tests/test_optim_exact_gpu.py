@@ -259,6 +259,77 @@ def test_wn_bwd(ranged):
     assert torch.equal(pd.cpu(), params)
 
 
+# ---- on real rows (optim_exact.wn_real_case): float64 references, errors in ulps of the terms' magnitudes, bounds from the restatement
+@pytest.mark.parametrize("ranged", [False, True])
+def test_wn_scale_real(ranged):
+    jobs, total_rows, nout, params, _, vals = X.wn_real_case(410)
+    jb, nj, r0, nr = _row_range(jobs, total_rows, ranged)
+    table = X.to_device(jobs, DEV)
+    pd = params.to(DEV)
+    scale, inv = (torch.full((nout,), X.SENT, device=DEV) for _ in range(2))
+    if ranged:
+        _lib.check(lib().ipoke_wn_scale_multi_range(ptr(pd), ptr(scale), ptr(inv), ptr(table), jb, nj, r0, nr, stream()))
+    else:
+        _lib.check(lib().ipoke_wn_scale_multi(ptr(pd), ptr(scale), ptr(inv), ptr(table), len(jobs), total_rows, stream()))
+    torch.cuda.synchronize()
+    scale, inv = scale.cpu(), inv.cpu()
+    untouched = torch.ones(nout, dtype=torch.bool)
+    worst = dict(scale=0.0, inv_norm=0.0)
+    for j, (g, v, _) in zip(jobs, vals):
+        sc_e, inv_e = X.wn_scale_ref(v, g)
+        sel = torch.tensor([r0 <= j.row_start + r < r0 + nr for r in range(j.rows)])
+        idx = j.out_off + torch.nonzero(sel).reshape(-1)
+        untouched[idx] = False
+        worst["scale"] = max(worst["scale"], X.units(scale[idx], sc_e[sel], sc_e[sel]))
+        worst["inv_norm"] = max(worst["inv_norm"], X.units(inv[idx], inv_e[sel], inv_e[sel]))
+    print(f"weight norm scale / inv_norm on real rows: worst {worst} units, bounds {X.wn_bound('scale')} / {X.wn_bound('inv_norm')}")
+    assert worst["scale"] <= X.wn_bound("scale") and worst["inv_norm"] <= X.wn_bound("inv_norm"), worst
+    assert bool((scale[untouched] == X.SENT).all()) and bool((inv[untouched] == X.SENT).all()), "store outside the rows of the range"
+    assert torch.equal(pd.cpu(), params)
+
+
+@pytest.mark.parametrize("ranged", [False, True])
+def test_wn_bwd_real(ranged):
+    """register path (K <= 768, aligned), two-pass path (up to 18432 = 2048 channels x 9 taps) and the scalar path; two runs on fresh
+    copies of the gradient buffer must agree bit for bit (a row always takes the same path)"""
+    jobs, total_rows, nout, params, grads, vals = X.wn_real_case(510)
+    jb, nj, r0, nr = _row_range(jobs, total_rows, ranged)
+    inv_buf = torch.full((nout,), X.SENT)
+    for j, (g, v, dw) in zip(jobs, vals):
+        inv_buf[j.out_off:j.out_off + j.rows] = X.wn_scale_ref(v, g)[1].float()
+    table = X.to_device(jobs, DEV)
+    pd, invd = params.to(DEV), inv_buf.to(DEV)
+    outs = []
+    for _ in range(2):
+        gd = grads.to(DEV)
+        if ranged:
+            _lib.check(lib().ipoke_wn_bwd_multi_range(ptr(pd), ptr(gd), ptr(invd), ptr(table), jb, nj, r0, nr, stream()))
+        else:
+            _lib.check(lib().ipoke_wn_bwd_multi(ptr(pd), ptr(gd), ptr(invd), ptr(table), len(jobs), total_rows, stream()))
+        torch.cuda.synchronize()
+        outs.append(gd.cpu())
+    got = outs[0]
+    untouched = torch.ones(got.numel(), dtype=torch.bool)
+    worst = dict(dg=0.0, dv=0.0)
+    for j, (g, v, dw) in zip(jobs, vals):
+        inv32 = inv_buf[j.out_off:j.out_off + j.rows]
+        dg, dv = X.wn_bwd_ref(v, g, dw, inv32)
+        mdg, mdv = X.wn_bwd_mags(v, g, dw, inv32)
+        sel = torch.tensor([r0 <= j.row_start + r < r0 + nr for r in range(j.rows)])
+        rows = torch.nonzero(sel).reshape(-1)
+        untouched[j.g_off + rows] = False
+        worst["dg"] = max(worst["dg"], X.units(got[j.g_off + rows], dg[sel], mdg[sel]))
+        for r in rows.tolist():
+            sl = slice(j.v_off + r * j.K, j.v_off + (r + 1) * j.K)
+            worst["dv"] = max(worst["dv"], X.units(got[sl], dv[r], mdv[r]))
+            untouched[sl] = False
+    print(f"weight norm dg / dv on real rows: worst {worst} units, bounds {X.wn_bound('dg')} / {X.wn_bound('dv')}")
+    assert worst["dg"] <= X.wn_bound("dg") and worst["dv"] <= X.wn_bound("dv"), worst
+    assert torch.equal(got[untouched].view(torch.int32), grads[untouched].view(torch.int32)), "store outside the rows of the range"
+    assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32)), "two runs differ"
+    assert torch.equal(pd.cpu(), params)
+
+
 # ------------------------------------------------------------------ relayout: ipoke_relayout_multi(_range)
 def _relayout_jobs():
     """(job, source element count): taps 9 / 6 / 1, strided sources both ways, the 16-byte 1 x 1 path with k_real % 4 != 0, a

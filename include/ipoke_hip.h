@@ -970,6 +970,28 @@ int64_t ipoke_poke_workspace_bytes(int B, int H, int W, int poke_size, int n_pok
 int ipoke_poke_simulate(const float* flow, int B, int H, int W, int poke_size, int n_pokes, int fix_n_pokes, int equal_poke_val,
                         const int* zero_poke, const float* u, float* poke, int64_t* centers, float* flow_out, int* status, void* workspace,
                         void* stream);
+/* _get_poke with filter_flow on (:520-538, :577-583; the default of the Iper and Taichi data sets, data/flow_dataset.py:357, 375):
+ * ipoke_poke_simulate with a foreground mask uint8 [B][H][W] (nonzero = foreground, the reference's self.mask["img_start"]).  On the
+ * window, with amp the normalised amplitude:
+ *   ordinary sample   amp_filt = mask ? amp : 0; mean and unbiased std of amp_filt; candidates amp_filt > mean + 2 std, and where that
+ *                     set is empty amp > mean + std, then amp > mean -- the two fallbacks test the UNFILTERED amp against amp_filt's
+ *                     statistics, as :577-583 do;
+ *   zero-poke sample  statistics and value sources as without a mask (:530, :543-553); the centres are the window positions where the
+ *                     mask is zero, in row-major order, and only where there is none those below the 5th percentile (:534-538).
+ * Poke count, picks, outputs and status as in ipoke_poke_simulate; mask == NULL is ipoke_poke_simulate itself, bit for bit.  The sums
+ * are taken in double in a fixed order and no atomics touch floats: two runs are bit-identical.  workspace:
+ * ipoke_poke_masked_workspace_bytes (one more window array than ipoke_poke_workspace_bytes). */
+int64_t ipoke_poke_masked_workspace_bytes(int B, int H, int W, int poke_size, int n_pokes);
+int ipoke_poke_simulate_masked(const float* flow, int B, int H, int W, int poke_size, int n_pokes, int fix_n_pokes, int equal_poke_val,
+                               const int* zero_poke, const float* u, const uint8_t* mask, float* poke, int64_t* centers, float* flow_out,
+                               int* status, void* workspace, void* stream);
+/* _compute_mask_with_flow (:343-351, the mask source that use_flow_for_weights selects): over the WHOLE H x W map of flow [B][2][H][W],
+ * amp = sqrt(fx^2 + fy^2) in fp32 without contraction, minus its minimum, divided by its maximum; mask uint8 [B][H][W] = amp > mean + std
+ * (unbiased std, the sums in double in a fixed order, the threshold one fp32 add).  status int32 [B]: 1 for a constant map, which is 0 / 0
+ * everywhere and gives an all-zero mask, else 0.  One workgroup per sample, no atomics.  workspace: ipoke_flow_mask_workspace_bytes,
+ * owned by the caller. */
+int64_t ipoke_flow_mask_workspace_bytes(int B, int H, int W);
+int ipoke_flow_mask(const float* flow, int B, int H, int W, uint8_t* mask, int* status, void* workspace, void* stream);
 /* Poke editing.  Both entry points write squares with the semantics of the reference's slice assignment
  *     p[:, r - half : r + half + 1, c - half : c + half + 1] = v
  * under Python's slice rules: a start (or stop) below zero wraps once by the extent and then clamps at 0, one above the extent clamps at

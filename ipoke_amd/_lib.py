@@ -301,6 +301,10 @@ SIGNATURES = {
     "ipoke_flow_resize": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P]),
     "ipoke_poke_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "ipoke_poke_simulate": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ipoke_poke_masked_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "ipoke_poke_simulate_masked": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ipoke_flow_mask_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "ipoke_flow_mask": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P]),
     "ipoke_poke_stamp": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "ipoke_poke_randomize_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "ipoke_poke_randomize": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),

@@ -35,6 +35,7 @@ constexpr int kMaxPokes = 16;
 struct PokeArgs {
   const float* flow; int B, H, W, poke_size, n_pokes, fix_n_pokes;
   const int* zero; const float* u; float* amp; int* sel; long long* centers; int* status;
+  const uint8_t* mask; float* amp_filt;                        // the masked instantiation only
 };
 
 __device__ __forceinline__ double block_sum_d(double v, double* red) {
@@ -112,6 +113,12 @@ __device__ void pick_positions(const float* a, int n, int mode, float thr, const
   __syncthreads();
 }
 
+// kMasked = false is _get_poke with filter_flow off.  kMasked = true (filter_flow on, :520-538 and :577-583) keeps a second window array:
+// for an ordinary sample amp_filt = mask ? amp : 0, which supplies the statistics and the candidates of the first rule, while the two
+// fallback rules test the unfiltered amp against those statistics; for a zero-poke sample the statistics and the value sources stay
+// with amp, the second array holds the indicator of the mask's background, and the centres are its positions -- the 5th-percentile rule
+// only when there is none.
+template <bool kMasked>
 __global__ __launch_bounds__(kPokeThreads) void poke_select_kernel(PokeArgs p) {
   __shared__ double red_d[16];
   __shared__ float red_f[16];
@@ -137,34 +144,58 @@ __global__ __launch_bounds__(kPokeThreads) void poke_select_kernel(PokeArgs p) {
   for (int i = tid; i < n; i += blockDim.x) { const float v = __fsub_rn(a[i], lo); a[i] = v; hi = fmaxf(hi, v); }
   hi = block_minmax(hi, true, red_f);
   double s = 0.0;
-  for (int i = tid; i < n; i += blockDim.x) { const float v = __fdiv_rn(a[i], hi); a[i] = v; s += (double)v; }
+  const float* st = a;                                               // the array the statistics are taken of
+  if constexpr (kMasked) {
+    float* af = p.amp_filt + (long)b * n;
+    const uint8_t* m = p.mask + (long)b * p.H * p.W;
+    if (!zero) st = af;
+    for (int i = tid; i < n; i += blockDim.x) {
+      const float v = __fdiv_rn(a[i], hi);
+      const bool fg = m[(h0 + i / ww) * p.W + w0 + i % ww] != 0;
+      const float f = zero ? (fg ? 0.f : 1.f) : (fg ? v : 0.f);
+      a[i] = v; af[i] = f; s += (double)(zero ? v : f);
+    }
+  } else {
+    for (int i = tid; i < n; i += blockDim.x) { const float v = __fdiv_rn(a[i], hi); a[i] = v; s += (double)v; }
+  }
   const double mean_d = block_sum_d(s, red_d) / (double)n;
   double q = 0.0;
-  for (int i = tid; i < n; i += blockDim.x) { const double d = (double)a[i] - mean_d; q += d * d; }
+  for (int i = tid; i < n; i += blockDim.x) { const double d = (double)st[i] - mean_d; q += d * d; }
   const float mean = (float)mean_d, stdv = (float)sqrt(block_sum_d(q, red_d) / (double)(n - 1));
   const float t2 = __fadd_rn(mean, __fmul_rn(stdv, 2.0f)), t1 = __fadd_rn(mean, stdv);
 
   // candidate counts of every rule in one pass
   int c2 = 0, c1 = 0, c0 = 0;
-  for (int i = tid; i < n; i += blockDim.x) { const float v = a[i]; c2 += v > t2; c1 += v > t1; c0 += v > mean; }
+  for (int i = tid; i < n; i += blockDim.x) { const float v = a[i]; c2 += st[i] > t2; c1 += v > t1; c0 += v > mean; }
   int n2, n1, n0;
   block_scan(c2, sh_i, &n2); block_scan(c1, sh_i, &n1); block_scan(c0, sh_i, &n0);
-  int cand_mode, cand_cnt; float cand_thr;
+  int cand_mode, cand_cnt = 0; float cand_thr;
+  const float* cand_a = a;                                           // the array the centres are picked from
   int src_cnt = 0; float src_thr = t1;
   if (zero) {
-    // np.percentile(amplitude, 5), linear interpolation between the two neighbouring order statistics
-    const double vi = 0.05 * (double)(n - 1);
-    const int k = (int)floor(vi);
-    const double g = vi - (double)k;
-    const float ak = kth_smallest(a, n, k, sh_i), ak1 = kth_smallest(a, n, min(k + 1, n - 1), sh_i);
-    const double diff = (double)ak1 - (double)ak;
-    const double pv = g >= 0.5 ? (double)ak1 - diff * (1.0 - g) : (double)ak + diff * g;
-    cand_thr = (float)pv; cand_mode = SEL_LT;
-    int cl = 0;
-    for (int i = tid; i < n; i += blockDim.x) cl += a[i] < cand_thr;
-    block_scan(cl, sh_i, &cand_cnt);
+    int nb = 0;
+    if constexpr (kMasked) {                                         // the background of the mask, where there is any (:534-536)
+      const float* af = p.amp_filt + (long)b * n;
+      int cb = 0;
+      for (int i = tid; i < n; i += blockDim.x) cb += af[i] > 0.5f;
+      block_scan(cb, sh_i, &nb);
+      if (nb > 0) { cand_a = af; cand_mode = SEL_GT0; cand_thr = 0.5f; cand_cnt = nb; }
+    }
+    if (nb == 0) {
+      // np.percentile(amplitude, 5), linear interpolation between the two neighbouring order statistics
+      const double vi = 0.05 * (double)(n - 1);
+      const int k = (int)floor(vi);
+      const double g = vi - (double)k;
+      const float ak = kth_smallest(a, n, k, sh_i), ak1 = kth_smallest(a, n, min(k + 1, n - 1), sh_i);
+      const double diff = (double)ak1 - (double)ak;
+      const double pv = g >= 0.5 ? (double)ak1 - diff * (1.0 - g) : (double)ak + diff * g;
+      cand_thr = (float)pv; cand_mode = SEL_LT;
+      int cl = 0;
+      for (int i = tid; i < n; i += blockDim.x) cl += a[i] < cand_thr;
+      block_scan(cl, sh_i, &cand_cnt);
+    }
     if (n1 > 0) { src_thr = t1; src_cnt = n1; } else { src_thr = mean; src_cnt = n0; }
-  } else if (n2 > 0) { cand_mode = SEL_GT2; cand_thr = t2; cand_cnt = n2; }
+  } else if (n2 > 0) { cand_a = st; cand_mode = SEL_GT2; cand_thr = t2; cand_cnt = n2; }
   else if (n1 > 0) { cand_mode = SEL_GT1; cand_thr = t1; cand_cnt = n1; }
   else { cand_mode = SEL_GT0; cand_thr = mean; cand_cnt = n0; }
 
@@ -178,7 +209,7 @@ __global__ __launch_bounds__(kPokeThreads) void poke_select_kernel(PokeArgs p) {
   const int np = p.fix_n_pokes ? p.n_pokes : 1 + (int)floor((double)u[0] * (double)min(p.n_pokes, cand_cnt));
   if (tid < np) picks[tid] = (int)floor((double)u[1 + p.n_pokes + tid] * (double)cand_cnt);
   __syncthreads();
-  pick_positions(a, n, cand_mode == SEL_LT ? SEL_LT : SEL_GT0, cand_thr, picks, np, pos, sh_i);
+  pick_positions(cand_a, n, cand_mode == SEL_LT ? SEL_LT : SEL_GT0, cand_thr, picks, np, pos, sh_i);
   if (zero) {
     if (tid < np) picks[tid] = (int)floor((double)u[1 + tid] * (double)src_cnt);
     __syncthreads();
@@ -194,6 +225,38 @@ __global__ __launch_bounds__(kPokeThreads) void poke_select_kernel(PokeArgs p) {
     e[2] = on ? (zero ? h0 + pos_src[tid] / ww : r) : -1;
     e[3] = on ? (zero ? w0 + pos_src[tid] % ww : c) : -1;
   }
+}
+
+// _compute_mask_with_flow (:343-351), one workgroup per sample over the whole H x W map: amplitude as above, shifted to min 0, scaled to
+// max 1, mask = amplitude > mean + std (double sums in a fixed order, the threshold one fp32 add).  A constant map is 0 / 0 everywhere:
+// no pixel passes and the sample is flagged.
+__global__ __launch_bounds__(kPokeThreads) void flow_mask_kernel(const float* __restrict__ flow, int H, int W, float* __restrict__ amp,
+                                                                  uint8_t* __restrict__ mask, int* __restrict__ status) {
+  __shared__ double red_d[16];
+  __shared__ float red_f[16];
+  const int b = blockIdx.x, tid = threadIdx.x, n = H * W;
+  const float* fx = flow + (long)b * 2 * n;
+  const float* fy = fx + n;
+  float* a = amp + (long)b * n;
+  uint8_t* m = mask + (long)b * n;
+  float lo = INFINITY;
+  for (int i = tid; i < n; i += blockDim.x) {
+    const float vx = fx[i], vy = fy[i];
+    const float v = __fsqrt_rn(__fadd_rn(__fmul_rn(vx, vx), __fmul_rn(vy, vy)));
+    a[i] = v; lo = fminf(lo, v);
+  }
+  lo = block_minmax(lo, false, red_f);
+  float hi = -INFINITY;
+  for (int i = tid; i < n; i += blockDim.x) { const float v = __fsub_rn(a[i], lo); a[i] = v; hi = fmaxf(hi, v); }
+  hi = block_minmax(hi, true, red_f);
+  double s = 0.0;
+  for (int i = tid; i < n; i += blockDim.x) { const float v = __fdiv_rn(a[i], hi); a[i] = v; s += (double)v; }
+  const double mean_d = block_sum_d(s, red_d) / (double)n;
+  double q = 0.0;
+  for (int i = tid; i < n; i += blockDim.x) { const double d = (double)a[i] - mean_d; q += d * d; }
+  const float thr = __fadd_rn((float)mean_d, (float)sqrt(block_sum_d(q, red_d) / (double)(n - 1)));
+  for (int i = tid; i < n; i += blockDim.x) m[i] = a[i] > thr ? 1 : 0;
+  if (tid == 0) status[b] = hi > 0.f ? 0 : 1;
 }
 
 // poke[b][ch][y][x] = value of the LAST poke whose window covers (y, x) (later pokes overwrite earlier ones), else 0;
@@ -378,20 +441,51 @@ extern "C" int64_t ipoke_poke_workspace_bytes(int B, int H, int W, int poke_size
   return (int64_t)B * (n * (long)sizeof(float) + (1 + 4L * n_pokes) * (long)sizeof(int));
 }
 
-extern "C" int ipoke_poke_simulate(const float* flow, int B, int H, int W, int poke_size, int n_pokes, int fix_n_pokes, int equal_poke_val,
-                                   const int* zero_poke, const float* u, float* poke, int64_t* centers, float* flow_out, int* status, void* workspace,
-                                   void* stream) {
+static int poke_simulate(const float* flow, int B, int H, int W, int poke_size, int n_pokes, int fix_n_pokes, int equal_poke_val,
+                         const int* zero_poke, const float* u, const uint8_t* mask, float* poke, int64_t* centers, float* flow_out, int* status,
+                         void* workspace, void* stream) {
   IPK_REQUIRE(flow && u && poke && centers && status && workspace, "null argument");
   IPK_REQUIRE(B >= 1 && poke_size >= 1 && n_pokes >= 1 && n_pokes <= kMaxPokes, "bad poke configuration");
   IPK_REQUIRE(H > 2 * poke_size + 1 && W > 2 * poke_size + 1, "the candidate window [poke_size, size - poke_size) is empty");
   const long n = (long)(H - 2 * poke_size) * (W - 2 * poke_size);
   PokeArgs a;
   a.flow = flow; a.B = B; a.H = H; a.W = W; a.poke_size = poke_size; a.n_pokes = n_pokes; a.fix_n_pokes = fix_n_pokes;
-  a.zero = zero_poke; a.u = u; a.amp = reinterpret_cast<float*>(workspace);
-  a.sel = reinterpret_cast<int*>(a.amp + (long)B * n); a.centers = reinterpret_cast<long long*>(centers); a.status = status;
-  hipLaunchKernelGGL(poke_select_kernel, dim3(B), dim3(kPokeThreads), 0, STREAM(stream), a);
+  a.zero = zero_poke; a.u = u; a.amp = reinterpret_cast<float*>(workspace); a.mask = mask;
+  a.amp_filt = mask ? a.amp + (long)B * n : nullptr;
+  a.sel = reinterpret_cast<int*>(a.amp + (mask ? 2 : 1) * (long)B * n); a.centers = reinterpret_cast<long long*>(centers); a.status = status;
+  if (mask) hipLaunchKernelGGL(poke_select_kernel<true>, dim3(B), dim3(kPokeThreads), 0, STREAM(stream), a);
+  else hipLaunchKernelGGL(poke_select_kernel<false>, dim3(B), dim3(kPokeThreads), 0, STREAM(stream), a);
   hipLaunchKernelGGL(poke_fill_kernel, dim3(grid1((long)B * H * W)), dim3(256), 0, STREAM(stream), flow, a.sel, zero_poke, poke, flow_out, B, H, W,
                      poke_size / 2, n_pokes, equal_poke_val);
+  IPK_LAUNCH_CHECK();
+  return IPOKE_OK;
+}
+
+extern "C" int ipoke_poke_simulate(const float* flow, int B, int H, int W, int poke_size, int n_pokes, int fix_n_pokes, int equal_poke_val,
+                                   const int* zero_poke, const float* u, float* poke, int64_t* centers, float* flow_out, int* status, void* workspace,
+                                   void* stream) {
+  return poke_simulate(flow, B, H, W, poke_size, n_pokes, fix_n_pokes, equal_poke_val, zero_poke, u, nullptr, poke, centers, flow_out, status,
+                       workspace, stream);
+}
+
+extern "C" int64_t ipoke_poke_masked_workspace_bytes(int B, int H, int W, int poke_size, int n_pokes) {
+  const long n = (long)(H - 2 * poke_size) * (W - 2 * poke_size);
+  return (int64_t)B * (2 * n * (long)sizeof(float) + (1 + 4L * n_pokes) * (long)sizeof(int));
+}
+
+extern "C" int ipoke_poke_simulate_masked(const float* flow, int B, int H, int W, int poke_size, int n_pokes, int fix_n_pokes, int equal_poke_val,
+                                          const int* zero_poke, const float* u, const uint8_t* mask, float* poke, int64_t* centers,
+                                          float* flow_out, int* status, void* workspace, void* stream) {
+  return poke_simulate(flow, B, H, W, poke_size, n_pokes, fix_n_pokes, equal_poke_val, zero_poke, u, mask, poke, centers, flow_out, status,
+                       workspace, stream);
+}
+
+extern "C" int64_t ipoke_flow_mask_workspace_bytes(int B, int H, int W) { return (int64_t)B * H * W * (long)sizeof(float); }
+
+extern "C" int ipoke_flow_mask(const float* flow, int B, int H, int W, uint8_t* mask, int* status, void* workspace, void* stream) {
+  IPK_REQUIRE(flow && mask && status && workspace, "null argument");
+  IPK_REQUIRE(B >= 1 && H >= 1 && W >= 1 && (long)H * W >= 2 && (long)H * W < (1L << 30), "bad flow shape");
+  hipLaunchKernelGGL(flow_mask_kernel, dim3(B), dim3(kPokeThreads), 0, STREAM(stream), flow, H, W, reinterpret_cast<float*>(workspace), mask, status);
   IPK_LAUNCH_CHECK();
   return IPOKE_OK;
 }

@@ -4,7 +4,9 @@
 poke_size, n_pokes, fix_n_pokes, equal_poke_val, scale_poke_to_res) and offers
 
     get_flow(raw)                 _get_flow (:651-693)   raw flows [B, 2, Hs, Ws] -> [B, 2, H, W] (scaled to the resolution, bilinear)
-    get_poke(flow, zero, u)       _get_poke (:507-648)   -> (poke [B, 2, H, W], poke_centers int64 [B, n_pokes, 2], flow_out, status)
+    get_poke(flow, zero, u)       _get_poke (:507-648)   -> (poke [B, 2, H, W], poke_centers int64 [B, n_pokes, 2], flow_out, status);
+                                  with mask= the filter_flow branches (:520-538, :577-583)
+    flow_mask(flow)               _compute_mask_with_flow (:343-351)   -> (mask bool [B, H, W], status)
     stamp(centers, values | flow) squares of given values, or of the flow at the centres, on a zero poke (models/second_stage_video.py
                                   :959-966, testing/gui.py:120-150)
     randomize_pokes(flow, centers, n)  the re-aimed pokes of the control-sensitivity study (models/second_stage_video.py:798-833)
@@ -115,8 +117,10 @@ class ClipAugmenter:
     by its flow (:204-206).  ``config`` is the ``data`` section (:86-93): augment, p_col, p_geom, augment_b/c/h/s, aug_deg, aug_trans,
     spatial_size.
 
-    Out of scope: ``fancy_aug`` (use_fb_aug, :425-442), which blends a second colour draw in through the segmentation masks, and
-    ``_get_flip_transform`` (:724-729), which nothing calls."""
+    Out of scope: ``fancy_aug`` (use_fb_aug, :425-442), which blends a second colour draw in through the foreground mask into an
+    ``img_aT`` entry no model here consumes -- the mask itself is on the device now (``PokeSimulator.flow_mask`` / ``get_poke(mask=)``),
+    the blend is not; the warp of a caller's mask, which ``make_batch`` takes in the augmented frame; cv2.grabCut (_compute_mask,
+    :327-341), the loader's; and ``_get_flip_transform`` (:724-729), which nothing calls."""
 
     def __init__(self, config):
         self.config = config
@@ -185,6 +189,9 @@ class PokeSimulator:
             raise ValueError("poke_size must be integral (the reference slices tensors with it)")
         self.poke_size = int(self.poke_size)
         self.equal_poke_val = bool(config.get("equal_poke_val", True))
+        # the mask path of _get_poke (:520-538) and its flow-derived source (:353-359); off in BaseDataset (:67, :188)
+        self.filter_flow = bool(config.get("filter_flow", False))
+        self.use_flow_for_weights = bool(config.get("use_flow_for_weights", False))
         self.valid_h = [self.poke_size, self.spatial_size[0] - self.poke_size]
         self.valid_w = [self.poke_size, self.spatial_size[1] - self.poke_size]
 
@@ -198,14 +205,23 @@ class PokeSimulator:
         check(_lib.lib().ipoke_flow_resize(ptr(raw), ptr(out), B, C, Hs, Ws, H, W, div, _lib.current_stream()))
         return out
 
-    def get_poke(self, flow, zero_poke=None, u=None, generator=None, strict=True):
+    def get_poke(self, flow, zero_poke=None, u=None, generator=None, strict=True, mask=None):
         """flow fp32 [B, 2, H, W] on the device; zero_poke: bool/int [B] (samples with seq_len_idx == -1) or None;
-        u: fp32 [B, 1 + 2 n_pokes] uniforms in [0, 1) or None (drawn on the device from ``generator``)."""
+        u: fp32 [B, 1 + 2 n_pokes] uniforms in [0, 1) or None (drawn on the device from ``generator``).
+
+        mask: bool or uint8 [B, H, W] on the device, nonzero = foreground -- the reference's ``self.mask["img_start"]`` under
+        ``filter_flow`` (data/base_dataset.py:520-538, :577-583; on by default for Iper and Taichi, data/flow_dataset.py:357, 375).
+        Ordinary samples then take their candidates from the amplitude inside the mask, zero-poke samples their centres from the
+        mask's background (``ipoke_poke_simulate_masked`` in include/ipoke_hip.h).  None is the unmasked call, unchanged."""
         _lib.require_gpu()
         flow = flow.contiguous().float()
         B, C, H, W = flow.shape
         assert C == 2 and (H, W) == self.spatial_size
         dev = flow.device
+        if mask is not None:
+            if mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (B, H, W):
+                raise ValueError(f"mask must be bool or uint8 [{B}, {H}, {W}], got {mask.dtype} {tuple(mask.shape)}")
+            mask = mask.to(dev).to(torch.uint8).contiguous()
         if u is None:
             u = torch.rand(B, 1 + 2 * self.n_pokes, device=dev, generator=generator)
         u = u.to(dev, torch.float32).contiguous()
@@ -215,12 +231,35 @@ class PokeSimulator:
         flow_out = torch.empty_like(flow)
         centers = torch.empty(B, self.n_pokes, 2, dtype=torch.int64, device=dev)
         status = torch.empty(B, dtype=torch.int32, device=dev)
-        ws = torch.empty(_lib.lib().ipoke_poke_workspace_bytes(B, H, W, self.poke_size, self.n_pokes), dtype=torch.uint8, device=dev)
-        check(_lib.lib().ipoke_poke_simulate(ptr(flow), B, H, W, self.poke_size, self.n_pokes, int(self.fix_n_pokes), int(self.equal_poke_val),
-                                             ptr(zero), ptr(u), ptr(poke), ptr(centers), ptr(flow_out), ptr(status), ptr(ws), _lib.current_stream()))
+        if mask is None:
+            ws = torch.empty(_lib.lib().ipoke_poke_workspace_bytes(B, H, W, self.poke_size, self.n_pokes), dtype=torch.uint8, device=dev)
+            check(_lib.lib().ipoke_poke_simulate(ptr(flow), B, H, W, self.poke_size, self.n_pokes, int(self.fix_n_pokes), int(self.equal_poke_val),
+                                                 ptr(zero), ptr(u), ptr(poke), ptr(centers), ptr(flow_out), ptr(status), ptr(ws),
+                                                 _lib.current_stream()))
+        else:
+            ws = torch.empty(_lib.lib().ipoke_poke_masked_workspace_bytes(B, H, W, self.poke_size, self.n_pokes), dtype=torch.uint8, device=dev)
+            check(_lib.lib().ipoke_poke_simulate_masked(ptr(flow), B, H, W, self.poke_size, self.n_pokes, int(self.fix_n_pokes),
+                                                        int(self.equal_poke_val), ptr(zero), ptr(u), ptr(mask), ptr(poke), ptr(centers),
+                                                        ptr(flow_out), ptr(status), ptr(ws), _lib.current_stream()))
         if strict and bool(status.any()):
             raise FlowError(f"Empty indices array for samples {status.nonzero().flatten().tolist()}")
         return poke, centers, flow_out, status
+
+    def flow_mask(self, flow):
+        """The foreground mask the reference derives from the flow itself (_compute_mask_with_flow, data/base_dataset.py:343-351, the
+        source ``use_flow_for_weights`` selects in _get_mask :353-362): over the whole map, the amplitude shifted to min 0 and scaled to
+        max 1, thresholded at mean + std (``ipoke_flow_mask``).  flow fp32 [B, 2, H, W] on the device -> (mask bool [B, H, W], status
+        int32 [B]: 1 for a constant map, whose mask is empty).  Current stream, no host synchronisation."""
+        _lib.require_gpu()
+        flow = flow.contiguous().float()
+        B, C, H, W = flow.shape
+        assert C == 2 and (H, W) == self.spatial_size
+        dev = flow.device
+        mask = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        ws = torch.empty(_lib.lib().ipoke_flow_mask_workspace_bytes(B, H, W), dtype=torch.uint8, device=dev)
+        check(_lib.lib().ipoke_flow_mask(ptr(flow), B, H, W, ptr(mask), ptr(status), ptr(ws), _lib.current_stream()))
+        return mask.view(torch.bool), status
 
     def stamp(self, centers, values=None, flow=None, skip_negative=True):
         """A poke [B, 2, H, W] from its centres: zeros with ``p[:, r-half:r+half+1, c-half:c+half+1] = v`` applied for poke 0, 1, ... in that
@@ -276,11 +315,24 @@ class PokeSimulator:
                             f"(status {status[bad].tolist()})")
         return pokes, picked, status
 
-    def make_batch(self, images, raw_flow, zero_poke=None, u=None, generator=None, augment=None, frames_u8=None):
+    def make_batch(self, images, raw_flow, zero_poke=None, u=None, generator=None, augment=None, frames_u8=None, mask=None):
         """The ``batch`` dict the second stage consumes (images, flow, poke = [poke, poke_centers]) from frames already on the device
         and raw flows: the part of BaseDataset.__getitem__ that follows the file reads.  With ``augment`` (the parameters of
         ``ClipAugmenter.draw`` / ``params``) the order is the reference's: _get_flow -> the warp -> _get_poke, so the pokes are taken from
-        the warped flow, and ``images`` comes from the uint8 clip ``frames_u8`` [B, T, S, S, 3] through the colour chain and the same warp."""
+        the warped flow, and ``images`` comes from the uint8 clip ``frames_u8`` [B, T, S, S, 3] through the colour chain and the same warp.
+
+        ``mask`` is the foreground mask of ``filter_flow`` (see ``get_poke``).  ``"flow"`` computes it with ``flow_mask`` from the
+        sample's flow after the warp and before the zero-poke zeroing, the flow _get_mask sees (:353-359: _compute_mask_with_flow
+        calls _get_flow with ids whose last entry is not -1).  A tensor (bool / uint8 [B, H, W]) is used as given: the caller supplies
+        it in the augmented frame, no warp is applied to it.  With None the config decides: ``filter_flow`` with
+        ``use_flow_for_weights`` is ``"flow"``; ``filter_flow`` alone raises, since the reference's other source is cv2.grabCut on the
+        start frame (_compute_mask, :327-341), which stays with the caller's loader.  Where a mask is in play the batch gains ``"mask"`` (bool [B, H, W]); without one it is the
+        dict it was."""
+        if mask is None and self.filter_flow:
+            if not self.use_flow_for_weights:
+                raise ValueError("filter_flow is on: pass mask= (the reference's grabCut mask of the start frame, base_dataset.py:327-341, is "
+                                 "the caller's job), or mask='flow' / use_flow_for_weights for the flow-derived one")
+            mask = "flow"
         flow = self.get_flow(raw_flow)
         if augment is not None:
             if frames_u8 is None:
@@ -291,5 +343,12 @@ class PokeSimulator:
             images = augment_images(frames_u8, augment)
         # no host synchronisation on the loader path: samples without a candidate (the reference's FlowError) are flagged in
         # ``poke_status`` (int32 [B], 1 = resample), for the caller to inspect when it chooses to
-        poke, centers, flow_out, status = self.get_poke(flow, zero_poke, u, generator, strict=False)
-        return {"images": images, "flow": flow_out, "poke": [poke, centers], "poke_status": status}
+        if isinstance(mask, str):
+            if mask != "flow":
+                raise ValueError(f"mask={mask!r}: 'flow', a tensor or None")
+            mask, _ = self.flow_mask(flow)                 # a constant map has an empty mask and no poke candidate: poke_status flags it
+        poke, centers, flow_out, status = self.get_poke(flow, zero_poke, u, generator, strict=False, mask=mask)
+        batch = {"images": images, "flow": flow_out, "poke": [poke, centers], "poke_status": status}
+        if mask is not None:
+            batch["mask"] = mask.to(flow.device).bool()
+        return batch

@@ -3,7 +3,7 @@
 models/first_stage_image_conv.py, models/modules/autoencoders/fully_conv_models.py).
 
 The parameter holders are the blocks of ``ipoke_amd.first_stage`` (reference state-dict names), the differentiable ops are those of
-``ipoke_amd.first_stage_train`` (convolution, Group / InstanceNorm, spectral norm with power iteration, multi-tensor Adam).  New
+``ipoke_amd.autograd_ops`` (convolution, Group / InstanceNorm, spectral norm with power iteration, multi-tensor Adam).  New
 here: the decoder, the autoencoder modules, the loss with a device-resident log-variance (``ipoke_l1_nll``, csrc/ae2d_loss.hip),
 the two trainers and the plateau scheduler.
 
@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import autograd_ops as A
 from . import first_stage as FS
 from . import first_stage_train as FT
 from ._lib import check, ptr
@@ -54,8 +55,8 @@ def encode_train(enc, x, dt, pit):
     N, C, H, W = x.shape
     first = enc.model[0]
     st = (x.stride(0), x.stride(1), 0, x.stride(2), x.stride(3))
-    h = FT.conv(first.conv, None, dt, src=(x, N, C, (1, H, W), st), w=FT.effective_weight(first.conv, pit))
-    h = FT.norm(first.norm, h, dt, act=FS.ACT[first.activation])
+    h = A.conv(first.conv, None, dt, src=(x, N, C, (1, H, W), st), w=A.effective_weight(first.conv, pit))
+    h = A.norm(first.norm, h, dt, act=FS.ACT[first.activation])
     for blk in list(enc.model)[1:]:
         h = FT.res_block(blk, h, dt, pit=pit)
     return FT.res_block(enc.bottleneck[0], h, dt, pit=pit)
@@ -102,7 +103,7 @@ class _AutoencoderOps(nn.Module):
         """Drop cached weight operands (after an optimiser step or a state-dict load)."""
         for m in self.modules():
             m.__dict__.pop("_opcache", None)
-        FT.clear_operand_cache()
+        A.clear_operand_cache()
 
 
 def _check_deterministic(arch):
@@ -330,7 +331,7 @@ class _AutoencoderTrainer:
 
     def __init__(self, model, params, lr, weight_decay, perceptual, scheduler):
         self.model, self.perceptual = model, perceptual
-        self.opt = FT.MultiTensorAdam(params, lr, betas=(0.9, 0.999), weight_decay=weight_decay, eps=1e-8)
+        self.opt = A.MultiTensorAdam(params, lr, betas=(0.9, 0.999), weight_decay=weight_decay, eps=1e-8)
         self.scheduler = ReduceLROnPlateau(self.opt, **scheduler)
 
     def _loss(self, batch, power_iteration):

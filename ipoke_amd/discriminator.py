@@ -4,7 +4,7 @@ reference models/modules/discriminators/patchgan_3d.py:171-304 as ``first_stage_
 
 Parameter names equal the reference's state dict (``conv1.weight_orig / weight_u / weight_v``, ``gn1.weight``,
 ``layer2.0.downsample.0.weight_orig``, ``fc.weight`` ...).  Every layer runs through the differentiable ops of
-``first_stage_train`` (implicit-GEMM Conv3d with the spectral-norm kernels, GroupNorm + ReLU (+ residual)), plus
+``autograd_ops`` (implicit-GEMM Conv3d with the spectral-norm kernels, GroupNorm + ReLU (+ residual)), plus
 MaxPool3d / AvgPool3d from vae_train.hip.  Supported: predictions and the four feature maps, hinge / feature-matching /
 generator losses, gradients w.r.t. the parameters and w.r.t. the input clip.
 
@@ -20,7 +20,7 @@ import math
 import torch
 import torch.nn as nn
 
-from . import _lib, first_stage as FS, first_stage_train as T, nn as K, ops
+from . import _lib, autograd_ops as T, first_stage as FS, nn as K, ops
 from ._lib import check, ptr
 
 
@@ -230,7 +230,7 @@ class TemporalDiscriminator(nn.Module):
         B, C, Tn, H, W = x.shape
         w1 = T.effective_weight(self.conv1, pit)
         if x.requires_grad:          # generator side: the clip itself needs a gradient -> enter through a channels-last copy
-            xcl = T._pad_cols(x.permute(0, 2, 3, 4, 1).reshape(-1, C), K.round_up(C, K.e16(dt)), dt)
+            xcl = T.pad_cols(x.permute(0, 2, 3, 4, 1).reshape(-1, C), K.round_up(C, K.e16(dt)), dt)
             h = T.conv(self.conv1, K.CL(xcl, B, (Tn, H, W), C), dt, w=w1)
         else:
             x = x.float()
@@ -247,9 +247,8 @@ class TemporalDiscriminator(nn.Module):
         if Hh != self.last or Ww != self.last:
             raise ValueError(f"AvgPool3d((1, {self.last}, {self.last})) does not cover the {Hh}x{Ww} map: only the global case is built")
         p = _AvgPoolRowsFn.apply(h.t, B * D, Hh * Ww, h.C, dt)
-        meta = dict(N=B, dhw=(D, 1, 1), cin=h.C, cout=self.num_classes, k=(1, 1, 1), stride=(1, 1, 1), pad=(0, 0, 0), transposed=False,
-                    out_pad=(0, 0, 0), dtype=dt, act=_lib.ACT_NONE, out_f32=True, src=None)
-        rows = T._ConvFn.apply(p, self.fc.weight.view(self.num_classes, h.C, 1, 1, 1), None, meta)       # [B*D, >= num_classes] fp32
+        rows = T.conv_weight(K.CL(p, B, (D, 1, 1), h.C), self.fc.weight.view(self.num_classes, h.C, 1, 1, 1), None, (1, 1, 1), (1, 1, 1),
+                             (0, 0, 0), dt, out_f32=True).t                                          # [B*D, >= num_classes] fp32
         pred = rows[:, :self.num_classes].float().reshape(B, D * self.num_classes)
         return pred, fmaps
 
@@ -288,13 +287,11 @@ class TemporalDiscriminator(nn.Module):
             for blk in getattr(self, f"layer{li}"):
                 hp, hd = _block_pair(blk, hp, hd, dt)
         D, Hh, Ww = hp.dhw
-        meta = dict(N=B, dhw=(D, 1, 1), cin=hp.C, cout=self.num_classes, k=(1, 1, 1), stride=(1, 1, 1), pad=(0, 0, 0), transposed=False,
-                    out_pad=(0, 0, 0), dtype=dt, act=_lib.ACT_NONE, out_f32=True, src=None)
         wfc = self.fc.weight.view(self.num_classes, hp.C, 1, 1, 1)
         outs = []
         for h in (hp, hd):
             pooled = _AvgPoolRowsFn.apply(h.t, B * D, Hh * Ww, h.C, dt)
-            rows = T._ConvFn.apply(pooled, wfc, None, dict(meta))
+            rows = T.conv_weight(K.CL(pooled, B, (D, 1, 1), h.C), wfc, None, (1, 1, 1), (1, 1, 1), (0, 0, 0), dt, out_f32=True).t
             outs.append(rows[:, :self.num_classes].float().reshape(B, D * self.num_classes))
         return outs[0], outs[1]
 
@@ -348,7 +345,7 @@ class PatchDiscriminator(nn.Module):
         N, C, H, W = x.shape
         w0 = T.effective_weight(self.in_conv, pit)
         if x.requires_grad:
-            xcl = T._pad_cols(x.permute(0, 2, 3, 1).reshape(-1, C), K.round_up(C, K.e16(dt)), dt)
+            xcl = T.pad_cols(x.permute(0, 2, 3, 1).reshape(-1, C), K.round_up(C, K.e16(dt)), dt)
             h = T.conv(self.in_conv, K.CL(xcl, N, (1, H, W), C), dt, act=_lib.ACT_LRELU02, w=w0)
         else:
             x = x.float()

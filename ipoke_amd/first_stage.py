@@ -34,8 +34,8 @@ class _Cached(nn.Module):
     def invalidate(self):
         for m in self.modules():
             m.__dict__.pop("_opcache", None)
-        from . import first_stage_train
-        first_stage_train.clear_operand_cache()
+        from . import autograd_ops
+        autograd_ops.clear_operand_cache()
 
     def _load_from_state_dict(self, *a, **k):
         self.__dict__.pop("_opcache", None)
@@ -587,16 +587,16 @@ class SpadeCondMotionModel(nn.Module):
         # clip's start frame.  In evaluation mode (no power iteration between the reference's per-frame calls) the frames are
         # therefore decoded as ONE batch of length x B samples -- 15x fewer launches, and the 8x8 ... 32x32 stages become
         # GEMMs of a useful height (c5: 63.6 -> see DESIGN.md section 7).  Chunked so that row offsets stay below 2^31 elements.
-        from . import first_stage_train as FT
+        from . import autograd_ops as A
         seq = None
-        if FT.gru_native_ok(self.rnn, in_rnn, m, dt):
+        if A.gru_native_ok(self.rnn, in_rnn, m, dt):
             # the ConvGRU steps issued natively (csrc/gru.hip): one call instead of length x n_layers cells of Python launches
             weights = []
             for c in self.rnn.cells:
                 weights += [torch.cat([c.update_gate.weight, c.reset_gate.weight], 0), torch.cat([c.update_gate.bias, c.reset_gate.bias]),
                             c.out_gate.weight, c.out_gate.bias]
             geom = (B, length, self.n_layers, in_rnn.C, m.C, m.dhw[1], m.dhw[2])
-            seq, _ = FT.gru_unroll_forward(weights, in_rnn.t.contiguous(), m.t.contiguous(), geom, dt)
+            seq, _ = A.gru_unroll_forward(weights, in_rnn.t.contiguous(), m.t.contiguous(), geom, dt)
             rows = B * m.S
         else:
             hs = []
@@ -690,5 +690,5 @@ class SpadeCondMotionModel(nn.Module):
         """Drop the cached inference weight operands (after an optimiser step or a state-dict load)."""
         for m in self.modules():
             m.__dict__.pop("_opcache", None)
-        from . import first_stage_train
-        first_stage_train.clear_operand_cache()
+        from . import autograd_ops
+        autograd_ops.clear_operand_cache()

@@ -9,7 +9,7 @@
        w_l1 * L1 + w_kl * KL (+ w_vgg * VGG);  Adam step                                                          (:226-277)
 
 with three ``Adam(lr, betas=(0.5, 0.9), weight_decay)`` optimisers (:376-386).  Everything runs through the differentiable
-HIP ops of ``first_stage_train`` / ``discriminator`` and ``ipoke_adam_multi``; the gradient penalty is evaluated
+HIP ops of ``autograd_ops`` / ``discriminator`` and ``ipoke_adam_multi``; the gradient penalty is evaluated
 forward-over-reverse (``TemporalDiscriminator.gp2``).
 
 The VGG perceptual term (``w_vgg``, utils/losses.py:67-82) is ``ipoke_amd.vgg.VGGLoss``, passed in by the caller with the
@@ -20,7 +20,8 @@ global RNG) are arguments, so that the caller owns the random stream.
 import numpy as np
 import torch
 
-from . import first_stage_train as T
+from .autograd_ops import MultiTensorAdam
+from .first_stage_train import first_stage_forward_loss
 
 
 class FirstStageGANTrainer:
@@ -36,9 +37,9 @@ class FirstStageGANTrainer:
         self.w_l1, self.w_kl = float(tr["w_l1"]), float(tr["w_kl"])
         self.mf_dt = min(int(cfg["d_t"]["max_frames"]), int(cfg["data"]["max_frames"]))
         kw = dict(lr=tr["lr"], betas=(0.5, 0.9), weight_decay=tr["weight_decay"])
-        self.opt_g = T.MultiTensorAdam(model.parameters(), **kw)
-        self.opt_dt = T.MultiTensorAdam(disc_t.parameters(), **kw) if disc_t is not None else None
-        self.opt_ds = T.MultiTensorAdam(disc_s.parameters(), **kw) if disc_s is not None else None
+        self.opt_g = MultiTensorAdam(model.parameters(), **kw)
+        self.opt_dt = MultiTensorAdam(disc_t.parameters(), **kw) if disc_t is not None else None
+        self.opt_ds = MultiTensorAdam(disc_s.parameters(), **kw) if disc_s is not None else None
         self.gamma = float(tr.get("gamma", 0.98))                    # first_stage.yaml:45
 
     def optimizers(self):
@@ -74,7 +75,7 @@ class FirstStageGANTrainer:
         cdt = self.cfg["d_t"]
         pit = bool(power_iteration)
         log = {}
-        loss_rec, X_hat, mu, lv = T.first_stage_forward_loss(m, X, eps, w_l1=self.w_l1, w_kl=self.w_kl, power_iteration=pit)
+        loss_rec, X_hat, mu, lv = first_stage_forward_loss(m, X, eps, w_l1=self.w_l1, w_kl=self.w_kl, power_iteration=pit)
         X = X.float()
         true_ids = torch.as_tensor(np.asarray(true_ids), device=X.device, dtype=torch.long)
         fake_ids = torch.as_tensor(np.asarray(fake_ids), device=X.device, dtype=torch.long)

@@ -10,7 +10,7 @@ convolutions only -- the weights are frozen, so no weight gradient is formed.  T
 import torch
 import torch.nn as nn
 
-from . import _lib, first_stage as FS, first_stage_train as T, nn as K
+from . import _lib, autograd_ops as T, first_stage as FS, nn as K
 from .discriminator import _L1MeanFn, max_pool3d
 
 CFG_E = (64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512, 512, 512, 512, "M", 512)     # features[:30]
@@ -64,7 +64,7 @@ class VGG(nn.Module):
         N, C, H, W = X.shape
         first = self.slice1["0"]
         if X.requires_grad:
-            xcl = T._pad_cols(X.permute(0, 2, 3, 1).reshape(-1, C), K.round_up(C, K.e16(dt)), dt)
+            xcl = T.pad_cols(X.permute(0, 2, 3, 1).reshape(-1, C), K.round_up(C, K.e16(dt)), dt)
             h = T.conv(first, K.CL(xcl, N, (1, H, W), C), dt, act=_lib.ACT_RELU)
         else:
             X = X.float()

@@ -3,7 +3,7 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from ipoke_amd import _lib, nn as K
-from ipoke_amd import first_stage_train as FT
+from ipoke_amd import autograd_ops as FT
 from ipoke_amd.first_stage import ConvGRU
 from ipoke_amd._lib import check
 

@@ -5,7 +5,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from ipoke_amd import configs, first_stage as FS, first_stage_train as FT
+from ipoke_amd import configs, first_stage as FS, autograd_ops as FT
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 m = FS.SpadeCondMotionModel(configs.first_stage_config(128, 32, 16), dirs={}, train=False, dtype="bf16").cuda()

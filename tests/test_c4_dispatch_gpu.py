@@ -12,7 +12,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from ipoke_amd import _lib, first_stage as FS, first_stage_train as FT, nn as K, ops
+from ipoke_amd import _lib, autograd_ops as FT, first_stage as FS, nn as K, ops
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"

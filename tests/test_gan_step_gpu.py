@@ -13,7 +13,7 @@ from ipoke_amd import configs
 from ipoke_amd.discriminator import PatchDiscriminator, TemporalDiscriminator
 from ipoke_amd.first_stage import SpadeCondMotionModel
 from ipoke_amd.first_stage_gan import FirstStageGANTrainer
-from ipoke_amd.first_stage_train import MultiTensorAdam
+from ipoke_amd.autograd_ops import MultiTensorAdam
 from ipoke_amd.utils.detfill import deterministic_fill_
 from oracle import disc_ref, vae_ref, vgg_ref
 

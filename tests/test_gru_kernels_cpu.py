@@ -29,7 +29,7 @@ def err():
 def test_unforced_reference_equals_autograd_through_the_oracle(geom):
     """the phases chained in float64 without any rounding against torch autograd through oracle.vae_ref.ConvGRU driven as
     SpadeCondMotionModel.forward drives it: the output sequence, d x0, d h0 (summed over the cells), every weight and bias gradient"""
-    from ipoke_amd import first_stage_train as FT
+    from ipoke_amd import autograd_ops as FT
     c = Case(*geom, "f32", 0, True, 0)
     B, T, L, Cx, Ch, H, W = geom
     ops = X.operands(c, False)

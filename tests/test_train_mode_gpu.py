@@ -236,7 +236,7 @@ def test_weight_gradients_on_a_second_stream(golden, dtype, copies):
     ordering between the streams reads unfinished buffers), every parameter that has a gradient in the plain backward has one, and nothing
     is left parked.  (Two plain backward passes are not bit-identical either -- fp32 atomics in the norm statistics -- so the bar is the
     golden one.)"""
-    from ipoke_amd import first_stage_train as FT
+    from ipoke_amd import autograd_ops as FT
     g = golden("g13_first_stage_train_mode_128")
     X, eps = clip(g, copies=copies)
     side = torch.cuda.Stream()

@@ -7,7 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from ipoke_amd import _lib, nn as K, ops
-from ipoke_amd import first_stage_train as FT
+from ipoke_amd import autograd_ops as FT
 from ipoke_amd._lib import check, ptr
 
 pytestmark = pytest.mark.gpu

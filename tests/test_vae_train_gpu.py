@@ -18,7 +18,7 @@ DEV = "cuda"
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 @pytest.mark.parametrize("shape,transposed", [((40, 12, 3, 3), False), ((12, 40, 3, 3), True), ((16, 3, 3, 7, 7), False), ((64, 64, 1, 1), False)])
 def test_weight_operand_matches_the_torch_chain(shape, transposed, dtype):
-    from ipoke_amd.first_stage_train import _weight_operand
+    from ipoke_amd.autograd_ops import _weight_operand
     g = torch.Generator().manual_seed(1)
     w = torch.randn(*shape, generator=g).to(DEV)
     inv = torch.tensor([0.37], device=DEV)
@@ -122,7 +122,7 @@ def test_weight_operand_multi_matches_single_calls_and_the_refreshed_cache():
     launch takes (64) -- and the trainer-side cache: after ``take_operand_cache`` / raw-pointer update / ``refresh_operand_cache`` the
     cache hands out the SAME tensors holding the operands of the NEW values."""
     import ctypes as ct
-    from ipoke_amd import first_stage_train as FT
+    from ipoke_amd import autograd_ops as FT
     lib = _lib.lib()
     gen = torch.Generator().manual_seed(3)
     shapes = [((64, 3, 3, 3), 0), ((128, 64, 3, 3), 0), ((64, 128, 3, 3), 1), ((32, 20, 1, 1), 0), ((16, 8, 3, 3, 3), 0)] * 14     # 70 weights

@@ -6,7 +6,6 @@
 // gradient GEMMs are forked onto a side stream so that they overlap the serial data-gradient chain.
 //
 // Host code only (compiled by hipcc together with the kernels).
-#include <functional>
 #include <memory>
 #include <vector>
 #include <string>
@@ -517,7 +516,18 @@ struct Ctx {
   float* dld() const { return at<float>(plan.dld); }
   // per-sample partial sums of op op_index: `parts` rows of ldp floats per sample (fused unit launches split over workgroups)
   float* dbp(int op_index) const { return at<float>(plan.dbias_part) + (int64_t)op_index * (kMaxUnitSplit * B + 1) * 128; }
+  // optional ActNorm / Shuffle tensors of an op (a bare shuffle has no parameters, a plain ActNorm no permutation)
+  const float* an_ls(const Op& op) const { return op.p_ls >= 0 ? params + op.p_ls : nullptr; }
+  const float* an_bias(const Op& op) const { return op.p_bias >= 0 ? params + op.p_bias : nullptr; }
+  const int32_t* an_idx_fwd(const Op& op) const { return op.idx_fwd >= 0 ? perm + op.idx_fwd : nullptr; }
+  const int32_t* an_idx_bwd(const Op& op) const { return op.idx_bwd >= 0 ? perm + op.idx_bwd : nullptr; }
 };
+// address of entry i of a device table
+const unsigned char* tab_entry(const void* tab, size_t i, size_t entry_size) { return reinterpret_cast<const unsigned char*>(tab) + i * entry_size; }
+// the masked convs among the six ops of a MaCowUnit (two adjacent units: twelve ops) and the state index, relative to the unit's head,
+// each of them writes when states are saved
+constexpr int kUnitMcf[8] = {0, 1, 3, 4, 6, 7, 9, 10};
+constexpr int kUnitMcfOut[8] = {1, 3, 4, 6, 7, 9, 10, 12};
 
 void set_conv8(ipoke_conv_desc& d, int B, int k, int pad) {
   std::memset(&d, 0, sizeof(d));
@@ -532,6 +542,17 @@ void set_a_state(ipoke_conv_desc& d, const float* state, int ld, int off, int st
 void set_a_dense(ipoke_conv_desc& d, const void* act, int ld, int kc) {
   d.A = act; d.a_f32 = 0; d.a_sn = 64L * ld; d.a_sd = 0; d.a_sh = 8L * ld; d.a_sw = ld; d.a_sc = 1;
   d.a_coff = 0; d.Kc_real = kc; d.Kc = kc;
+}
+// weight gradient of a kh x kw convolution on the 8 x 8 latent grid; every other field zero
+void set_wgrad8(ipoke_wgrad_desc& w, int B, int kh, int kw, int pad) {
+  std::memset(&w, 0, sizeof(w));
+  w.NB = B; w.Di = 1; w.Hi = 8; w.Wi = 8; w.Do = 1; w.Ho = 8; w.Wo = 8; w.kd = 1; w.kh = kh; w.kw = kw;
+  w.sd = w.sh = w.sw = 1; w.ph = w.pw = pad;
+  w.max_workgroups = 0;
+}
+// its input operand: a dense [M][ld] matrix in the compute dtype
+void set_wa_dense(ipoke_wgrad_desc& w, int ld, int kc_real, int kc) {
+  w.a_f32 = 0; w.a_sn = 64L * ld; w.a_sh = 8L * ld; w.a_sw = ld; w.a_sc = 1; w.Kc_real = kc_real; w.Kc = kc;
 }
 
 int nice_splitk(const Ctx& c) { return max_splitk(*c.f, c.B); }
@@ -622,6 +643,45 @@ void mcf_desc(const Ctx& c, const Op& op, ipoke_mcf_desc& d) {
   d.W1 = c.sh(op.sh_w1); d.W2 = c.sh(op.sh_w2); d.bias2 = c.params + op.p_b; d.order = op.order;
   d.W1T = c.sh(op.sh_w1t); d.W2T = c.sh(op.sh_w2t);
 }
+// the ActNorm executed inside this layer's kernels
+void mcf_post(const Ctx& c, const Op& op, ipoke_mcf_desc& d) {
+  if (op.fuse_act < 0) return;
+  const Op& an = c.f->ops[op.fuse_act];
+  d.post_log_scale = c.params + an.p_ls; d.post_bias = c.params + an.p_bias;
+}
+// operands a training forward pass saves for the backward pass
+void mcf_saved(const Ctx& c, const Op& op, ipoke_mcf_desc& d) { d.a2_save = c.at<void>(op.ws_a); d.scale_save = c.at<float>(op.ws_b); }
+// backward of masked-conv op j: the saved operands, what it leaves for the deferred weight gradients, the partial sums of its bias
+// gradient and the fused ActNorm with its saved output and partial sums
+void mcf_saved_bwd(const Ctx& c, int j, ipoke_mcf_desc& d) {
+  const Op& op = c.f->ops[j];
+  mcf_saved(c, op, d);
+  d.dparams_save = c.at<void>(op.ws_c); d.dc_save = c.at<void>(op.ws_d);
+  if (c.f->mcf_xop) d.x_op_save = c.at<void>(op.ws_e);
+  d.dbias_part = c.dbp(j);
+  mcf_post(c, op, d);
+  if (op.fuse_act >= 0) { d.y_post = c.state(j + 2); d.post_part = c.dbp(op.fuse_act); }
+}
+// How a coupling net is launched at this batch size: conv3 + coupling in one launch (one_launch), conv2 in it as well (pair), the pair at
+// its two-launch slices (split: the parity hook), and the conv2 argument of nice_net that goes with them
+struct NiceRoute { bool one_launch, pair, split; int conv2; };
+NiceRoute nice_route(const Ctx& c, const Op& op, bool fusable = true) {
+  NiceRoute r;
+  r.one_launch = fusable && nice_fused(c, op);
+  r.pair = r.one_launch && nice_pair(c, op); r.split = r.pair && c.f->split_pair_coupling;
+  r.conv2 = r.pair ? (r.split ? 2 : 0) : 1;
+  return r;
+}
+// The coupling executed after coupling i (op i + dir; dir = 1 forward, -1 reverse) conditions on exactly the channels i transforms: the
+// operand buffer i's transform writes for it (null: none) and its pitch
+void* nice_ext(const Ctx& c, int i, int dir, bool save, int* ext_ld) {
+  const std::vector<Op>& ops = c.f->ops;
+  const int n = i + dir;
+  *ext_ld = 0;
+  if (n < 0 || n >= (int)ops.size() || !nice_feeds(ops[i], ops[n])) return nullptr;
+  *ext_ld = ops[n].Kc1;
+  return c.at<void>(save ? ops[n].ws_g : c.plan.tmp_zc);
+}
 
 // W, W^-1, wl, wu of every LU 1x1 conv into the workspace (one launch; the matrices depend on the current parameters)
 int lu_prepare_all(const Ctx& c) {
@@ -642,6 +702,13 @@ int common_checks(ipoke_flow* f, int B) {
 
 struct WgEntryH { long a_off, y_off, w_off; int kh, kw, ph, pw; long sh_off = 0; };      // mirrors TnBatchEntry of gemm.hip
 struct RedEntryH { long src, dst; int ld, ncols, rmul, pad; };   // rmul: rows per sample (ipoke_reduce_rows_multi sums R * rmul rows)
+
+// a host table copied into a device allocation of its own
+template <typename T> int upload(void** dst, const std::vector<T>& src) {
+  IPK_HIP(hipMalloc(dst, src.size() * sizeof(T)));
+  IPK_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+  return IPOKE_OK;
+}
 
 void drop_graphs(ipoke_flow* f) {
   for (auto& g : f->graphs) {
@@ -689,15 +756,11 @@ int ensure_tables(ipoke_flow* f, int B, const Plan& plan) {
   if (f->d_w1tab) { (void)hipFree(f->d_w1tab); (void)hipFree(f->d_w2tab); (void)hipFree(f->d_redtab); }
   for (int k = 0; k < 3; ++k) {
     if (f->d_ntab[k]) (void)hipFree(f->d_ntab[k]);
-    IPK_HIP(hipMalloc(&f->d_ntab[k], nt[k].size() * sizeof(WgEntryH)));
-    IPK_HIP(hipMemcpy(f->d_ntab[k], nt[k].data(), nt[k].size() * sizeof(WgEntryH), hipMemcpyHostToDevice));
+    int rc = upload(&f->d_ntab[k], nt[k]); if (rc) return rc;
   }
-  IPK_HIP(hipMalloc(&f->d_w1tab, w1.size() * sizeof(WgEntryH)));
-  IPK_HIP(hipMalloc(&f->d_w2tab, w2.size() * sizeof(WgEntryH)));
-  IPK_HIP(hipMalloc(&f->d_redtab, red.size() * sizeof(RedEntryH)));
-  IPK_HIP(hipMemcpy(f->d_w1tab, w1.data(), w1.size() * sizeof(WgEntryH), hipMemcpyHostToDevice));
-  IPK_HIP(hipMemcpy(f->d_w2tab, w2.data(), w2.size() * sizeof(WgEntryH), hipMemcpyHostToDevice));
-  IPK_HIP(hipMemcpy(f->d_redtab, red.data(), red.size() * sizeof(RedEntryH), hipMemcpyHostToDevice));
+  int rc = upload(&f->d_w1tab, w1); if (rc) return rc;
+  rc = upload(&f->d_w2tab, w2); if (rc) return rc;
+  rc = upload(&f->d_redtab, red); if (rc) return rc;
   f->n_red = (int)red.size();
   f->tab_B = B;
   return IPOKE_OK;
@@ -732,16 +795,24 @@ std::vector<std::pair<int, int>> backward_pieces(const ipoke_flow* f, int npiece
   }
   return pieces;
 }
-// flat-parameter ranges [begin, end) of a piece: layers.*, priors.* and (use1x1) shuffle_layers.* are separate regions
-void piece_param_ranges(const ipoke_flow* f, int lvl_lo, int lvl_hi, int64_t p0[3], int64_t p1[3]) {
-  for (int k = 0; k < 3; ++k) { p0[k] = -1; p1[k] = -1; }
-  for (int u = lvl_lo; u <= lvl_hi; ++u) {
+// Ranges of a piece (units lo .. hi).  layers.* and priors.* are separate flat regions: the units of one kind inside the piece form one
+// contiguous range each of flat parameters [p0, p1), weight-norm jobs [wj0, wj1) and weight-norm rows [rw0, rw1)
+// (use1x1: the LU convs' parameters form a third region, flow.shuffle_layers.*, without weight-norm rows)
+struct PieceRanges {
+  int64_t p0[3] = {-1, -1, -1}, p1[3] = {-1, -1, -1};
+  int wj0[3] = {0, 0, 0}, wj1[3] = {0, 0, 0}, rw0[3] = {0, 0, 0}, rw1[3] = {0, 0, 0};
+  bool has_params(int k) const { return p0[k] >= 0 && p1[k] > p0[k]; }
+};
+PieceRanges piece_ranges(const ipoke_flow* f, int unit_lo, int unit_hi) {
+  PieceRanges r;
+  for (int u = unit_lo; u <= unit_hi; ++u) {
     const auto& un = f->units[u];
     const int k = un.kind;
-    if (p0[k] < 0) p0[k] = un.p_lo;
-    p1[k] = un.p_hi;
-    if (un.p2_lo >= 0) { if (p0[2] < 0) p0[2] = un.p2_lo; p1[2] = un.p2_hi; }
+    if (r.p0[k] < 0) { r.p0[k] = un.p_lo; r.wj0[k] = un.wj_lo; r.rw0[k] = un.row_lo; }
+    r.p1[k] = un.p_hi; r.wj1[k] = un.wj_hi; r.rw1[k] = un.row_hi;
+    if (un.p2_lo >= 0) { if (r.p0[2] < 0) r.p0[2] = un.p2_lo; r.p1[2] = un.p2_hi; }
   }
+  return r;
 }
 
 hipEvent_t next_event(ipoke_flow* f) {
@@ -801,6 +872,17 @@ extern "C" int ipoke_flow_create(const ipoke_flow_config* cfg, ipoke_flow** out)
   return IPOKE_OK;
 }
 
+// a relayout job table and its block -> job map (saves every block of the launch a 12-step search through the job table)
+static int upload_relayout_jobs(const std::vector<RelayoutJobH>& jobs, int nblocks, void** d_jobs, void** d_blockjob) {
+  int rc = upload(d_jobs, jobs); if (rc) return rc;
+  std::vector<int32_t> bj((size_t)nblocks);
+  for (size_t k = 0; k < jobs.size(); ++k) {
+    const int b0 = jobs[k].block_start, b1 = k + 1 < jobs.size() ? jobs[k + 1].block_start : nblocks;
+    for (int b = b0; b < b1; ++b) bj[b] = (int32_t)k;
+  }
+  return upload(d_blockjob, bj);
+}
+
 // Device-side tables, the side stream and its events are created on first use so that the topology
 // (names, shapes, offsets) can be inspected on a host without a GPU.
 static int ensure_device(ipoke_flow* f) {
@@ -829,47 +911,18 @@ static int ensure_device(ipoke_flow* f) {
   }
   IPK_REQUIRE((int)sizeof(RelayoutJobH) == ipoke_relayout_job_size() && (int)sizeof(WnJobH) == ipoke_wn_job_size(),
               "job table layout mismatch");
-  IPK_HIP(hipMalloc(&f->d_rjobs, f->rjobs.size() * sizeof(RelayoutJobH)));
-  IPK_HIP(hipMemcpy(f->d_rjobs, f->rjobs.data(), f->rjobs.size() * sizeof(RelayoutJobH), hipMemcpyHostToDevice));
-  {   // block -> job map of the relayout launch (saves every block a 12-step search through the job table)
-    std::vector<int32_t> bj((size_t)f->rblocks);
-    for (size_t k = 0; k < f->rjobs.size(); ++k) {
-      const int b0 = f->rjobs[k].block_start, b1 = k + 1 < f->rjobs.size() ? f->rjobs[k + 1].block_start : f->rblocks;
-      for (int b = b0; b < b1; ++b) bj[b] = (int32_t)k;
-    }
-    IPK_HIP(hipMalloc(&f->d_rblockjob, bj.size() * sizeof(int32_t)));
-    IPK_HIP(hipMemcpy(f->d_rblockjob, bj.data(), bj.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  }
+  int rc = upload_relayout_jobs(f->rjobs, f->rblocks, &f->d_rjobs, &f->d_rblockjob); if (rc) return rc;
   IPK_REQUIRE((int)sizeof(AdamTileJobH) == ipoke_adam_tile_job_size() && (int)sizeof(AdamSegH) == ipoke_adam_seg_size(), "Adam table layout mismatch");
-  if (!f->ajobs.empty()) {
-    IPK_HIP(hipMalloc(&f->d_ajobs, f->ajobs.size() * sizeof(AdamTileJobH)));
-    IPK_HIP(hipMemcpy(f->d_ajobs, f->ajobs.data(), f->ajobs.size() * sizeof(AdamTileJobH), hipMemcpyHostToDevice));
-  }
-  if (!f->asegs.empty()) {
-    IPK_HIP(hipMalloc(&f->d_asegs, f->asegs.size() * sizeof(AdamSegH)));
-    IPK_HIP(hipMemcpy(f->d_asegs, f->asegs.data(), f->asegs.size() * sizeof(AdamSegH), hipMemcpyHostToDevice));
-  }
-  if (!f->rjobs2.empty()) {
-    IPK_HIP(hipMalloc(&f->d_rjobs2, f->rjobs2.size() * sizeof(RelayoutJobH)));
-    IPK_HIP(hipMemcpy(f->d_rjobs2, f->rjobs2.data(), f->rjobs2.size() * sizeof(RelayoutJobH), hipMemcpyHostToDevice));
-    std::vector<int32_t> bj((size_t)f->rblocks2);
-    for (size_t k = 0; k < f->rjobs2.size(); ++k) {
-      const int b0 = f->rjobs2[k].block_start, b1 = k + 1 < f->rjobs2.size() ? f->rjobs2[k + 1].block_start : f->rblocks2;
-      for (int b = b0; b < b1; ++b) bj[b] = (int32_t)k;
-    }
-    IPK_HIP(hipMalloc(&f->d_rblockjob2, bj.size() * sizeof(int32_t)));
-    IPK_HIP(hipMemcpy(f->d_rblockjob2, bj.data(), bj.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  }
-  IPK_HIP(hipMalloc(&f->d_wjobs, f->wjobs.size() * sizeof(WnJobH)));
-  IPK_HIP(hipMemcpy(f->d_wjobs, f->wjobs.data(), f->wjobs.size() * sizeof(WnJobH), hipMemcpyHostToDevice));
+  if (!f->ajobs.empty()) { rc = upload(&f->d_ajobs, f->ajobs); if (rc) return rc; }
+  if (!f->asegs.empty()) { rc = upload(&f->d_asegs, f->asegs); if (rc) return rc; }
+  if (!f->rjobs2.empty()) { rc = upload_relayout_jobs(f->rjobs2, f->rblocks2, &f->d_rjobs2, &f->d_rblockjob2); if (rc) return rc; }
+  rc = upload(&f->d_wjobs, f->wjobs); if (rc) return rc;
   if (!f->lujobs.empty()) {
     IPK_REQUIRE((int)sizeof(LuJobH) == ipoke_lu_job_size(), "LU job table layout mismatch");
-    IPK_HIP(hipMalloc(&f->d_lujobs, f->lujobs.size() * sizeof(LuJobH)));
-    IPK_HIP(hipMemcpy(f->d_lujobs, f->lujobs.data(), f->lujobs.size() * sizeof(LuJobH), hipMemcpyHostToDevice));
+    rc = upload(&f->d_lujobs, f->lujobs); if (rc) return rc;
   }
   IPK_REQUIRE((int)sizeof(LsRefH) == ipoke_actnorm_logdet_ref_size(), "ActNorm log-det reference table layout mismatch");
-  IPK_HIP(hipMalloc(&f->d_lsrefs, f->lsrefs.size() * sizeof(LsRefH)));
-  IPK_HIP(hipMemcpy(f->d_lsrefs, f->lsrefs.data(), f->lsrefs.size() * sizeof(LsRefH), hipMemcpyHostToDevice));
+  rc = upload(&f->d_lsrefs, f->lsrefs); if (rc) return rc;
   {   // weight gradients are off the critical path: lowest priority so that chain kernels get the CUs first
     int least = 0, greatest = 0;
     IPK_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
@@ -883,22 +936,9 @@ static int ensure_device(ipoke_flow* f) {
 
 extern "C" void ipoke_flow_destroy(ipoke_flow* f) {
   if (!f) return;
-  if (f->d_rjobs) (void)hipFree(f->d_rjobs);
-  if (f->d_wjobs) (void)hipFree(f->d_wjobs);
-  if (f->d_lsrefs) (void)hipFree(f->d_lsrefs);
-  if (f->d_lujobs) (void)hipFree(f->d_lujobs);
-  if (f->d_rblockjob) (void)hipFree(f->d_rblockjob);
-  if (f->d_ajobs) (void)hipFree(f->d_ajobs);
-  if (f->d_asegs) (void)hipFree(f->d_asegs);
-  if (f->d_rjobs2) (void)hipFree(f->d_rjobs2);
-  if (f->d_rblockjob2) (void)hipFree(f->d_rblockjob2);
-  if (f->d_w1tab) (void)hipFree(f->d_w1tab);
-  for (int k = 0; k < 3; ++k) if (f->d_ntab[k]) (void)hipFree(f->d_ntab[k]);
-  if (f->d_w2tab) (void)hipFree(f->d_w2tab);
-  if (f->d_redtab) (void)hipFree(f->d_redtab);
-  if (f->d_xchg) (void)hipFree(f->d_xchg);
-  if (f->d_cxchg) (void)hipFree(f->d_cxchg);
-  if (f->d_acc) (void)hipFree(f->d_acc);
+  for (void* p : {f->d_rjobs, f->d_wjobs, f->d_lsrefs, f->d_lujobs, f->d_rblockjob, f->d_ajobs, f->d_asegs, f->d_rjobs2, f->d_rblockjob2,
+                  f->d_w1tab, f->d_ntab[0], f->d_ntab[1], f->d_ntab[2], f->d_w2tab, f->d_redtab, f->d_xchg, f->d_cxchg, f->d_acc})
+    if (p) (void)hipFree(p);
   if (f->pass_ev) (void)hipEventDestroy(f->pass_ev);
   if (f->h_tmo) (void)hipHostFree(f->h_tmo);
   for (auto e : f->events) (void)hipEventDestroy(e);
@@ -916,11 +956,10 @@ extern "C" int ipoke_flow_piece_ranges(const ipoke_flow* f, int npieces, int64_t
   const std::vector<std::pair<int, int>> pieces = backward_pieces(f, npieces);
   int n = 0;
   for (size_t i = 0; i < pieces.size(); ++i) {
-    int64_t p0[3], p1[3];
-    piece_param_ranges(f, pieces[i].first, pieces[i].second, p0, p1);
+    const PieceRanges r = piece_ranges(f, pieces[i].first, pieces[i].second);
     for (int kind = 0; kind < 3; ++kind) {
-      if (p0[kind] < 0 || p1[kind] <= p0[kind]) continue;
-      if (n < max_ranges) { ranges[3 * n] = (int64_t)i; ranges[3 * n + 1] = p0[kind]; ranges[3 * n + 2] = p1[kind]; }
+      if (!r.has_params(kind)) continue;
+      if (n < max_ranges) { ranges[3 * n] = (int64_t)i; ranges[3 * n + 1] = r.p0[kind]; ranges[3 * n + 2] = r.p1[kind]; }
       ++n;
     }
   }
@@ -1263,56 +1302,102 @@ extern "C" int ipoke_flow_handoff_timeouts(ipoke_flow* f, uint32_t* out) {
   return IPOKE_OK;
 }
 
+// What every pass starts with: the handle / batch checks, the device tables and the execution context (mode as make_plan's)
+static int make_ctx(ipoke_flow* f, int B, const float* params, const int32_t* perm, const void* shadow, void* workspace, hipStream_t stream,
+                    int mode, Ctx* c) {
+  int rc = common_checks(f, B); if (rc) return rc;
+  rc = ensure_device(f); if (rc) return rc;
+  *c = Ctx{f, B, (int64_t)B * f->P, f->cfg.z_channels, f->cfg.dtype, stream, params, perm,
+           reinterpret_cast<const unsigned char*>(shadow), reinterpret_cast<unsigned char*>(workspace), make_plan(*f, B, mode)};
+  return IPOKE_OK;
+}
+
+// whole MaCowUnit (ops i .. i+5) in one launch, or two adjacent ones (nops = 12: ops i .. i+11), from state x to state y
+static int forward_unit(const Ctx& c, int i, int nops, bool save, const float* x, float* y) {
+  ipoke_flow* f = c.f;
+  const int nl = nops / 6 * 4;
+  ipoke_mcf_desc d4[8];
+  for (int k = 0; k < nl; ++k) {
+    const Op& mk = f->ops[i + kUnitMcf[k]];
+    mcf_desc(c, mk, d4[k]);
+    d4[k].x = k == 0 ? x : nullptr;
+    d4[k].y = k == nl - 1 ? y : (save ? c.state(i + kUnitMcfOut[k]) : nullptr);
+    d4[k].logdet_slot = c.slot(mk.slot);
+    d4[k].rows_per_block = 16;               // slot width 4, as the per-layer launches
+    mcf_post(c, mk, d4[k]);
+    if (save) mcf_saved(c, mk, d4[k]);
+  }
+  if (unit_feeds(f, i + nops)) {
+    const Op& nx = f->ops[i + nops];
+    ipoke_mcf_desc& dl = d4[nl - 1];
+    dl.zc_out = c.at<void>(save ? nx.ws_g : c.plan.tmp_zc);
+    dl.zc_off = nx.z_off; dl.zc_stride = nx.z_stride; dl.zc_cin = nx.cin; dl.zc_ld = nx.Kc1;
+  }
+  if (f->unit_split > 1 && f->d_xchg) { d4[0].split = f->unit_split; d4[0].xchg = f->d_xchg; }
+  return nl == 8 ? ipoke_macow_unit2_fwd(d4, c.dtype, c.stream()) : ipoke_macow_unit_fwd(d4, c.dtype, c.stream());
+}
+
+// coupling op i from state `in` to state `out`; with_an: the stand-alone ActNorm (+ Shuffle) behind it, op i + 1, in the same launch
+// (never reached by the data-dependent initialisation, which skips the couplings)
+static int forward_nice(const Ctx& c, int i, bool save, bool with_an, const float* in, float* out) {
+  ipoke_flow* f = c.f;
+  const Op& op = f->ops[i];
+  void* h1 = c.at<void>(save ? op.ws_a : c.plan.tmp_h1);
+  void* h2 = c.at<void>(save ? op.ws_b : c.plan.tmp_h2);
+  void* zc = c.at<void>(save ? op.ws_g : c.plan.tmp_zc);
+  const bool have_zc = (i > 0 && nice_feeds(f->ops[i - 1], op)) || unit_feeds(f, i);
+  const NiceRoute r = nice_route(c, op);
+  int rc = nice_net(c, op, in, h1, h2, zc, have_zc, !r.one_launch, r.conv2); if (rc) return rc;
+  ipoke_affine_desc a; nice_affine_desc(c, op, a);
+  int ext_ld = 0;
+  void* ext = nice_ext(c, i, 1, save, &ext_ld);
+  float* scale_out = save ? c.at<float>(op.ws_c) : nullptr;
+  float* an_in = save ? c.state(i + 1) : nullptr;      // with_an: the ActNorm's saved input
+  if (r.one_launch) {
+    ipoke_coupling_epi e; std::memset(&e, 0, sizeof(e));
+    e.mode = with_an ? 1 : 0; e.in = in; e.scale_out = scale_out;
+    e.logdet_slot = c.slot(op.slot); e.slot_stride = 4; e.xchg = f->d_cxchg;
+    if (with_an) {
+      const Op& an = f->ops[op.an_next];
+      e.out = an_in; e.out2 = out;
+      e.an_c0 = an.c0; e.an_C = an.Cn; e.an_log_scale = c.an_ls(an); e.an_bias = c.an_bias(an); e.an_idx = c.an_idx_fwd(an);
+    } else {
+      e.out = out; e.ext = ext; e.ext_ld = ext_ld;
+    }
+    return nice_coupling(c, op, r.pair, r.split, h1, h2, true, a, e);      // (h2 is stored: the backward pass reads it)
+  }
+  if (with_an) {
+    const Op& an = f->ops[op.an_next];
+    return ipoke_affine_actnorm_fwd(&a, in, an_in, out, scale_out, c.slot(op.slot), 4, c.B, an.c0, an.Cn, c.an_ls(an), c.an_bias(an),
+                                    c.an_idx_fwd(an), c.stream());
+  }
+  return ipoke_affine_fwd_ext(&a, in, out, scale_out, c.slot(op.slot), 4, c.B, ext, ext_ld, c.dtype, c.stream());
+}
+
 static int run_forward(ipoke_flow* f, const float* params, const int32_t* perm, const void* shadow, const float* x_nchw,
                        const float* cond_nchw, int B, float* out_nchw, float* logdet, void* workspace, int save, int init,
                        float* params_mut, hipStream_t stream_h) {
-  void* stream = reinterpret_cast<void*>(stream_h);
-  int rc = common_checks(f, B); if (rc) return rc;
-  rc = ensure_device(f); if (rc) return rc;
+  Ctx c;
+  int rc = make_ctx(f, B, params, perm, shadow, workspace, stream_h, save ? 1 : 0, &c); if (rc) return rc;
   IPK_REQUIRE(params && perm && x_nchw && out_nchw && workspace, "null argument");
   IPK_REQUIRE(init || (shadow && cond_nchw), "shadow weights and cond are required");
-  Ctx c{f, B, (int64_t)B * f->P, f->cfg.z_channels, f->cfg.dtype, reinterpret_cast<hipStream_t>(stream),
-        params, perm, reinterpret_cast<const unsigned char*>(shadow), reinterpret_cast<unsigned char*>(workspace),
-        make_plan(*f, B, save ? 1 : 0)};
   const int z = f->cfg.z_channels;
-  rc = ipoke_nchw_to_state(x_nchw, c.state(0), B, z, f->P, c.ld, stream); if (rc) return rc;
+  rc = ipoke_nchw_to_state(x_nchw, c.state(0), B, z, f->P, c.ld, c.stream()); if (rc) return rc;
   if (!init) {
-    rc = ipoke_cond_prepare(cond_nchw, c.cond(), B, f->cfg.cond_channels, f->P, IPOKE_ACT_ELU, c.dtype, stream);
+    rc = ipoke_cond_prepare(cond_nchw, c.cond(), B, f->cfg.cond_channels, f->P, IPOKE_ACT_ELU, c.dtype, c.stream());
     if (rc) return rc;
   }
   IPK_HIP(hipMemsetAsync(c.at<void>(c.plan.slots), 0, (size_t)f->nslots * B * 4 * sizeof(float), c.s));
   rc = lu_prepare_all(c); if (rc) return rc;
   constexpr int kMcfRows = 16;          // per-layer MCF forward slice height: 4 slices per sample -> slot width 4
   int cur = 0;
-  for (size_t i = 0; i < f->ops.size(); ++i) {
+  for (int i = 0; i < (int)f->ops.size(); ++i) {
     const Op& op = f->ops[i];
     if (init && op.type != OP_ACTNORM && op.type != OP_LU) continue;   // zero-initialised couplings are the identity (macow_utils.py:231-250)
     if (!init && op.unit_head) {                   // whole MaCowUnit (ops i .. i+5) in one launch, or two adjacent ones (ops i .. i+11)
-      const int nl = unit2_at(f, (int)i, IPOKE_UNIT2_FWD) ? 8 : 4;
-      const int nops = nl / 4 * 6;
-      const int nxt = save ? (int)i + nops : (cur ^ 1);
-      static const int lidx[8] = {0, 1, 3, 4, 6, 7, 9, 10};     // the masked convs among the six ops of a unit
-      static const int oidx[8] = {1, 3, 4, 6, 7, 9, 10, 12};    // state index (relative to i) each of them writes when states are saved
-      ipoke_mcf_desc d4[8];
-      for (int k = 0; k < nl; ++k) {
-        const Op& mk = f->ops[i + lidx[k]];
-        mcf_desc(c, mk, d4[k]);
-        d4[k].x = k == 0 ? c.state(cur) : nullptr;
-        d4[k].y = k == nl - 1 ? c.state(nxt) : (save ? c.state((int)i + oidx[k]) : nullptr);
-        d4[k].logdet_slot = c.slot(mk.slot);
-        d4[k].rows_per_block = 16;               // slot width 4, as the per-layer launches
-        if (mk.fuse_act >= 0) { d4[k].post_log_scale = params + f->ops[mk.fuse_act].p_ls; d4[k].post_bias = params + f->ops[mk.fuse_act].p_bias; }
-        if (save) { d4[k].a2_save = c.at<void>(mk.ws_a); d4[k].scale_save = c.at<float>(mk.ws_b); }
-      }
-      if (unit_feeds(f, i + nops)) {
-        const Op& nx = f->ops[i + nops];
-        ipoke_mcf_desc& dl = d4[nl - 1];
-        dl.zc_out = c.at<void>(save ? nx.ws_g : c.plan.tmp_zc);
-        dl.zc_off = nx.z_off; dl.zc_stride = nx.z_stride; dl.zc_cin = nx.cin; dl.zc_ld = nx.Kc1;
-      }
-      if (f->unit_split > 1 && f->d_xchg) { d4[0].split = f->unit_split; d4[0].xchg = f->d_xchg; }
-      rc = nl == 8 ? ipoke_macow_unit2_fwd(d4, c.dtype, c.stream()) : ipoke_macow_unit_fwd(d4, c.dtype, c.stream());
-      if (rc) return rc;
+      const int nops = unit2_at(f, i, IPOKE_UNIT2_FWD) ? 12 : 6;
+      const int nxt = save ? i + nops : (cur ^ 1);
+      rc = forward_unit(c, i, nops, save != 0, c.state(cur), c.state(nxt)); if (rc) return rc;
       cur = nxt;
       i += nops - 1;
       continue;
@@ -1320,75 +1405,36 @@ static int run_forward(ipoke_flow* f, const float* params, const int32_t* perm, 
     if (!init && op.fused) continue;               // done by the preceding MCF launch, which wrote this op's output state
     const bool fuse = !init && op.type == OP_MCF && op.fuse_act >= 0;
     const bool with_an = !init && op.type == OP_NICE && op.an_next >= 0;       // the ActNorm behind this coupling runs in its affine launch
-    const int nxt = save ? (int)i + (fuse || with_an ? 2 : 1) : (cur ^ 1);
+    const int nxt = save ? i + (fuse || with_an ? 2 : 1) : (cur ^ 1);
     const float* in = c.state(cur); float* out = c.state(nxt);
     if (op.type == OP_LU) {
       rc = ipoke_lu_apply(in, out, c.M, c.ld, op.C, lu_mat(c, op, 0), 0, c.stream());
     } else if (op.type == OP_ACTNORM) {
-      const float* ls = op.p_ls >= 0 ? params + op.p_ls : nullptr;
-      const float* bs = op.p_bias >= 0 ? params + op.p_bias : nullptr;
-      const int32_t* idx = op.idx_fwd >= 0 ? perm + op.idx_fwd : nullptr;
       if (init && op.p_ls >= 0) {
         rc = ipoke_actnorm_init(in, (int)c.M, c.ld, op.c0, op.Cn, params_mut + op.p_ls, params_mut + op.p_bias, c.stream());
         if (rc) return rc;
       }
-      rc = ipoke_actnorm_fwd(in, out, (int)c.M, c.ld, op.c0, op.Cn, ls, bs, idx, c.stream());
+      rc = ipoke_actnorm_fwd(in, out, (int)c.M, c.ld, op.c0, op.Cn, c.an_ls(op), c.an_bias(op), c.an_idx_fwd(op), c.stream());
     } else if (op.type == OP_MCF) {
       ipoke_mcf_desc d; mcf_desc(c, op, d);
       d.x = in; d.y = out;
       d.logdet_slot = c.slot(op.slot);
       d.rows_per_block = kMcfRows;
-      if (fuse) { d.post_log_scale = params + f->ops[op.fuse_act].p_ls; d.post_bias = params + f->ops[op.fuse_act].p_bias; }
-      if (save) { d.a2_save = c.at<void>(op.ws_a); d.scale_save = c.at<float>(op.ws_b); }
+      mcf_post(c, op, d);
+      if (save) mcf_saved(c, op, d);
       rc = ipoke_mcf_fwd(&d, c.dtype, c.stream());
     } else {
-      void* h1 = c.at<void>(save ? op.ws_a : c.plan.tmp_h1);
-      void* h2 = c.at<void>(save ? op.ws_b : c.plan.tmp_h2);
-      void* zc = c.at<void>(save ? op.ws_g : c.plan.tmp_zc);
-      const bool have_zc = (i > 0 && nice_feeds(f->ops[i - 1], op)) || (!init && unit_feeds(f, i));
-      const bool one_launch = !init && nice_fused(c, op);
-      const bool pair = one_launch && nice_pair(c, op), split = pair && f->split_pair_coupling;
-      rc = nice_net(c, op, in, h1, h2, zc, have_zc, !one_launch, pair ? (split ? 2 : 0) : 1); if (rc) return rc;
-      ipoke_affine_desc a; nice_affine_desc(c, op, a);
-      void* ext = nullptr; int ext_ld = 0;
-      if (i + 1 < f->ops.size() && nice_feeds(op, f->ops[i + 1])) {
-        const Op& nx = f->ops[i + 1];
-        ext = c.at<void>(save ? nx.ws_g : c.plan.tmp_zc);
-        ext_ld = nx.Kc1;
-      }
-      if (one_launch) {
-        ipoke_coupling_epi e; std::memset(&e, 0, sizeof(e));
-        e.mode = with_an ? 1 : 0; e.in = in; e.scale_out = save ? c.at<float>(op.ws_c) : nullptr;
-        e.logdet_slot = c.slot(op.slot); e.slot_stride = 4; e.xchg = f->d_cxchg;
-        if (with_an) {
-          const Op& an = f->ops[op.an_next];
-          e.out = save ? c.state((int)i + 1) : nullptr; e.out2 = out;
-          e.an_c0 = an.c0; e.an_C = an.Cn; e.an_log_scale = an.p_ls >= 0 ? params + an.p_ls : nullptr;
-          e.an_bias = an.p_bias >= 0 ? params + an.p_bias : nullptr; e.an_idx = an.idx_fwd >= 0 ? perm + an.idx_fwd : nullptr;
-        } else {
-          e.out = out; e.ext = ext; e.ext_ld = ext_ld;
-        }
-        rc = nice_coupling(c, op, pair, split, h1, h2, true, a, e);      // (h2 is stored: the backward pass reads it)
-      } else if (with_an) {
-        const Op& an = f->ops[op.an_next];
-        rc = ipoke_affine_actnorm_fwd(&a, in, save ? c.state((int)i + 1) : nullptr, out, save ? c.at<float>(op.ws_c) : nullptr,
-                                      c.slot(op.slot), 4, c.B, an.c0, an.Cn, an.p_ls >= 0 ? params + an.p_ls : nullptr,
-                                      an.p_bias >= 0 ? params + an.p_bias : nullptr, an.idx_fwd >= 0 ? perm + an.idx_fwd : nullptr,
-                                      c.stream());
-      } else {
-        rc = ipoke_affine_fwd_ext(&a, in, out, save ? c.at<float>(op.ws_c) : nullptr, c.slot(op.slot), 4, c.B, ext, ext_ld, c.dtype,
-                                  c.stream());
-      }
+      rc = forward_nice(c, i, save != 0, with_an, in, out);
     }
     if (rc) return rc;
     cur = nxt;
     if (with_an) ++i;                              // the ActNorm op has been executed
   }
-  rc = ipoke_state_to_nchw(c.state(cur), out_nchw, B, z, f->P, c.ld, stream); if (rc) return rc;
+  rc = ipoke_state_to_nchw(c.state(cur), out_nchw, B, z, f->P, c.ld, c.stream()); if (rc) return rc;
   if (logdet) {
-    rc = ipoke_actnorm_logdet(params, f->d_lsrefs, (int)f->lsrefs.size(), f->P, c.at<float>(c.plan.ls_const), stream);
+    rc = ipoke_actnorm_logdet(params, f->d_lsrefs, (int)f->lsrefs.size(), f->P, c.at<float>(c.plan.ls_const), c.stream());
     if (rc) return rc;
-    rc = ipoke_logdet_finalize(c.at<float>(c.plan.slots), init ? 0 : f->nslots, B, 4, 0.f, c.at<float>(c.plan.ls_const), logdet, stream);
+    rc = ipoke_logdet_finalize(c.at<float>(c.plan.slots), init ? 0 : f->nslots, B, 4, 0.f, c.at<float>(c.plan.ls_const), logdet, c.stream());
     if (rc) return rc;
   }
   return IPOKE_OK;
@@ -1422,56 +1468,75 @@ extern "C" int ipoke_flow_init_forward(ipoke_flow* f, float* params, const int32
   return run_forward(f, params, perm, nullptr, x_nchw, nullptr, B, out_nchw, logdet, workspace, 0, 1, params, reinterpret_cast<hipStream_t>(stream));
 }
 
+// a stand-alone ActNorm (+ Shuffle), op k, whose inverse is directly followed by the inverse of a coupling (ops[k - 1] in this direction)
+// (one launch less per coupling pair than ipoke_actnorm_inv + ipoke_extract_cols; nothing measurable: c5 44.70 vs 44.70, 44.42 vs 44.37 ms)
+static bool actnorm_feeds(const Ctx& c, int k) {
+  const ipoke_flow* f = c.f;
+  if (k < 1 || k >= (int)f->ops.size()) return false;
+  const Op& an = f->ops[k]; const Op& nx = f->ops[k - 1];
+  return an.type == OP_ACTNORM && an.unit_of < 0 && nx.type == OP_NICE && nx.Kc1 - nx.cin <= c.ld && nx.Kc1 <= 64;
+}
+
+// whole MaCowUnit (ops h .. h+5) inverted by one launch, or two adjacent ones (nl = 8: h .. h+11), from state x to state y
+static int reverse_unit(const Ctx& c, int h, int nl, const float* x, float* y) {
+  ipoke_mcf_desc d4[8];
+  for (int k = 0; k < nl; ++k) {
+    const Op& mk = c.f->ops[h + kUnitMcf[k]];
+    mcf_desc(c, mk, d4[k]);
+    mcf_post(c, mk, d4[k]);
+  }
+  d4[nl - 1].x = x; d4[0].y = y;
+  d4[0].x = d4[nl - 1].x; d4[nl - 1].y = d4[0].y;          // (the shared validator wants input / output on the first / last layer)
+  return nl == 8 ? ipoke_macow_unit2_inv(d4, c.dtype, c.stream()) : ipoke_macow_unit_inv(d4, c.dtype, c.stream());
+}
+
+// inverse of coupling op i from state `in` to state `out`
+static int reverse_nice(const Ctx& c, int i, const float* in, float* out) {
+  ipoke_flow* f = c.f;
+  const Op& op = f->ops[i];
+  // the conditioning channels are untouched by the coupling, so the net sees the same input as in forward
+  const bool have_zc = i + 1 < (int)f->ops.size() && (nice_feeds(f->ops[i + 1], op) || actnorm_feeds(c, i + 1));     // written by the layer inverted just before this one
+  const NiceRoute r = nice_route(c, op);
+  void* h1 = c.at<void>(c.plan.tmp_h1);
+  void* h2 = c.at<void>(c.plan.tmp_h2);
+  int rc = nice_net(c, op, in, h1, h2, c.at<void>(c.plan.tmp_zc), have_zc, !r.one_launch, r.conv2);
+  if (rc) return rc;
+  ipoke_affine_desc a; nice_affine_desc(c, op, a);
+  int ext_ld = 0;
+  void* ext = nice_ext(c, i, -1, false, &ext_ld);
+  if (r.one_launch) {
+    ipoke_coupling_epi e; std::memset(&e, 0, sizeof(e));
+    e.mode = 2; e.in = in; e.out = out; e.ext = ext; e.ext_ld = ext_ld; e.xchg = f->d_cxchg;
+    return nice_coupling(c, op, r.pair, r.split, h1, h2, false, a, e);     // (nothing reads h2 behind this launch: not stored)
+  }
+  return ipoke_affine_inv_ext(&a, in, out, c.B, ext, ext_ld, c.dtype, c.stream());
+}
+
 static int run_reverse(ipoke_flow* f, const float* params, const int32_t* perm, const void* shadow,
                        const float* z_nchw, const float* cond_nchw, int B, float* x_nchw, void* workspace, hipStream_t stream_h) {
-  void* stream = reinterpret_cast<void*>(stream_h);
-  int rc = common_checks(f, B); if (rc) return rc;
-  rc = ensure_device(f); if (rc) return rc;
+  Ctx c;
+  int rc = make_ctx(f, B, params, perm, shadow, workspace, stream_h, 0, &c); if (rc) return rc;
   IPK_REQUIRE(params && perm && shadow && z_nchw && cond_nchw && x_nchw && workspace, "null argument");
-  Ctx c{f, B, (int64_t)B * f->P, f->cfg.z_channels, f->cfg.dtype, reinterpret_cast<hipStream_t>(stream),
-        params, perm, reinterpret_cast<const unsigned char*>(shadow), reinterpret_cast<unsigned char*>(workspace),
-        make_plan(*f, B, 0)};
   const int z = f->cfg.z_channels;
-  rc = ipoke_nchw_to_state(z_nchw, c.state(0), B, z, f->P, c.ld, stream); if (rc) return rc;
-  rc = ipoke_cond_prepare(cond_nchw, c.cond(), B, f->cfg.cond_channels, f->P, IPOKE_ACT_ELU, c.dtype, stream);
+  rc = ipoke_nchw_to_state(z_nchw, c.state(0), B, z, f->P, c.ld, c.stream()); if (rc) return rc;
+  rc = ipoke_cond_prepare(cond_nchw, c.cond(), B, f->cfg.cond_channels, f->P, IPOKE_ACT_ELU, c.dtype, c.stream());
   if (rc) return rc;
   rc = lu_prepare_all(c); if (rc) return rc;
-  // a stand-alone ActNorm (+ Shuffle) whose inverse is directly followed by the inverse of a coupling (ops[k - 1] in this direction)
-  // (one launch less per coupling pair than ipoke_actnorm_inv + ipoke_extract_cols; nothing measurable: c5 44.70 vs 44.70, 44.42 vs 44.37 ms)
-  auto actnorm_feeds = [&](int k) {
-    if (k < 1 || k >= (int)f->ops.size()) return false;
-    const Op& an = f->ops[k]; const Op& nx = f->ops[k - 1];
-    return an.type == OP_ACTNORM && an.unit_of < 0 && nx.type == OP_NICE && nx.Kc1 - nx.cin <= c.ld && nx.Kc1 <= 64;
-  };
   int cur = 0;
   for (int i = (int)f->ops.size() - 1; i >= 0; --i) {
     const Op& op = f->ops[i];
+    const float* in = c.state(cur); float* out = c.state(cur ^ 1);
     if (op.unit_of >= 0 && i == op.unit_of + 5) {     // whole MaCowUnit (ops h .. h+5) inverted by one launch, or two adjacent ones (h .. h+11)
       const int nl = unit2_at(f, op.unit_of - 6, IPOKE_UNIT2_INV) ? 8 : 4;
       const int h = nl == 8 ? op.unit_of - 6 : op.unit_of;
-      static const int lidx[8] = {0, 1, 3, 4, 6, 7, 9, 10};
-      ipoke_mcf_desc d4[8];
-      for (int k = 0; k < nl; ++k) {
-        const Op& mk = f->ops[h + lidx[k]];
-        mcf_desc(c, mk, d4[k]);
-        if (mk.fuse_act >= 0) { d4[k].post_log_scale = params + f->ops[mk.fuse_act].p_ls; d4[k].post_bias = params + f->ops[mk.fuse_act].p_bias; }
-      }
-      d4[nl - 1].x = c.state(cur); d4[0].y = c.state(cur ^ 1);
-      d4[0].x = d4[nl - 1].x; d4[nl - 1].y = d4[0].y;          // (the shared validator wants input / output on the first / last layer)
-      rc = nl == 8 ? ipoke_macow_unit2_inv(d4, c.dtype, c.stream()) : ipoke_macow_unit_inv(d4, c.dtype, c.stream());
-      if (rc) return rc;
-      cur ^= 1;
-      i = h;
-      continue;
-    }
-    const float* in = c.state(cur); float* out = c.state(cur ^ 1);
-    if (op.type == OP_LU) {
+      rc = reverse_unit(c, h, nl, in, out);
+      i = h;                                          // the loop decrement moves on to op h - 1
+    } else if (op.type == OP_LU) {
       rc = ipoke_lu_apply(in, out, c.M, c.ld, op.C, lu_mat(c, op, 1), 0, c.stream());
     } else if (op.type == OP_ACTNORM) {
       // followed (in this direction) by a coupling: its conditioning operand is written here instead of by an extract_cols launch
-      const Op* nx = actnorm_feeds(i) ? &f->ops[i - 1] : nullptr;
-      rc = ipoke_actnorm_inv_ext(in, out, (int)c.M, c.ld, op.c0, op.Cn, op.p_ls >= 0 ? params + op.p_ls : nullptr,
-                                 op.p_bias >= 0 ? params + op.p_bias : nullptr, op.idx_bwd >= 0 ? perm + op.idx_bwd : nullptr,
+      const Op* nx = actnorm_feeds(c, i) ? &f->ops[i - 1] : nullptr;
+      rc = ipoke_actnorm_inv_ext(in, out, (int)c.M, c.ld, op.c0, op.Cn, c.an_ls(op), c.an_bias(op), c.an_idx_bwd(op),
                                  nx ? c.at<void>(c.plan.tmp_zc) : nullptr, nx ? nx->Kc1 : 0, nx ? nx->z_off : 0,
                                  nx ? nx->z_stride : 1, nx ? nx->cin : 0, c.dtype, c.stream());
     } else if (op.type == OP_MCF) {
@@ -1479,30 +1544,12 @@ static int run_reverse(ipoke_flow* f, const float* params, const int32_t* perm, 
       d.x = in; d.y = out;
       rc = ipoke_mcf_inv(&d, c.dtype, c.stream());
     } else {
-      // the conditioning channels are untouched by the coupling, so the net sees the same input as in forward
-      const bool have_zc = i + 1 < (int)f->ops.size() && (nice_feeds(f->ops[i + 1], op) || actnorm_feeds(i + 1));     // written by the layer inverted just before this one
-      const bool one_launch = nice_fused(c, op);
-      const bool pair = one_launch && nice_pair(c, op), split = pair && f->split_pair_coupling;
-      void* h1 = c.at<void>(c.plan.tmp_h1);
-      void* h2 = c.at<void>(c.plan.tmp_h2);
-      rc = nice_net(c, op, in, h1, h2, c.at<void>(c.plan.tmp_zc), have_zc, !one_launch, pair ? (split ? 2 : 0) : 1);
-      if (rc) return rc;
-      ipoke_affine_desc a; nice_affine_desc(c, op, a);
-      const bool feed = i > 0 && nice_feeds(op, f->ops[i - 1]);
-      void* ext = feed ? c.at<void>(c.plan.tmp_zc) : nullptr;
-      const int ext_ld = feed ? f->ops[i - 1].Kc1 : 0;
-      if (one_launch) {
-        ipoke_coupling_epi e; std::memset(&e, 0, sizeof(e));
-        e.mode = 2; e.in = in; e.out = out; e.ext = ext; e.ext_ld = ext_ld; e.xchg = f->d_cxchg;
-        rc = nice_coupling(c, op, pair, split, h1, h2, false, a, e);     // (nothing reads h2 behind this launch: not stored)
-      } else {
-        rc = ipoke_affine_inv_ext(&a, in, out, c.B, ext, ext_ld, c.dtype, c.stream());
-      }
+      rc = reverse_nice(c, i, in, out);
     }
     if (rc) return rc;
     cur ^= 1;
   }
-  return ipoke_state_to_nchw(c.state(cur), x_nchw, B, z, f->P, c.ld, stream);
+  return ipoke_state_to_nchw(c.state(cur), x_nchw, B, z, f->P, c.ld, c.stream());
 }
 
 extern "C" int ipoke_flow_reverse(ipoke_flow* f, const float* params, const int32_t* perm, const void* shadow,
@@ -1519,139 +1566,125 @@ extern "C" int ipoke_flow_reverse(ipoke_flow* f, const float* params, const int3
 }
 
 // ------------------------------------------------------------------------------------------------
-static int run_backward(ipoke_flow* f, const float* params, const int32_t* perm, const void* shadow,
-                        const float* d_out_nchw, const float* d_logdet, int B, float* grads, float* dx_nchw,
-                        void* workspace, hipStream_t stream_h, int npieces = 1, hipStream_t ready_stream = nullptr,
-                        ipoke_grad_ready_fn ready = nullptr, void* user = nullptr) {
-  void* stream = reinterpret_cast<void*>(stream_h);
-  int rc = common_checks(f, B); if (rc) return rc;
-  rc = ensure_device(f); if (rc) return rc;
-  IPK_REQUIRE(params && perm && shadow && d_out_nchw && d_logdet && grads && workspace, "null argument");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  Ctx c{f, B, (int64_t)B * f->P, f->cfg.z_channels, f->cfg.dtype, s, params, perm,
-        reinterpret_cast<const unsigned char*>(shadow), reinterpret_cast<unsigned char*>(workspace), make_plan(*f, B, 1)};
-  const int z = f->cfg.z_channels, hid = f->cfg.hidden;
-  rc = ipoke_nchw_to_state(d_out_nchw, c.at<float>(c.plan.g0), B, z, f->P, c.ld, stream); if (rc) return rc;
-  IPK_HIP(hipMemcpyAsync(c.dld(), d_logdet, B * sizeof(float), hipMemcpyDeviceToDevice, s));
-  // Weight gradients run on the side stream, after the chain has produced the operands of that layer (on the caller's stream
-  // instead: 116 vs 98 ms when measured; a one-wave spin at the head of every side-stream batch, so that the chain's next kernel takes
-  // its CUs first: no gain).
-  void* wstream = reinterpret_cast<void*>(f->side);
-  auto wgrads_wait_chain = [&]() -> int { return stream_wait(f, f->side, s); };
-  // Every parameter gradient is written exactly once per backward (no accumulation, no memset).  The weight gradients
-  // of the MCF layers are tiny GEMMs (a handful of output tiles): they are deferred and issued as batched launches,
-  // one per run of same-shape layers (= one level), using the per-layer saved operands that stay in the workspace.
-  rc = ensure_tables(f, B, c.plan); if (rc) return rc;
-  int pend_lo = -1, pend_hi = -1, pend_op = -1;      // pending MCF index range [lo, hi] and a representative op
-  auto flush_mcf = [&]() -> int {
-    if (pend_lo < 0) return IPOKE_OK;
-    const Op& op = f->ops[pend_op];
-    const int nb = pend_hi - pend_lo + 1;
-    int r = wgrads_wait_chain(); if (r) return r;
-    ipoke_wgrad_desc w; std::memset(&w, 0, sizeof(w));
-    w.NB = B; w.Di = 1; w.Hi = 8; w.Wi = 8; w.Do = 1; w.Ho = 8; w.Wo = 8; w.kd = w.kh = w.kw = 1; w.sd = w.sh = w.sw = 1;
-    w.max_workgroups = 0;
-    const int K2 = op.H + f->cfg.cond_channels;
-    w.a_f32 = 0; w.a_sn = 64L * op.K2p; w.a_sh = 8L * op.K2p; w.a_sw = op.K2p; w.a_sc = 1; w.Kc_real = K2; w.Kc = op.K2p;
-    w.ldy = op.K3p; w.Nout = 2 * op.C; w.w_sn = K2; w.w_sc = 1; w.w_st = 0;
-    r = ipoke_conv_wgrad_batched(&w, reinterpret_cast<const unsigned char*>(f->d_w2tab) + (size_t)pend_lo * ipoke_wgrad_batch_entry_size(),
-                                 nb, c.ws, c.ws, grads, c.dtype, wstream);
-    if (r) return r;
-    std::memset(&w, 0, sizeof(w));
-    w.NB = B; w.Di = 1; w.Hi = 8; w.Wi = 8; w.Do = 1; w.Ho = 8; w.Wo = 8; w.kd = 1; w.kh = 2; w.kw = 3; w.sd = w.sh = w.sw = 1;
-    w.max_workgroups = 0;
-    if (f->mcf_xop) {   // dtype copy [M][Cp] of every layer input, zero padded: the LDS-DMA weight-gradient GEMM
-      w.a_f32 = 0; w.a_sn = 64L * op.Cp; w.a_sh = 8L * op.Cp; w.a_sw = op.Cp; w.a_sc = 1; w.Kc_real = op.Cp; w.Kc = op.Cp; w.Kc_store = op.C;
-    } else {
-      w.a_f32 = 1; w.a_sn = 64L * c.ld; w.a_sh = 8L * c.ld; w.a_sw = c.ld; w.a_sc = 1; w.Kc_real = op.C; w.Kc = op.Cp;
-    }
-    w.ldy = op.Hq; w.Nout = op.H; w.w_sn = (int64_t)op.C * 6; w.w_sc = 6; w.w_st = 1;
-    r = ipoke_conv_wgrad_batched(&w, reinterpret_cast<const unsigned char*>(f->d_w1tab) + (size_t)pend_lo * ipoke_wgrad_batch_entry_size(),
-                                 nb, c.ws, c.ws, grads, c.dtype, wstream);
-    pend_lo = pend_hi = pend_op = -1;
-    return r;
-  };
-  rc = stream_wait(f, f->side, s); if (rc) return rc;      // the side stream joins after everything already queued on the main stream
+namespace {
+
+// One backward pass over the layer program: the chain of data gradients on the caller's stream (c.s), the weight gradients on the side
+// stream, and -- as soon as the lowest op of a piece has been queued -- the piece's reductions, optimizer and `ready` calls on the ready
+// stream.  run_backward drives it op by op, last op first.
+struct BackwardPass {
+  const Ctx& c;
+  ipoke_flow* const f;
+  float* const grads;
+  const hipStream_t rs;                                  // ready stream (the chain's when the caller names none)
+  const ipoke_grad_ready_fn ready; void* const user;
   // pieces: groups of consecutive units (steps / priors), last unit first, of roughly equal parameter counts
-  hipStream_t rs = ready_stream ? ready_stream : s;
-  const std::vector<std::pair<int, int>> pieces = backward_pieces(f, npieces);            // (lowest unit, highest unit)
-  // IPOKE_WGRAD_ADAM=1 (opt-in; =2: the gradient written as well): Adam-amsgrad of conv2 (plain 1x1, 73 % of the parameters) in the
-  // epilogue of its weight-gradient GEMM (ipoke_wgrad_desc.adam) instead of adam_cast over the written gradient -- single-process
-  // training with the engine-issued optimizer only (a data-parallel run must exchange the gradient first).  Bit-identical
-  // parameters and moments (tests/test_full_gpu.py), 8 of 42 bytes per parameter less -- and MEASURED SLOWER on c2 (round 6, one call):
-  // 53.2 / 53.2 ms against 49.9 / 49.8.  The launch takes 155 us instead of 53 (the same 2.8 TB/s the stand-alone kernel streams at
-  // beside the chain, but on 512 workgroups that hold every CU instead of a 160-workgroup grid), the weight-gradient queue grows from
-  // 11.0 to 15.0 ms per half step and the chain's kernels from 22.2 to 24.5 ms; the saved gradient round trip was served by the
-  // memory-side cache anyway.  Off by default.  A caller option, read here only;
-  // tests/test_full_gpu.py::test_adam_in_the_conv2_weight_gradient_epilogue_trains_bit_identically compares it against the default.
-  const char* wgrad_adam_env = getenv("IPOKE_WGRAD_ADAM");
-  const int wgrad_adam_mode = wgrad_adam_env ? atoi(wgrad_adam_env) : 0;
-  const bool wgrad_adam = wgrad_adam_mode != 0 && f->nadam.on && f->c2_straight && c.dtype == IPOKE_BF16 && hid % 128 == 0 &&
-                          (int)f->ajobs.size() == f->n_nice && !f->cfg.condition_nice;
-  std::function<int()> flush_nice_fn = []() { return (int)IPOKE_OK; };
-  auto native_adam_range = [&](int64_t b0, int64_t b1, int max_blocks) -> int {
-    const ipoke_flow::NativeAdam& A = f->nadam;
-    float* pm = const_cast<float*>(params);
-    void* rstream = reinterpret_cast<void*>(rs);
-    if (f->c2_straight)      // conv2 tensors: update + their one operand in the same linear pass; the rest: update, then relayout
-      return adam_range(f, pm, grads, A.m, A.v, A.vmax, const_cast<void*>(shadow), b0, b1, A.lr, A.beta1, A.beta2, A.eps, A.wd, A.step,
-                        A.grad_scale, max_blocks, rstream, wgrad_adam);
-    int r = ipoke_adam_amsgrad_step_grid(pm + b0, grads + b0, A.m + b0, A.v + b0, A.vmax + b0, b1 - b0, A.lr, A.beta1, A.beta2, A.eps, A.wd, A.step,
-                                         A.grad_scale, max_blocks, rstream);
-    if (r) return r;
-    return prepare_range(f, params, const_cast<void*>(shadow), b0, b1, false, rstream);
-  };
-  auto finish_piece = [&](int lvl_lo, int lvl_hi, int piece) -> int {
-    int r = flush_nice_fn(); if (r) return r;
-    r = flush_mcf(); if (r) return r;
-    r = stream_wait(f, rs, s); if (r) return r;                     // the chain up to here ...
-    r = stream_wait(f, rs, f->side); if (r) return r;               // ... and the weight gradients of this piece
-    void* rstream = reinterpret_cast<void*>(rs);
-    // bias / ActNorm parameter gradients: multi-tensor reduction over the per-sample partial sums of the piece's layers
-    const int r0 = f->red_first[f->units[lvl_lo].op_lo], r1 = f->red_first[f->units[lvl_hi].op_hi];
-    if (r1 > r0) {
-      r = ipoke_reduce_rows_multi(reinterpret_cast<const float*>(c.ws), grads,
-                                  reinterpret_cast<const unsigned char*>(f->d_redtab) + (size_t)r0 * ipoke_reduce_entry_size(), r1 - r0, B,
-                                  rstream);
-      if (r) return r;
-    }
-    // layers.* and priors.* are separate flat regions: the units of one kind inside the piece form one contiguous range each
-    // (use1x1: the LU convs' parameters form a third region, flow.shuffle_layers.*, without weight-norm rows)
-    int64_t p0[3] = {-1, -1, -1}, p1[3] = {-1, -1, -1};
-    int wj0[3] = {0, 0, 0}, wj1[3] = {0, 0, 0}, rw0[3] = {0, 0, 0}, rw1[3] = {0, 0, 0};
-    for (int u = lvl_lo; u <= lvl_hi; ++u) {
-      const auto& un = f->units[u];
-      const int k = un.kind;
-      if (p0[k] < 0) { p0[k] = un.p_lo; wj0[k] = un.wj_lo; rw0[k] = un.row_lo; }
-      p1[k] = un.p_hi; wj1[k] = un.wj_hi; rw1[k] = un.row_hi;
-      if (un.p2_lo >= 0) { if (p0[2] < 0) p0[2] = un.p2_lo; p1[2] = un.p2_hi; }
-    }
-    for (int kind = 0; kind < 2; ++kind) {
-      if (p0[kind] < 0) continue;
-      r = ipoke_wn_bwd_multi_range(params, grads, c.wn_inv(), f->d_wjobs, wj0[kind], wj1[kind] - wj0[kind], rw0[kind],
-                                   rw1[kind] - rw0[kind], rstream);
-      if (r) return r;
-    }
-    // (Moving the first k pieces' update + refresh behind the last piece's, into the step-boundary hole, was measured in round 6 and
-    // removed: 50.9 / 52.3 / 54.1 ms at k = 4 / 8 / 12 against 49.5 -- profiles/r06_ab_lines.txt.)
-    // (The optimizer of all but the last three pieces on a smaller grid: 61.0 / 55.1 / 54.2 ms at 64 / 96 / 128 blocks against 54.4-54.6.)
-    if (f->nadam.on) {
-      // single-GPU training: the update of the piece's ranges and the refresh of their shadows, natively, on the ready stream
-      for (int kind = 0; kind < 3; ++kind) {
-        if (p0[kind] < 0 || p1[kind] <= p0[kind]) continue;
-        r = native_adam_range(p0[kind], p1[kind], f->nadam.max_blocks); if (r) return r;
-      }
-    }
-    if (ready)
-      for (int kind = 0; kind < 3; ++kind)
-        if (p0[kind] >= 0 && p1[kind] > p0[kind]) ready(user, piece, p0[kind], p1[kind]);
-    return IPOKE_OK;
-  };
+  const std::vector<std::pair<int, int>> pieces;         // (lowest unit, highest unit)
+  size_t pk = 0;                                         // the piece the chain is in
+  int cur = 0;                                           // gradient ping-pong: g(cur) holds the gradient the next op reads
+  int pending_an = -1;                                   // ActNorm op whose backward is carried by the next (lower) coupling's launch
+  int pend_lo = -1, pend_hi = -1, pend_op = -1;          // pending MCF index range [lo, hi] and a representative op
   // NICE weight gradients are not started right behind their coupling: the couplings come in pairs whose data-gradient
   // GEMMs want the whole chip, and a weight-gradient kernel that is already running holds its CUs for 30 us.  They are
   // queued when the chain moves on to the (latency-bound, 20..80 workgroup) masked-conv layers.
   std::vector<int> pend_nice;
-  auto flush_nice = [&]() -> int {
+  int wgrad_adam_mode = 0; bool wgrad_adam = false;
+
+  BackwardPass(const Ctx& ctx, float* g, int npieces, hipStream_t ready_stream, ipoke_grad_ready_fn rdy, void* usr)
+      : c(ctx), f(ctx.f), grads(g), rs(ready_stream ? ready_stream : ctx.s), ready(rdy), user(usr), pieces(backward_pieces(ctx.f, npieces)) {
+    pend_nice.reserve((size_t)f->n_nice);
+    // IPOKE_WGRAD_ADAM=1 (opt-in; =2: the gradient written as well): Adam-amsgrad of conv2 (plain 1x1, 73 % of the parameters) in the
+    // epilogue of its weight-gradient GEMM (ipoke_wgrad_desc.adam) instead of adam_cast over the written gradient -- single-process
+    // training with the engine-issued optimizer only (a data-parallel run must exchange the gradient first).  Bit-identical
+    // parameters and moments (tests/test_full_gpu.py), 8 of 42 bytes per parameter less -- and MEASURED SLOWER on c2 (round 6, one call):
+    // 53.2 / 53.2 ms against 49.9 / 49.8.  The launch takes 155 us instead of 53 (the same 2.8 TB/s the stand-alone kernel streams at
+    // beside the chain, but on 512 workgroups that hold every CU instead of a 160-workgroup grid), the weight-gradient queue grows from
+    // 11.0 to 15.0 ms per half step and the chain's kernels from 22.2 to 24.5 ms; the saved gradient round trip was served by the
+    // memory-side cache anyway.  Off by default.  A caller option, read here only;
+    // tests/test_full_gpu.py::test_adam_in_the_conv2_weight_gradient_epilogue_trains_bit_identically compares it against the default.
+    const char* wgrad_adam_env = getenv("IPOKE_WGRAD_ADAM");
+    wgrad_adam_mode = wgrad_adam_env ? atoi(wgrad_adam_env) : 0;
+    wgrad_adam = wgrad_adam_mode != 0 && f->nadam.on && f->c2_straight && c.dtype == IPOKE_BF16 && f->cfg.hidden % 128 == 0 &&
+                 (int)f->ajobs.size() == f->n_nice && !f->cfg.condition_nice;
+  }
+
+  float* g(int k) const { return c.at<float>(k ? c.plan.g1 : c.plan.g0); }
+  void* wstream() const { return reinterpret_cast<void*>(f->side); }
+  bool lowest_of_piece(int i) const { return i == f->units[pieces[pk].first].op_lo; }
+  // Weight gradients run on the side stream, after the chain has produced the operands of that layer (on the caller's stream
+  // instead: 116 vs 98 ms when measured; a one-wave spin at the head of every side-stream batch, so that the chain's next kernel takes
+  // its CUs first: no gain).
+  int wgrads_wait_chain() { return stream_wait(f, f->side, c.s); }
+
+  // Every parameter gradient is written exactly once per backward (no accumulation, no memset).  The weight gradients
+  // of the MCF layers are tiny GEMMs (a handful of output tiles): they are deferred and issued as batched launches,
+  // one per run of same-shape layers (= one level), using the per-layer saved operands that stay in the workspace.
+  int flush_mcf() {
+    if (pend_lo < 0) return IPOKE_OK;
+    const Op& op = f->ops[pend_op];
+    const int nb = pend_hi - pend_lo + 1;
+    const size_t esz = (size_t)ipoke_wgrad_batch_entry_size();
+    int r = wgrads_wait_chain(); if (r) return r;
+    ipoke_wgrad_desc w;
+    const int K2 = op.H + f->cfg.cond_channels;
+    set_wgrad8(w, c.B, 1, 1, 0);
+    set_wa_dense(w, op.K2p, K2, op.K2p);
+    w.ldy = op.K3p; w.Nout = 2 * op.C; w.w_sn = K2; w.w_sc = 1; w.w_st = 0;
+    r = ipoke_conv_wgrad_batched(&w, tab_entry(f->d_w2tab, pend_lo, esz), nb, c.ws, c.ws, grads, c.dtype, wstream());
+    if (r) return r;
+    set_wgrad8(w, c.B, 2, 3, 0);
+    if (f->mcf_xop) {   // dtype copy [M][Cp] of every layer input, zero padded: the LDS-DMA weight-gradient GEMM
+      set_wa_dense(w, op.Cp, op.Cp, op.Cp); w.Kc_store = op.C;
+    } else {            // the fp32 state itself
+      set_wa_dense(w, c.ld, op.C, op.Cp); w.a_f32 = 1;
+    }
+    w.ldy = op.Hq; w.Nout = op.H; w.w_sn = (int64_t)op.C * 6; w.w_sc = 6; w.w_st = 1;
+    r = ipoke_conv_wgrad_batched(&w, tab_entry(f->d_w1tab, pend_lo, esz), nb, c.ws, c.ws, grads, c.dtype, wstream());
+    pend_lo = pend_hi = pend_op = -1;
+    return r;
+  }
+  // masked-conv op j has been differentiated: its weight gradients are deferred, batched per run of same-width layers
+  int defer_mcf_wgrads(int j) {
+    const Op& mk = f->ops[j];
+    if (pend_lo >= 0 && (f->ops[pend_op].C != mk.C || pend_hi - pend_lo + 1 >= 256)) { int r = flush_mcf(); if (r) return r; }
+    if (pend_lo < 0) { pend_hi = mk.mcf_idx; pend_op = j; }
+    pend_lo = mk.mcf_idx;
+    return IPOKE_OK;
+  }
+
+  // the three batched weight-gradient launches of nb couplings of op's widths, nice_idx lo .. lo + nb - 1
+  int nice_wgrads(const Op& op, int nb, int lo) {
+    const int hid = f->cfg.hidden;
+    const size_t esz = (size_t)ipoke_wgrad_batch_entry_size();
+    ipoke_wgrad_desc w;
+    // conv3 (effective weight; weight-norm backward runs at the end)
+    set_wgrad8(w, c.B, 3, 3, 1);
+    set_wa_dense(w, op.hidK, op.hidK, op.hidK);
+    w.ldy = op.Kc3; w.Nout = 2 * op.cout;
+    w.w_sn = (int64_t)op.hidK * 9; w.w_sc = 9; w.w_st = 1;
+    int rc = ipoke_conv_wgrad_batched(&w, tab_entry(f->d_ntab[2], lo, esz), nb, c.ws, c.ws, grads, c.dtype, wstream()); if (rc) return rc;
+    // conv2
+    set_wgrad8(w, c.B, 1, 1, 0);
+    set_wa_dense(w, hid, hid, hid);
+    w.ldy = hid; w.Nout = hid;
+    w.w_sn = hid; w.w_sc = 1; w.w_st = 0;
+    ipoke_wgrad_adam wa;
+    if (wgrad_adam) {
+      const ipoke_flow::NativeAdam& A = f->nadam;
+      wa.params = const_cast<float*>(c.params); wa.m = A.m; wa.v = A.v; wa.vmax = A.vmax;
+      wa.operand = const_cast<unsigned char*>(c.shadow + c.shadow_base());
+      wa.lr = A.lr; wa.beta1 = A.beta1; wa.beta2 = A.beta2; wa.eps = A.eps; wa.weight_decay = A.wd; wa.grad_scale = A.grad_scale; wa.step = A.step;
+      wa.keep_grad = wgrad_adam_mode == 2;
+      w.adam = &wa;
+    }
+    rc = ipoke_conv_wgrad_batched(&w, tab_entry(f->d_ntab[1], lo, esz), nb, c.ws, c.ws, grads, c.dtype, wstream()); if (rc) return rc;
+    // conv1 (input = conditioning channels of the saved state)
+    set_wgrad8(w, c.B, 3, 3, 1);
+    set_wa_dense(w, op.Kc1, op.Kc1, op.Kc1);
+    w.ldy = hid; w.Nout = hid;
+    w.w_sn = (int64_t)op.cin * 9; w.w_sc = 9; w.w_st = 1; w.Kc_store = op.cin;
+    return ipoke_conv_wgrad_batched(&w, tab_entry(f->d_ntab[0], lo, esz), nb, c.ws, c.ws, grads, c.dtype, wstream());
+  }
+  int flush_nice() {
     if (pend_nice.empty()) return IPOKE_OK;
     int rc = wgrads_wait_chain(); if (rc) return rc;
     // cap on workgroups per weight-gradient launch (leaving CUs to the chain): measured 79.6 ms uncapped, 81.0 at 128,
@@ -1669,223 +1702,251 @@ static int run_backward(ipoke_flow* f, const float* params, const int32_t* perm,
             o2.Kc3 != op.Kc3) break;
         ++i1;
       }
-      const int nb = (int)(i1 - i0), lo = f->ops[pend_nice[i1 - 1]].nice_idx;
-      ipoke_wgrad_desc w;
-      auto base8 = [&](int k, int pad) {
-        std::memset(&w, 0, sizeof(w));
-        w.NB = B; w.Di = 1; w.Hi = 8; w.Wi = 8; w.Do = 1; w.Ho = 8; w.Wo = 8; w.kd = 1; w.kh = w.kw = k;
-        w.sd = w.sh = w.sw = 1; w.ph = w.pw = pad;
-        w.max_workgroups = 0;
-      };
-      auto entries = [&](int k) {
-        return reinterpret_cast<const unsigned char*>(f->d_ntab[k]) + (size_t)lo * ipoke_wgrad_batch_entry_size();
-      };
-      // conv3 (effective weight; weight-norm backward runs at the end)
-      base8(3, 1);
-      w.a_sn = 64L * op.hidK; w.a_sh = 8L * op.hidK; w.a_sw = op.hidK; w.a_sc = 1; w.Kc_real = op.hidK; w.Kc = op.hidK;
-      w.ldy = op.Kc3; w.Nout = 2 * op.cout;
-      w.w_sn = (int64_t)op.hidK * 9; w.w_sc = 9; w.w_st = 1;
-      rc = ipoke_conv_wgrad_batched(&w, entries(2), nb, c.ws, c.ws, grads, c.dtype, wstream); if (rc) return rc;
-      // conv2
-      base8(1, 0);
-      w.a_sn = 64L * hid; w.a_sh = 8L * hid; w.a_sw = hid; w.a_sc = 1; w.Kc_real = hid; w.Kc = hid;
-      w.ldy = hid; w.Nout = hid;
-      w.w_sn = hid; w.w_sc = 1; w.w_st = 0;
-      ipoke_wgrad_adam wa;
-      if (wgrad_adam) {
-        const ipoke_flow::NativeAdam& A = f->nadam;
-        wa.params = const_cast<float*>(params); wa.m = A.m; wa.v = A.v; wa.vmax = A.vmax;
-        wa.operand = const_cast<unsigned char*>(c.shadow + c.shadow_base());
-        wa.lr = A.lr; wa.beta1 = A.beta1; wa.beta2 = A.beta2; wa.eps = A.eps; wa.weight_decay = A.wd; wa.grad_scale = A.grad_scale; wa.step = A.step;
-        wa.keep_grad = wgrad_adam_mode == 2;
-        w.adam = &wa;
-      }
-      rc = ipoke_conv_wgrad_batched(&w, entries(1), nb, c.ws, c.ws, grads, c.dtype, wstream); if (rc) return rc;
-      // conv1 (input = conditioning channels of the saved state)
-      base8(3, 1);
-      w.a_f32 = 0; w.a_sn = 64L * op.Kc1; w.a_sh = 8L * op.Kc1; w.a_sw = op.Kc1; w.a_sc = 1;
-      w.Kc_real = op.Kc1; w.Kc = op.Kc1;
-      w.ldy = hid; w.Nout = hid;
-      w.w_sn = (int64_t)op.cin * 9; w.w_sc = 9; w.w_st = 1; w.Kc_store = op.cin;
-      rc = ipoke_conv_wgrad_batched(&w, entries(0), nb, c.ws, c.ws, grads, c.dtype, wstream); if (rc) return rc;
+      rc = nice_wgrads(op, (int)(i1 - i0), f->ops[pend_nice[i1 - 1]].nice_idx); if (rc) return rc;
       i0 = i1;
     }
     pend_nice.clear();
     return IPOKE_OK;
-  };
-  flush_nice_fn = flush_nice;
+  }
   // Every flush costs the CHAIN an event record (the side stream must see the couplings' operands): a barrier packet with a completion
   // signal between two chain kernels, ~10 us of queue time each (profiles/r03_bench_trace_gaps.txt: 112 gaps of 12.8 us per step in
   // front of the fused units).  kNiceFlushMin couplings are collected before the chain pays for one (the end of a piece always
   // flushes: finish_piece).
   // round 6 (with the stationary-input conv1 / conv3 weight gradients: 32 workgroups per problem): four couplings per batch, 48.83 / 48.62
   // against 48.98 / 49.04 ms at two (one call); 3 / 6 / 8: 48.9 / 48.8 / 48.8
-  constexpr int kNiceFlushMin = 4;
-  auto maybe_flush_nice = [&]() -> int { return (int)pend_nice.size() >= kNiceFlushMin ? flush_nice() : (int)IPOKE_OK; };
-  size_t pk = 0;
-  int cur = 0;
-  int pending_an = -1;              // ActNorm op whose backward is carried by the next (lower) coupling's launch
-  const int64_t goff[2] = {c.plan.g0, c.plan.g1};
-  for (int i = (int)f->ops.size() - 1; i >= 0; --i) {
+  static constexpr int kNiceFlushMin = 4;
+  int maybe_flush_nice() { return (int)pend_nice.size() >= kNiceFlushMin ? flush_nice() : (int)IPOKE_OK; }
+
+  int native_adam_range(int64_t b0, int64_t b1, int max_blocks) {
+    const ipoke_flow::NativeAdam& A = f->nadam;
+    float* pm = const_cast<float*>(c.params);
+    void* shadow = const_cast<unsigned char*>(c.shadow);
+    void* rstream = reinterpret_cast<void*>(rs);
+    if (f->c2_straight)      // conv2 tensors: update + their one operand in the same linear pass; the rest: update, then relayout
+      return adam_range(f, pm, grads, A.m, A.v, A.vmax, shadow, b0, b1, A.lr, A.beta1, A.beta2, A.eps, A.wd, A.step, A.grad_scale, max_blocks,
+                        rstream, wgrad_adam);
+    int r = ipoke_adam_amsgrad_step_grid(pm + b0, grads + b0, A.m + b0, A.v + b0, A.vmax + b0, b1 - b0, A.lr, A.beta1, A.beta2, A.eps, A.wd, A.step,
+                                         A.grad_scale, max_blocks, rstream);
+    if (r) return r;
+    return prepare_range(f, c.params, shadow, b0, b1, false, rstream);
+  }
+  // The chain has queued the lowest op of piece pk: the piece's last weight gradients, then on the ready stream its reductions, weight-norm
+  // backward, optimizer (ipoke_flow_set_native_adam) and `ready` calls; piece pk + 1 becomes the current one
+  int finish_piece() {
+    const int unit_lo = pieces[pk].first, unit_hi = pieces[pk].second;
+    int r = flush_nice(); if (r) return r;
+    r = flush_mcf(); if (r) return r;
+    r = stream_wait(f, rs, c.s); if (r) return r;                   // the chain up to here ...
+    r = stream_wait(f, rs, f->side); if (r) return r;               // ... and the weight gradients of this piece
+    void* rstream = reinterpret_cast<void*>(rs);
+    // bias / ActNorm parameter gradients: multi-tensor reduction over the per-sample partial sums of the piece's layers
+    const int r0 = f->red_first[f->units[unit_lo].op_lo], r1 = f->red_first[f->units[unit_hi].op_hi];
+    if (r1 > r0) {
+      r = ipoke_reduce_rows_multi(reinterpret_cast<const float*>(c.ws), grads, tab_entry(f->d_redtab, r0, (size_t)ipoke_reduce_entry_size()),
+                                  r1 - r0, c.B, rstream);
+      if (r) return r;
+    }
+    const PieceRanges pr = piece_ranges(f, unit_lo, unit_hi);
+    for (int kind = 0; kind < 2; ++kind) {
+      if (pr.p0[kind] < 0) continue;
+      r = ipoke_wn_bwd_multi_range(c.params, grads, c.wn_inv(), f->d_wjobs, pr.wj0[kind], pr.wj1[kind] - pr.wj0[kind], pr.rw0[kind],
+                                   pr.rw1[kind] - pr.rw0[kind], rstream);
+      if (r) return r;
+    }
+    // (Moving the first k pieces' update + refresh behind the last piece's, into the step-boundary hole, was measured in round 6 and
+    // removed: 50.9 / 52.3 / 54.1 ms at k = 4 / 8 / 12 against 49.5 -- profiles/r06_ab_lines.txt.)
+    // (The optimizer of all but the last three pieces on a smaller grid: 61.0 / 55.1 / 54.2 ms at 64 / 96 / 128 blocks against 54.4-54.6.)
+    if (f->nadam.on) {
+      // single-GPU training: the update of the piece's ranges and the refresh of their shadows, natively, on the ready stream
+      for (int kind = 0; kind < 3; ++kind) {
+        if (!pr.has_params(kind)) continue;
+        r = native_adam_range(pr.p0[kind], pr.p1[kind], f->nadam.max_blocks); if (r) return r;
+      }
+    }
+    if (ready)
+      for (int kind = 0; kind < 3; ++kind)
+        if (pr.has_params(kind)) ready(user, (int)pk, pr.p0[kind], pr.p1[kind]);
+    ++pk;                                                           // the chain is in the next piece
+    return IPOKE_OK;
+  }
+  // after op i has been handled: when it is the lowest op of the current piece, the piece is final
+  int end_of_op(int i) { return lowest_of_piece(i) ? finish_piece() : (int)IPOKE_OK; }
+
+  // Whole MaCowUnit (ops h .. h+5) whose last op is i differentiated by one launch, or two adjacent ones (h .. h+11); *head = h, where the
+  // driver goes on (no piece ends inside a unit or at its head: a piece's lowest op is the ActNorm that opens a step or a prior)
+  int unit(int i, int* head) {
     const Op& op = f->ops[i];
-    if (op.unit_of >= 0 && i == op.unit_of + 5) {     // whole MaCowUnit (ops h .. h+5) differentiated by one launch, or two adjacent ones (h .. h+11)
-      const int nl = unit2_at(f, op.unit_of - 6, IPOKE_UNIT2_BWD) ? 8 : 4;
-      const int h = nl == 8 ? op.unit_of - 6 : op.unit_of;
-      rc = maybe_flush_nice(); if (rc) return rc;
-      static const int lidx[8] = {0, 1, 3, 4, 6, 7, 9, 10};
-      ipoke_mcf_desc d4[8];
-      for (int k = 0; k < nl; ++k) {
-        const int j = h + lidx[k];
-        const Op& mk = f->ops[j];
-        mcf_desc(c, mk, d4[k]);
-        d4[k].x = c.state(j);
-        d4[k].a2_save = c.at<void>(mk.ws_a); d4[k].scale_save = c.at<float>(mk.ws_b);
-        d4[k].dparams_save = c.at<void>(mk.ws_c); d4[k].dc_save = c.at<void>(mk.ws_d);
-        if (f->mcf_xop) d4[k].x_op_save = c.at<void>(mk.ws_e);
-        d4[k].dbias_part = c.dbp(j);
-        if (mk.fuse_act >= 0) {
-          const Op& an = f->ops[mk.fuse_act];
-          d4[k].post_log_scale = params + an.p_ls; d4[k].post_bias = params + an.p_bias;
-          d4[k].y_post = c.state(j + 2);
-          d4[k].post_part = c.dbp(mk.fuse_act);
-        }
-      }
-      d4[nl - 1].dy = c.at<float>(goff[cur]); d4[0].dx = c.at<float>(goff[cur ^ 1]); d4[0].dld = c.dld();
-      IPK_REQUIRE(f->unit_split == 1 || f->d_xchg, "row-split unit launches without exchange scratch (ensure_tables)");
-      if (f->unit_split > 1) { d4[0].split = f->unit_split; d4[0].xchg = f->d_xchg; }
-      ipoke_unit_pair_desc pq;
-      if (h >= 2 && f->ops[h - 1].pair_unit == h) {     // the (coupling, ActNorm) pair in front of the unit rides along
-        const Op& an = f->ops[h - 1]; const Op& cp = f->ops[h - 2];
-        std::memset(&pq, 0, sizeof(pq));
-        pq.an_log_scale = an.p_ls >= 0 ? params + an.p_ls : nullptr; pq.an_idx = an.idx_fwd >= 0 ? perm + an.idx_fwd : nullptr;
-        pq.an_x = c.state(h - 1); pq.an_part = an.p_ls >= 0 ? c.dbp(h - 1) : nullptr;
-        pq.Cp = cp.cout; pq.t_off = cp.t_off; pq.t_stride = cp.t_stride; pq.x0 = c.state(h - 2); pq.scale = c.at<float>(cp.ws_c);
-        pq.dparams = c.at<void>(cp.ws_d); pq.ldp = cp.Kc3; pq.dbias_part = c.dbp(h - 2);
-        pq.dx = d4[0].dx;
-        d4[0].pair = &pq;
-      }
-      rc = nl == 8 ? ipoke_macow_unit2_bwd(d4, c.dtype, c.stream()) : ipoke_macow_unit_bwd(d4, c.dtype, c.stream());
-      if (rc) return rc;
-      for (int k = nl - 1; k >= 0; --k) {            // weight gradients: deferred, batched per run of same-width layers
-        const int j = h + lidx[k];
-        const Op& mk = f->ops[j];
-        if (pend_lo >= 0 && (f->ops[pend_op].C != mk.C || pend_hi - pend_lo + 1 >= 256)) { rc = flush_mcf(); if (rc) return rc; }
-        if (pend_lo < 0) { pend_hi = mk.mcf_idx; pend_op = j; }
-        pend_lo = mk.mcf_idx;
-      }
-      cur ^= 1;
-      i = h;                                         // the loop decrement moves on to op h - 1
-      continue;
+    const int nl = unit2_at(f, op.unit_of - 6, IPOKE_UNIT2_BWD) ? 8 : 4;
+    const int h = *head = nl == 8 ? op.unit_of - 6 : op.unit_of;
+    int rc = maybe_flush_nice(); if (rc) return rc;
+    ipoke_mcf_desc d4[8];
+    for (int k = 0; k < nl; ++k) {
+      const int j = h + kUnitMcf[k];
+      mcf_desc(c, f->ops[j], d4[k]);
+      d4[k].x = c.state(j);
+      mcf_saved_bwd(c, j, d4[k]);
     }
-    if (op.fused) {                                  // differentiated inside the preceding MCF layer's backward kernel
-      if (i == f->units[pieces[pk].first].op_lo) { rc = finish_piece(pieces[pk].first, pieces[pk].second, pk); if (rc) return rc; ++pk; }
-      continue;
+    d4[nl - 1].dy = g(cur); d4[0].dx = g(cur ^ 1); d4[0].dld = c.dld();
+    IPK_REQUIRE(f->unit_split == 1 || f->d_xchg, "row-split unit launches without exchange scratch (ensure_tables)");
+    if (f->unit_split > 1) { d4[0].split = f->unit_split; d4[0].xchg = f->d_xchg; }
+    ipoke_unit_pair_desc pq;                          // (d4[0].pair points at it: it lives until the launch call has returned)
+    if (h >= 2 && f->ops[h - 1].pair_unit == h) {     // the (coupling, ActNorm) pair in front of the unit rides along
+      const Op& an = f->ops[h - 1]; const Op& cp = f->ops[h - 2];
+      std::memset(&pq, 0, sizeof(pq));
+      pq.an_log_scale = c.an_ls(an); pq.an_idx = c.an_idx_fwd(an);
+      pq.an_x = c.state(h - 1); pq.an_part = an.p_ls >= 0 ? c.dbp(h - 1) : nullptr;
+      pq.Cp = cp.cout; pq.t_off = cp.t_off; pq.t_stride = cp.t_stride; pq.x0 = c.state(h - 2); pq.scale = c.at<float>(cp.ws_c);
+      pq.dparams = c.at<void>(cp.ws_d); pq.ldp = cp.Kc3; pq.dbias_part = c.dbp(h - 2);
+      pq.dx = d4[0].dx;
+      d4[0].pair = &pq;
     }
+    rc = nl == 8 ? ipoke_macow_unit2_bwd(d4, c.dtype, c.stream()) : ipoke_macow_unit_bwd(d4, c.dtype, c.stream());
+    if (rc) return rc;
+    for (int k = nl - 1; k >= 0; --k) { rc = defer_mcf_wgrads(h + kUnitMcf[k]); if (rc) return rc; }
+    cur ^= 1;
+    return IPOKE_OK;
+  }
+  int lu(int i) {
+    const Op& op = f->ops[i];
+    int rc = maybe_flush_nice(); if (rc) return rc;
+    const float* gin = g(cur); float* gout = g(cur ^ 1);
+    // dx = dy W (W^T applied per position); parameter gradients straight into the flat buffer (the forward pass of
+    // this step left [W | W^-1 | wl | wu] in the workspace)
+    rc = ipoke_lu_apply(gin, gout, c.M, c.ld, op.C, lu_mat(c, op, 0), 1, c.stream()); if (rc) return rc;
+    rc = ipoke_lu_wgrad(gin, c.state(i), c.B, f->P, c.ld, c.params, f->fbuf, c.at<float>(c.plan.lu),
+                        tab_entry(f->d_lujobs, op.lu_idx, sizeof(LuJobH)), c.dld(), grads, c.stream());
+    if (rc) return rc;
+    cur ^= 1;
+    return IPOKE_OK;
+  }
+  int actnorm(int i) {
+    const Op& op = f->ops[i];
+    if (op.pair_unit >= 0) return IPOKE_OK;        // differentiated by the unit's launch (unit(); so was its coupling: nice())
     // An ActNorm right behind a coupling is differentiated by the coupling's launch (ipoke_actnorm_affine_bwd), unless it is the
     // lowest op of the current piece: its parameter-gradient partials must exist when the piece is finished right after this op.
-    if (op.type == OP_ACTNORM && op.pair_unit >= 0) {      // differentiated by the unit's launch above (so was its coupling: below)
-      if (i == f->units[pieces[pk].first].op_lo) { rc = finish_piece(pieces[pk].first, pieces[pk].second, pk); if (rc) return rc; ++pk; }
+    if (op.an_prev >= 0 && !lowest_of_piece(i)) { pending_an = i; return IPOKE_OK; }
+    int rc = maybe_flush_nice(); if (rc) return rc;
+    rc = ipoke_actnorm_bwd(g(cur), c.state(i), g(cur ^ 1), (int)c.M, c.ld, op.c0, op.Cn, c.an_ls(op), c.an_idx_fwd(op), c.dld(), c.B, f->P,
+                           c.dbp(i), c.stream());
+    if (rc) return rc;
+    cur ^= 1;
+    return IPOKE_OK;
+  }
+  int mcf(int i) {                                 // a masked-conv layer outside a fused unit
+    const Op& op = f->ops[i];
+    int rc = maybe_flush_nice(); if (rc) return rc;
+    float* gout = g(cur ^ 1);
+    ipoke_mcf_desc d; mcf_desc(c, op, d);
+    d.x = c.state(i); d.dy = g(cur); d.dx = gout; d.dld = c.dld();
+    mcf_saved_bwd(c, i, d);
+    d.y = gout;   // unused by the backward kernel, must be non-null for the shared validator
+    rc = ipoke_mcf_bwd(&d, c.dtype, c.stream()); if (rc) return rc;
+    rc = defer_mcf_wgrads(i); if (rc) return rc;
+    cur ^= 1;
+    return IPOKE_OK;
+  }
+  // data gradients of coupling net `op` from dprm (d raw shift / scale): conv3's and conv2's into dp2 / dp1, conv1's accumulated into the
+  // conditioning channels of gout
+  int nice_dgrads(const Op& op, float* gout) {
+    const int hid = f->cfg.hidden;
+    const void* h1 = c.at<void>(op.ws_a); const void* h2 = c.at<void>(op.ws_b);
+    void* dprm = c.at<void>(op.ws_d); void* dp2 = c.at<void>(op.ws_e); void* dp1 = c.at<void>(op.ws_f);
+    ipoke_conv_desc d;
+    // conv3 data gradient, times ELU'(h2)
+    set_conv8(d, c.B, 3, 1); d.transposed = 1;
+    set_a_dense(d, dprm, op.Kc3, op.Kc3);
+    d.W = c.sh(op.sh_c3t); d.ldw = 9 * op.Kc3; d.Nout = hid; d.dact = h2; d.ld_dact = op.hidK; d.dact_act = IPOKE_ACT_ELU;
+    d.C = dp2; d.ldc = hid;
+    int rc = ipoke_conv_forward(&d, c.dtype, c.stream()); if (rc) return rc;
+    // conv2 data gradient, times ELU'(h1), and conv1 data gradient accumulated into the conditioning channels
+    ipoke_conv_desc d1;
+    set_conv8(d, c.B, 1, 0);
+    set_a_dense(d, dp2, hid, hid);
+    if (f->c2_straight) { d.W = c.sh(op.sh_c2); d.w_kmajor = 1; }      // W2[out][in] read K-major: no transposed copy exists
+    else d.W = c.sh(op.sh_c2t);
+    d.ldw = hid; d.Nout = hid; d.dact = h1; d.ld_dact = hid; d.dact_act = IPOKE_ACT_ELU;
+    d.C = dp1; d.ldc = hid;
+    set_conv8(d1, c.B, 3, 1); d1.transposed = 1;
+    set_a_dense(d1, dp1, hid, hid);
+    d1.W = c.sh(op.sh_c1t); d1.ldw = 9 * hid; d1.Nout = op.cin; d1.C = gout; d1.c_f32 = 1; d1.c_accumulate = 1; d1.ldc = c.ld;
+    d1.c_coff = op.z_off; d1.c_cstride = op.z_stride; d1.splitk = nice_splitk(c);
+    // the K slices meet in the engine's scratch and are summed in a fixed order (bit-reproducible steps); wider inputs keep the atomic form
+    if (op.cin <= 64) { d1.acc_scratch = f->d_acc; d1.acc_scratch_bytes = f->acc_bytes; }
+    // one launch where the pair kernel takes the shape (c2: B <= 32 at hidden 2048, cin <= 32): conv1's slices are the GEMM's column tiles
+    const bool pair_dgrad = f->c2_straight && !f->cfg.condition_nice &&
+                            ipoke_conv_pair_dgrad_applicable((int)c.M, hid, op.cin, c.dtype, f->acc_bytes);
+    if (pair_dgrad && !f->split_pair_dgrad) return ipoke_conv_pair_dgrad(&d, &d1, c.dtype, c.stream());
+    if (pair_dgrad) d1.splitk = hid / 128;      // test hook: the two launches with the pair kernel's slices, i.e. the same sums in the same order
+    rc = ipoke_conv_forward(&d, c.dtype, c.stream()); if (rc) return rc;
+    d = d1;
+    return ipoke_conv_forward(&d, c.dtype, c.stream());
+  }
+  int nice(int i) {
+    const Op& op = f->ops[i];
+    const bool by_unit = op.pair_unit >= 0;        // dx / dparams / partials of this coupling were written by a unit's launch
+    const float* gin = g(cur); float* gout = g(by_unit ? cur : cur ^ 1);
+    const float* xin = c.state(i);                 // saved input of op i
+    void* dprm = c.at<void>(op.ws_d);
+    int rc = IPOKE_OK;
+    if (by_unit) {
+    } else if (pending_an == i + 1) {
+      const Op& an = f->ops[i + 1];
+      rc = ipoke_actnorm_affine_bwd(an.c0, an.Cn, c.an_ls(an), c.an_idx_fwd(an), gin, c.state(i + 1), an.p_ls >= 0 ? c.dbp(i + 1) : nullptr,
+                                    op.cout, op.t_off, op.t_stride, f->P, c.ld, xin, c.at<float>(op.ws_c), c.dld(), gout, dprm, op.Kc3,
+                                    c.dbp(i), c.B, c.dtype, c.stream());
+    } else {
+      rc = ipoke_affine_bwd(op.cout, op.t_off, op.t_stride, f->P, c.ld, gin, xin, c.at<float>(op.ws_c), c.dld(), gout, dprm,
+                            op.Kc3, c.dbp(i), c.B, c.dtype, c.stream());
+    }
+    if (rc) return rc;
+    rc = nice_dgrads(op, gout); if (rc) return rc;
+    pend_nice.push_back(i);      // weight gradients: launched when the chain leaves this group of couplings
+    if (pending_an == i + 1) pending_an = -1;
+    if (!by_unit) cur ^= 1;
+    return IPOKE_OK;
+  }
+};
+
+}  // namespace
+
+static int run_backward(ipoke_flow* f, const float* params, const int32_t* perm, const void* shadow,
+                        const float* d_out_nchw, const float* d_logdet, int B, float* grads, float* dx_nchw,
+                        void* workspace, hipStream_t s, int npieces = 1, hipStream_t ready_stream = nullptr,
+                        ipoke_grad_ready_fn ready = nullptr, void* user = nullptr) {
+  Ctx c;
+  int rc = make_ctx(f, B, params, perm, shadow, workspace, s, 1, &c); if (rc) return rc;
+  IPK_REQUIRE(params && perm && shadow && d_out_nchw && d_logdet && grads && workspace, "null argument");
+  const int z = f->cfg.z_channels;
+  rc = ipoke_nchw_to_state(d_out_nchw, c.at<float>(c.plan.g0), B, z, f->P, c.ld, c.stream()); if (rc) return rc;
+  IPK_HIP(hipMemcpyAsync(c.dld(), d_logdet, B * sizeof(float), hipMemcpyDeviceToDevice, s));
+  rc = ensure_tables(f, B, c.plan); if (rc) return rc;
+  rc = stream_wait(f, f->side, s); if (rc) return rc;      // the side stream joins after everything already queued on the main stream
+  BackwardPass bp(c, grads, npieces, ready_stream, ready, user);
+  for (int i = (int)f->ops.size() - 1; i >= 0; --i) {
+    const Op& op = f->ops[i];
+    if (op.unit_of >= 0 && i == op.unit_of + 5) {      // the last op of a fused unit: the whole unit; the loop decrement moves on to op h - 1
+      rc = bp.unit(i, &i); if (rc) return rc;
       continue;
     }
-    if (op.type == OP_ACTNORM && op.an_prev >= 0 && i != f->units[pieces[pk].first].op_lo) { pending_an = i; continue; }
-    if (op.type != OP_NICE) { rc = maybe_flush_nice(); if (rc) return rc; }
-    const bool by_unit = op.type == OP_NICE && op.pair_unit >= 0;      // dx / dparams / partials of this coupling were written by a unit's launch
-    const float* gin = c.at<float>(goff[cur]); float* gout = c.at<float>(goff[by_unit ? cur : cur ^ 1]);
-    const float* xin = c.state(i);                 // saved input of op i
-    if (op.type == OP_LU) {
-      // dx = dy W (W^T applied per position); parameter gradients straight into the flat buffer (the forward pass of
-      // this step left [W | W^-1 | wl | wu] in the workspace)
-      rc = ipoke_lu_apply(gin, gout, c.M, c.ld, op.C, lu_mat(c, op, 0), 1, c.stream()); if (rc) return rc;
-      rc = ipoke_lu_wgrad(gin, xin, c.B, f->P, c.ld, params, f->fbuf, c.at<float>(c.plan.lu),
-                          reinterpret_cast<const unsigned char*>(f->d_lujobs) + (size_t)op.lu_idx * sizeof(LuJobH), c.dld(), grads,
-                          c.stream());
-      if (rc) return rc;
-    } else if (op.type == OP_ACTNORM) {
-      rc = ipoke_actnorm_bwd(gin, xin, gout, (int)c.M, c.ld, op.c0, op.Cn, op.p_ls >= 0 ? params + op.p_ls : nullptr,
-                             op.idx_fwd >= 0 ? perm + op.idx_fwd : nullptr, c.dld(), c.B, f->P, c.dbp(i), c.stream());
-      if (rc) return rc;
-    } else if (op.type == OP_MCF) {
-      ipoke_mcf_desc d; mcf_desc(c, op, d);
-      d.x = xin; d.dy = gin; d.dx = gout; d.dld = c.dld();
-      d.a2_save = c.at<void>(op.ws_a); d.scale_save = c.at<float>(op.ws_b);
-      d.dparams_save = c.at<void>(op.ws_c); d.dc_save = c.at<void>(op.ws_d);
-      d.dbias_part = c.dbp(i);
-      d.y = gout;   // unused by the backward kernel, must be non-null for the shared validator
-      if (op.fuse_act >= 0) {
-        const Op& an = f->ops[op.fuse_act];
-        d.post_log_scale = params + an.p_ls; d.post_bias = params + an.p_bias;
-        d.y_post = c.state(i + 2);                 // saved output of the fused pair
-        d.post_part = c.dbp(op.fuse_act);
-      }
-      rc = ipoke_mcf_bwd(&d, c.dtype, c.stream()); if (rc) return rc;
-    } else {
-      const void* h1 = c.at<void>(op.ws_a); const void* h2 = c.at<void>(op.ws_b);
-      void* dprm = c.at<void>(op.ws_d); void* dp2 = c.at<void>(op.ws_e); void* dp1 = c.at<void>(op.ws_f);
-      if (by_unit) {
-        rc = IPOKE_OK;
-      } else if (pending_an == i + 1) {
-        const Op& an = f->ops[i + 1];
-        rc = ipoke_actnorm_affine_bwd(an.c0, an.Cn, an.p_ls >= 0 ? params + an.p_ls : nullptr, an.idx_fwd >= 0 ? perm + an.idx_fwd : nullptr,
-                                      gin, c.state(i + 1), an.p_ls >= 0 ? c.dbp(i + 1) : nullptr, op.cout, op.t_off, op.t_stride,
-                                      f->P, c.ld, xin, c.at<float>(op.ws_c), c.dld(), gout, dprm, op.Kc3, c.dbp(i), c.B,
-                                      c.dtype, c.stream());
-      } else {
-        rc = ipoke_affine_bwd(op.cout, op.t_off, op.t_stride, f->P, c.ld, gin, xin, c.at<float>(op.ws_c), c.dld(), gout, dprm,
-                              op.Kc3, c.dbp(i), c.B, c.dtype, c.stream());
-      }
-      if (rc) return rc;
-      ipoke_conv_desc d;
-      // conv3 data gradient, times ELU'(h2)
-      set_conv8(d, c.B, 3, 1); d.transposed = 1;
-      set_a_dense(d, dprm, op.Kc3, op.Kc3);
-      d.W = c.sh(op.sh_c3t); d.ldw = 9 * op.Kc3; d.Nout = hid; d.dact = h2; d.ld_dact = op.hidK; d.dact_act = IPOKE_ACT_ELU;
-      d.C = dp2; d.ldc = hid;
-      rc = ipoke_conv_forward(&d, c.dtype, c.stream()); if (rc) return rc;
-      // conv2 data gradient, times ELU'(h1), and conv1 data gradient accumulated into the conditioning channels
-      ipoke_conv_desc d1;
-      set_conv8(d, c.B, 1, 0);
-      set_a_dense(d, dp2, hid, hid);
-      if (f->c2_straight) { d.W = c.sh(op.sh_c2); d.w_kmajor = 1; }      // W2[out][in] read K-major: no transposed copy exists
-      else d.W = c.sh(op.sh_c2t);
-      d.ldw = hid; d.Nout = hid; d.dact = h1; d.ld_dact = hid; d.dact_act = IPOKE_ACT_ELU;
-      d.C = dp1; d.ldc = hid;
-      set_conv8(d1, c.B, 3, 1); d1.transposed = 1;
-      set_a_dense(d1, dp1, hid, hid);
-      d1.W = c.sh(op.sh_c1t); d1.ldw = 9 * hid; d1.Nout = op.cin; d1.C = gout; d1.c_f32 = 1; d1.c_accumulate = 1; d1.ldc = c.ld;
-      d1.c_coff = op.z_off; d1.c_cstride = op.z_stride; d1.splitk = nice_splitk(c);
-      // the K slices meet in the engine's scratch and are summed in a fixed order (bit-reproducible steps); wider inputs keep the atomic form
-      if (op.cin <= 64) { d1.acc_scratch = f->d_acc; d1.acc_scratch_bytes = f->acc_bytes; }
-      // one launch where the pair kernel takes the shape (c2: B <= 32 at hidden 2048, cin <= 32): conv1's slices are the GEMM's column tiles
-      const bool pair_dgrad = f->c2_straight && !f->cfg.condition_nice &&
-                              ipoke_conv_pair_dgrad_applicable((int)c.M, hid, op.cin, c.dtype, f->acc_bytes);
-      if (pair_dgrad && !f->split_pair_dgrad) {
-        rc = ipoke_conv_pair_dgrad(&d, &d1, c.dtype, c.stream()); if (rc) return rc;
-      } else {
-        if (pair_dgrad) d1.splitk = hid / 128;      // test hook: the two launches with the pair kernel's slices, i.e. the same sums in the same order
-        rc = ipoke_conv_forward(&d, c.dtype, c.stream()); if (rc) return rc;
-        d = d1;
-        rc = ipoke_conv_forward(&d, c.dtype, c.stream()); if (rc) return rc;
-      }
-    }
-    if (op.type == OP_MCF) {
-      // weight gradients: deferred, batched per run of same-width layers
-      if (pend_lo >= 0 && (f->ops[pend_op].C != op.C || pend_hi - pend_lo + 1 >= 256)) { rc = flush_mcf(); if (rc) return rc; }
-      if (pend_lo < 0) { pend_hi = op.mcf_idx; pend_op = i; }
-      pend_lo = op.mcf_idx;
-    } else if (op.type == OP_NICE) {
-      pend_nice.push_back(i);      // weight gradients: launched when the chain leaves this group of couplings
-      if (pending_an == i + 1) pending_an = -1;
-    }
-    if (!(op.type == OP_NICE && op.pair_unit >= 0)) cur ^= 1;
-    if (i == f->units[pieces[pk].first].op_lo) {        // the lowest op of the current piece has been queued
-      rc = finish_piece(pieces[pk].first, pieces[pk].second, pk); if (rc) return rc;
-      ++pk;
-    }
+    if (op.fused) rc = IPOKE_OK;                       // differentiated inside the preceding MCF layer's backward kernel
+    else if (op.type == OP_LU) rc = bp.lu(i);
+    else if (op.type == OP_ACTNORM) rc = bp.actnorm(i);
+    else if (op.type == OP_MCF) rc = bp.mcf(i);
+    else rc = bp.nice(i);
+    if (rc) return rc;
+    rc = bp.end_of_op(i); if (rc) return rc;
   }
   // later work on the caller's stream (optimizer step) sees every gradient (this wait costs the next forward pass 0.25 ms; the
   // engine-issued optimizer and operand refresh as a whole 6.4 of 50.9 ms)
-  rc = stream_wait(f, s, rs); if (rc) return rc;
-  if (dx_nchw) { rc = ipoke_state_to_nchw(c.at<float>(goff[cur]), dx_nchw, B, z, f->P, c.ld, stream); if (rc) return rc; }
+  rc = stream_wait(f, s, bp.rs); if (rc) return rc;
+  if (dx_nchw) { rc = ipoke_state_to_nchw(bp.g(bp.cur), dx_nchw, B, z, f->P, c.ld, c.stream()); if (rc) return rc; }
+  return IPOKE_OK;
+}
+
+// the two backward entry points differentiate the states the last training forward pass left in the workspace
+static int require_saved_forward(const ipoke_flow* f, int B) {
+  if (!f->have_saved || f->last_fwd_B != B)
+    return fail(IPOKE_ERR_STATE, "ipoke_flow_backward needs a preceding ipoke_flow_forward(save_for_backward=1) with the same batch");
   return IPOKE_OK;
 }
 
@@ -1893,11 +1954,10 @@ extern "C" int ipoke_flow_backward(ipoke_flow* f, const float* params, const int
                                    const float* d_out_nchw, const float* d_logdet, int B, float* grads, float* dx_nchw,
                                    void* workspace, void* stream) {
   IPK_REQUIRE(f != nullptr, "null flow handle");
-  if (!f->have_saved || f->last_fwd_B != B)
-    return fail(IPOKE_ERR_STATE, "ipoke_flow_backward needs a preceding ipoke_flow_forward(save_for_backward=1) with the same batch");
+  int rc = require_saved_forward(f, B); if (rc) return rc;
   std::vector<uintptr_t> key = {3, (uintptr_t)params, (uintptr_t)perm, (uintptr_t)shadow, (uintptr_t)d_out_nchw, (uintptr_t)d_logdet,
                                 (uintptr_t)B, (uintptr_t)grads, (uintptr_t)dx_nchw, (uintptr_t)workspace};
-  int rc = pass_begin(f, reinterpret_cast<hipStream_t>(stream)); if (rc) return rc;
+  rc = pass_begin(f, reinterpret_cast<hipStream_t>(stream)); if (rc) return rc;
   rc = with_graph(f, std::move(key), reinterpret_cast<hipStream_t>(stream), [&](hipStream_t s) {
     return run_backward(f, params, perm, shadow, d_out_nchw, d_logdet, B, grads, dx_nchw, workspace, s);
   });
@@ -1909,10 +1969,9 @@ extern "C" int ipoke_flow_backward_pieces(ipoke_flow* f, const float* params, co
                                           void* workspace, int npieces, void* ready_stream, ipoke_grad_ready_fn ready, void* user,
                                           void* stream) {
   IPK_REQUIRE(f != nullptr, "null flow handle");
-  if (!f->have_saved || f->last_fwd_B != B)
-    return fail(IPOKE_ERR_STATE, "ipoke_flow_backward needs a preceding ipoke_flow_forward(save_for_backward=1) with the same batch");
+  int rc = require_saved_forward(f, B); if (rc) return rc;
   // host callbacks cannot be captured: always eager
-  int rc = pass_begin(f, reinterpret_cast<hipStream_t>(stream)); if (rc) return rc;
+  rc = pass_begin(f, reinterpret_cast<hipStream_t>(stream)); if (rc) return rc;
   rc = run_backward(f, params, perm, shadow, d_out_nchw, d_logdet, B, grads, dx_nchw, workspace,
                     reinterpret_cast<hipStream_t>(stream), npieces, reinterpret_cast<hipStream_t>(ready_stream), ready, user);
   return rc ? rc : pass_end(f, reinterpret_cast<hipStream_t>(stream));

@@ -285,6 +285,87 @@ def test_backward_in_pieces_matches_and_covers_all_parameters():
         assert starts and starts == sorted(starts, reverse=True)
 
 
+_PIECE_ARCHS = {"plain": lambda: configs.reduced_flow_arch(),
+                "use1x1": lambda: dict(configs.reduced_flow_arch(), use1x1=True),
+                "condition_nice": lambda: _condition_nice_arch(32)}
+_piece_refs = {}
+
+
+def _piecewise_reference(arch_name, dtype):
+    """(model, x, cond, one-shot gradients, their run-to-run noise, unit count) of one architecture and dtype, computed once and shared by
+    the piece counts"""
+    key = (arch_name, dtype)
+    if key not in _piece_refs:
+        import ctypes
+        from ipoke_amd import _lib
+        from ipoke_amd.flow import SupervisedMacowTransformer
+        arch = _PIECE_ARCHS[arch_name]()
+        m = SupervisedMacowTransformer(arch, dtype=dtype, max_batch=2, device="cuda")
+        gen = torch.Generator(device="cuda").manual_seed(5)
+        x = torch.randn(2, arch["flow_in_channels"], 8, 8, device="cuda", generator=gen)
+        cond = torch.randn(2, arch["h_channels"], 8, 8, device="cuda", generator=gen)
+        with torch.no_grad():
+            m(x, cond)
+            for name, p in m.named_parameters():
+                if name.endswith("weight_g"):
+                    p.fill_(0.07)
+        m.mark_weights_updated()
+        m.train()
+        ref = _piecewise_run(m, x, cond)
+        noise = (_piecewise_run(m, x, cond) - ref).abs().max().item()      # the split-K data gradients accumulate with fp32 atomics
+        # every unit its own piece: a request far above the unit count is clamped to it
+        nr = _lib.lib().ipoke_flow_piece_ranges(m.engine.handle, 1 << 20, None, 0)
+        buf = (ctypes.c_int64 * (3 * nr))()
+        assert _lib.lib().ipoke_flow_piece_ranges(m.engine.handle, 1 << 20, buf, nr) == nr
+        units = len({buf[3 * i] for i in range(nr)})
+        _piece_refs[key] = (m, x, cond, ref, noise, units)
+    return _piece_refs[key]
+
+
+def _piecewise_run(m, x, cond):
+    m.flat_grads.zero_()
+    out, logdet = m(x, cond)
+    ((out ** 2).sum() * 0.5 - logdet.sum()).backward()
+    torch.cuda.synchronize()
+    return m.flat_grads.clone()
+
+
+@pytest.mark.parametrize("npieces", ["2", "units", "64"])
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("arch_name", ["plain", "use1x1", "condition_nice"])
+def test_backward_in_pieces_over_architectures_and_piece_counts(arch_name, dtype, npieces):
+    """The three assertions of test_backward_in_pieces_matches_and_covers_all_parameters, by the same rules, where the piece boundaries
+    fall elsewhere: with the LU convs' third parameter region (use1x1), with condition_nice, in both dtypes, at 2 pieces, at one piece
+    per unit (an ActNorm is then the lowest op of its piece) and at a request above the unit count (clamped to it)."""
+    m, x, cond, ref, noise, units = _piecewise_reference(arch_name, dtype)
+    assert 2 < units < 64
+    n = units if npieces == "units" else int(npieces)
+    ranges = []
+    m.engine.grad_ready_hook = (n, torch.cuda.Stream(), lambda b, e: ranges.append((b, e)))
+    try:
+        got = _piecewise_run(m, x, cond)
+    finally:
+        m.engine.grad_ready_hook = None
+    scale = ref.abs().max().item()
+    diff = (got - ref).abs().max().item()
+    print(f"[{arch_name} {dtype} {n} pieces of {units} units] diff {diff:.3e}, noise {noise:.3e}, scale {scale:.3e}, {len(ranges)} ranges")
+    assert diff <= max(4 * noise, 1e-6 * scale), (diff, noise, scale)
+    assert len(ranges) >= min(n, units)
+    covered = torch.zeros(m.engine.n_params, dtype=torch.int32)
+    for b, e in ranges:
+        covered[b:e] += 1
+    assert int(covered.min()) == 1 and int(covered.max()) == 1
+    # per region (layers.*, priors.*, with use1x1 shuffle_layers.*) the ranges arrive from the end of the flat buffer towards its start
+    first = {pfx: min((off for name, off, shape, kind in m.engine.tensors if name.startswith(pfx) and kind == 0), default=m.engine.n_params)
+             for pfx in ("flow.priors.", "flow.shuffle_layers.")}
+    prior0, shuf0 = first["flow.priors."], first["flow.shuffle_layers."]
+    assert (shuf0 < m.engine.n_params) == (arch_name == "use1x1")
+    regions = [lambda b: b < prior0, lambda b: prior0 <= b < shuf0] + ([lambda b: b >= shuf0] if arch_name == "use1x1" else [])
+    for region in regions:
+        starts = [b for b, _ in ranges if region(b)]
+        assert starts and starts == sorted(starts, reverse=True)
+
+
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 def test_hipgraph_replay_is_bit_identical_to_eager(golden, dtype):
     """configs[4] (sampling, "hipGraph-captured"): reverse and forward replayed from captured graphs give the same bits as

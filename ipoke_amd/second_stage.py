@@ -9,6 +9,7 @@ the three sub-model configurations from ``config['first_stage']``, ``config['pok
 ``load_first_stage / load_poke_embedder / load_conditioner`` which mirror ``__initialize_*`` (:182-236).
 ``ipoke_amd.trainer.SecondStageTrainer`` is the loop that drives it (the counterpart of pl.Trainer.fit).
 """
+import itertools
 from functools import partial
 
 import numpy as np
@@ -17,16 +18,62 @@ import os
 import torch
 import torch.nn as nn
 
-from .first_stage import FirstStageWrapper, SpadeCondMotionModel
+from . import _lib, metrics, nn as K
+from .data import PokeSimulator
+from .first_stage import Conv2dTransposeBlock, FirstStageWrapper, SpadeCondMotionModel
 from .flow import SupervisedMacowTransformer
+from .fvd import FVD, calculate_FVD
 from .loss import FlowLoss
 from .optim import FusedAdamAmsgrad
+from .utils.streams import overlapping_stream
+from .vgg import metric_vgg16
 
 
 def linear_var(act_it, start_it, end_it, start_val, end_val, clip_min, clip_max):
     """utils/general.py:221-228."""
     act_val = float(end_val - start_val) / (end_it - start_it) * (act_it - start_it) + start_val
     return float(np.clip(act_val, a_min=clip_min, a_max=clip_max))
+
+
+class _GraphCache(dict):
+    """The captured hipGraphs of one device function: a dict with one entry per input shape.  An entry goes "absent" -> "warm" (the first call of a
+    shape ran eager, which builds every lazily cached weight operand) -> "ready" (the second call captured; it and every later call copy
+    their inputs in and replay).  The graphs hold the ADDRESSES of the cached weight operands, so whatever drops those (a state-dict
+    load) clears it (``PokeMotionModel._drop_graphs``).  What differs between the two users -- grad mode and streams of the capture, host draws per call, weight
+    refresh before a replay, who owns the outputs -- stays with them (``_flow_input_graphed``, ``_sample_graphed``)."""
+
+    enabled = False
+
+    def set(self, enable):
+        self.enabled = bool(enable)
+        self.clear()
+
+    def entry(self, *inputs):
+        """The entry of the inputs' shapes and dtypes; "absent" on their first call."""
+        return self.setdefault(tuple((tuple(x.shape), x.dtype) for x in inputs), {"state": "absent"})
+
+    @staticmethod
+    def warmed(ent, **remember):
+        """absent -> warm: the caller has run the function eager; ``remember``: what the later calls need from that run."""
+        ent.update(state="warm", **remember)
+
+    @staticmethod
+    def capture(ent, fn, inputs, device):
+        """warm -> ready: capture ``fn`` on static copies of ``inputs`` (on ``device``)."""
+        static = [x.to(device, copy=True) for x in inputs]
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            out = fn(*static)
+        ent.update(state="ready", graph=g, static=static, out=out)
+
+    @staticmethod
+    def replay(ent, inputs):
+        """Copy ``inputs`` into the static buffers and replay.  Returns the graph's STATIC outputs: the next replay overwrites them."""
+        for s, x in zip(ent["static"], inputs):
+            s.copy_(x, non_blocking=True)
+        ent["graph"].replay()
+        return ent["out"]
 
 
 class PokeMotionModel(nn.Module):
@@ -51,6 +98,13 @@ class PokeMotionModel(nn.Module):
         self.div_scores = []
         self.vggm = None
         self._test_state = None
+        # validation: attach_fvd() sets the metric; the clips kept for the epoch's FVD
+        self.FVD = None
+        self._fvd_fake, self._fvd_true, self._fvd_fake_x0, self._fvd_true_x0 = [], [], [], []
+        self._enc_graphs, self._sample_graphs = _GraphCache(), _GraphCache()     # set_encoder_graph / set_sample_graph
+        self._prefetched = {}                    # id(batch) -> FIFO of prefetch_flow_input results
+        self._decode_stream = None               # sample_stream's second stream, picked on first use
+        self._poke_simulator = None
         self.device_ = torch.device(device) if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
         lr = tr["lr"]
@@ -108,7 +162,6 @@ class PokeMotionModel(nn.Module):
             raise NotImplementedError("adapt_poke_emb_ssize: the reference's own adapter resizes in the wrong direction for either ratio "
                                       "(second_stage_video.py:114-118) and cannot run; use a poke embedder with the first stage's latent size")
         if self.adapt_cond_ssize:
-            from .first_stage import Conv2dTransposeBlock
             factor = float(fs_min) / self.conditioner_config["architecture"]["min_spatial_size"]
             if factor < 1 or factor != int(factor):
                 # :123-126: `nn.Conv2d(..., stride=int(factor))` with factor < 1 is a stride-0 convolution ("non-positive stride")
@@ -165,10 +218,8 @@ class PokeMotionModel(nn.Module):
     def _drop_graphs(self):
         """Captured graphs hold the ADDRESSES of the cached weight operands: a state-dict load drops those caches (``_Cached``), so the
         graphs of ``set_sample_graph`` / ``set_encoder_graph`` are recaptured on their next use."""
-        if getattr(self, "_sample_graphs", None):
-            self._sample_graphs = {}
-        if getattr(self, "_enc_graphs", None):
-            self._enc_graphs = {}
+        self._sample_graphs.clear()
+        self._enc_graphs.clear()
 
     def load_first_stage(self, ckpt):
         self.first_stage_model.load_state_dict(self._sd(ckpt), strict=False)
@@ -205,54 +256,85 @@ class PokeMotionModel(nn.Module):
                 pg["lr"] = lr
 
     # ---- hot path ---------------------------------------------------------------------------------------
-    def make_flow_input(self, batch, reverse=False, use_kp_poke=False):
-        X = batch["images"]
-        if use_kp_poke:
-            poke, *_ = batch["keypoint_poke"]
-            poke = poke.to(torch.float)
-        else:
-            poke = batch[self.poke_key]
-            poke = poke[0] if isinstance(poke, list) else poke
-        if self.embed_poke_and_image:
-            poke = torch.cat([poke, X[:, 0]], dim=1)
+    def _eval_frozen(self):
+        """The frozen models are forced to eval mode before every use (:271-272)."""
         self.first_stage_model.eval(); self.poke_embedder.eval()
         if self.use_cond:
-            self.conditioner.eval()                   # :271-272
-        with torch.no_grad():
+            self.conditioner.eval()
+
+    def _poke_of(self, batch, use_kp_poke=False):
+        if use_kp_poke:
+            poke, *_ = batch["keypoint_poke"]
+            return poke.to(torch.float)
+        poke = batch[self.poke_key]
+        return poke[0] if isinstance(poke, list) else poke
+
+    def _cond_parts(self, x0, poke, side=None):
+        """The conditioning encoders on start frame ``x0`` and ``poke``: (image code or None, poke code), joined by ``_join_cond``.  Two
+        steps because the callers differ in what they issue in between (``make_flow_input``: the 3-D encoder).  ``side``: a stream for
+        the two encoders; it starts behind the caller's stream here and is joined by the caller."""
+        if self.embed_poke_and_image:
+            poke = torch.cat([poke, x0], dim=1)
+        if side is not None:
+            side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
             poke_emb, *_ = self.poke_embedder.encoder(poke)
+            cond = None
             if self.use_cond:
-                cond, *_ = self.conditioner.encoder(X[:, 0])
+                cond, *_ = self.conditioner.encoder(x0)
                 if self.adapt_cond_ssize:
                     cond = self._adapt_cond(cond)
-        if reverse:
-            spatial = self.first_stage_config["architecture"]["min_spatial_size"]
-            # CPU generator, then moved: torch.randn(...).type_as(X) (:296-300)
-            flow_input = torch.randn((X.size(0), self.config["architecture"]["flow_in_channels"], spatial, spatial)).type_as(X).detach()
-        else:
-            with torch.no_grad():
-                flow_input, *_ = self.encode_first_stage(X)
+        return cond, poke_emb
+
+    def _join_cond(self, cond, poke_emb):
+        return torch.cat([cond, poke_emb], dim=1) if self.use_cond else poke_emb
+
+    def _draw_latent(self, X, pinned=False):
+        """The residual of one sample: CPU generator, then moved -- torch.randn(...).type_as(X) (:296-300), one draw per sample.
+        ``pinned``: through pinned memory without blocking; a pageable copy makes the host wait for the stream to drain."""
+        spatial = self.first_stage_config["architecture"]["min_spatial_size"]
+        z = torch.randn((X.size(0), self.config["architecture"]["flow_in_channels"], spatial, spatial), pin_memory=pinned)
+        return z.to(device=X.device, dtype=X.dtype, non_blocking=True) if pinned else z.type_as(X)
+
+    def make_flow_input(self, batch, reverse=False, use_kp_poke=False):
+        X = batch["images"]
+        poke = self._poke_of(batch, use_kp_poke)
+        self._eval_frozen()
+        with torch.no_grad():
+            parts = self._cond_parts(X[:, 0], poke)
+            if reverse:
+                flow_input = self._draw_latent(X)
+            else:
+                flow_input, *_ = self.encode_first_stage(X)       # its eps draw: after the 2-D encoders, before the augmentation noise
                 if self.augment_input:
                     n_aug = self.config["architecture"]["augment_channels"]
                     noise = torch.randn((flow_input.size(0), n_aug, *flow_input.shape[-2:])).type_as(X)
                     noise = self.scale_augment.to(X.device)[None, :, None, None] * noise + self.shift_augment.to(X.device)[None, :, None, None]
                     flow_input = torch.cat([flow_input, noise], dim=1)
-        cond = torch.cat([cond, poke_emb], dim=1) if self.use_cond else poke_emb
-        return flow_input, cond
+        return flow_input, self._join_cond(*parts)
 
     def _adapt_cond(self, cond):
         """conv_adapt_cond (second_stage_video.py:120-129, 286-287): the conditioner's 4x4 (...) latent brought to the first stage's size."""
-        from . import nn as K
         y = self.conv_adapt_cond.run(K.from_nchw(cond.float(), self.dtype), self.dtype)
         return K.to_nchw(y, self.dtype)
 
+    def _motion_encoder_input(self, X):
+        """The frames the 3-D encoder sees, [B, 3, T', H, W]."""
+        if self.full_seq:
+            X_in = X if self.first_stage_model.full_sequence or self.config["data"]["max_frames"] < 16 else X[:, :-1]
+        else:
+            X_in = X if self.first_stage_model.full_sequence else X[:, 1:]
+        return X_in.transpose(1, 2)
+
     def encode_first_stage(self, X):
         with torch.no_grad():
-            if self.full_seq:
-                X_in = X if self.first_stage_model.full_sequence or self.config["data"]["max_frames"] < 16 else X[:, :-1]
-            else:
-                X_in = X if self.first_stage_model.full_sequence else X[:, 1:]
-            motion, mu, cov = self.first_stage_model.enc_motion(X_in.transpose(1, 2))
+            motion, mu, cov = self.first_stage_model.enc_motion(self._motion_encoder_input(X))
         return motion, mu
+
+    def _cut_augmentation(self, motion):
+        if self.augment_input:
+            motion = motion[:, :-self.config["architecture"]["augment_channels"]].contiguous()
+        return motion
 
     def decode_first_stage(self, motion, X, length=None):
         if length is None:
@@ -275,7 +357,7 @@ class PokeMotionModel(nn.Module):
         else:
             stream.wait_stream(cur)
         with torch.cuda.stream(stream):
-            if getattr(self, "_graph_encoders", False) and not self.augment_input:
+            if self._enc_graphs.enabled and not self.augment_input:
                 flow_input, cond = self._flow_input_graphed(batch)
             else:
                 flow_input, cond = self.make_flow_input(batch)
@@ -285,8 +367,6 @@ class PokeMotionModel(nn.Module):
                 if torch.is_tensor(t_) and t_.is_cuda:
                     t_.record_stream(stream)
         flow_input.record_stream(cur); cond.record_stream(cur)
-        if not isinstance(getattr(self, "_prefetched", None), dict):
-            self._prefetched = {}
         # keyed FIFO: the next batch may be prefetched before this one is consumed (and a loop may feed the same object twice)
         self._prefetched.setdefault(id(batch), []).append((batch, flow_input, cond, ev))
 
@@ -299,67 +379,40 @@ class PokeMotionModel(nn.Module):
         backward pass shrinks from 5.5 to 4.7 ms, but the step is 60.2-61.2 ms against 59.2-59.4 eager -- the forward pass of the next step
         picks up gaps it did not have (IPOKE_ENC_GRAPH=1 turns it on in SecondStageTrainer; bit-identical results either way).  The reparameterisation noise is still drawn on the CPU generator per call, at the same point of the host program as the
         eager path (motion_encoder.py:220), and copied into the graph's input buffer."""
-        self._graph_encoders = bool(enable)
-        self._enc_graphs = {}
+        self._enc_graphs.set(enable)
 
-    def _flow_input_device(self, X, poke, eps, side=None):
+    @property
+    def encoder_graph_enabled(self):
+        return self._enc_graphs.enabled
+
+    def _flow_input_device(self, X, poke, eps, side):
         """Device side of ``make_flow_input`` (reverse = False) with the noise given; ``side``: a stream for the 2-D encoders."""
-        if self.embed_poke_and_image:
-            poke = torch.cat([poke, X[:, 0]], dim=1)
-        cur = torch.cuda.current_stream()
-        if side is not None:
-            side.wait_stream(cur)
-        with torch.cuda.stream(side if side is not None else cur):
-            poke_emb, *_ = self.poke_embedder.encoder(poke)
-            cond = None
-            if self.use_cond:
-                cond, *_ = self.conditioner.encoder(X[:, 0])
-                if self.adapt_cond_ssize:
-                    cond = self._adapt_cond(cond)
-        if self.full_seq:
-            X_in = X if self.first_stage_model.full_sequence or self.config["data"]["max_frames"] < 16 else X[:, :-1]
-        else:
-            X_in = X if self.first_stage_model.full_sequence else X[:, 1:]
-        flow_input, _, _ = self.first_stage_model.enc_motion(X_in.transpose(1, 2), eps=eps)
-        if side is not None:
-            cur.wait_stream(side)
-        cond = torch.cat([cond, poke_emb], dim=1) if self.use_cond else poke_emb
-        return flow_input, cond
+        parts = self._cond_parts(X[:, 0], poke, side=side)
+        flow_input, _, _ = self.first_stage_model.enc_motion(self._motion_encoder_input(X), eps=eps)
+        torch.cuda.current_stream().wait_stream(side)
+        return flow_input, self._join_cond(*parts)
 
     def _flow_input_graphed(self, batch):
-        X = batch["images"]
-        poke = batch[self.poke_key]
-        poke = poke[0] if isinstance(poke, list) else poke
-        key = (tuple(X.shape), tuple(poke.shape), X.dtype, poke.dtype)
-        ent = self._enc_graphs.get(key)
-        if ent is None:                                  # first call of a shape: eager (builds every lazily cached operand)
+        X, poke = batch["images"], self._poke_of(batch)
+        ent = self._enc_graphs.entry(X, poke)
+        if ent["state"] == "absent":
             flow_input, cond = self.make_flow_input(batch)
-            self._enc_graphs[key] = {"state": "warm", "eps_shape": tuple(flow_input.shape)}
+            self._enc_graphs.warmed(ent, eps_shape=tuple(flow_input.shape))
             return flow_input, cond
-        self.first_stage_model.eval(); self.poke_embedder.eval()
-        if self.use_cond:
-            self.conditioner.eval()
+        self._eval_frozen()
         enc = self.first_stage_model.enc_motion
         eps = None if enc.be_determinstic else torch.FloatTensor(*ent["eps_shape"]).normal_()      # CPU generator, motion_encoder.py:220
+        inputs = (X, poke) if eps is None else (X, poke, eps)
         if ent["state"] == "warm":
-            sX, sP = X.clone(), poke.clone()
-            sE = None if eps is None else eps.to(X.device)
-            torch.cuda.synchronize()
-            side = torch.cuda.Stream()
-            g = torch.cuda.CUDAGraph()
-            with torch.no_grad(), torch.cuda.graph(g):
-                out = self._flow_input_device(sX, sP, sE, side=side)
-            ent.update(state="ready", graph=g, X=sX, poke=sP, eps=sE, out=out, side=side)
-        ent["X"].copy_(X, non_blocking=True); ent["poke"].copy_(poke, non_blocking=True)
-        if eps is not None:
-            ent["eps"].copy_(eps, non_blocking=True)
-        ent["graph"].replay()
+            ent["side"] = torch.cuda.Stream()            # the captured second stream lives as long as the graph
+            with torch.no_grad():
+                self._enc_graphs.capture(ent, lambda sX, sP, sE=None: self._flow_input_device(sX, sP, sE, ent["side"]), inputs, X.device)
         # the graph writes into ITS static output buffers: a second replay (a prefetched batch k + 1 while batch k is still queued or in its
         # backward pass) would overwrite them -- hand out copies (ADVICE r4; two small tensors, ordered behind the replay on this stream)
-        return tuple(o.clone() for o in ent["out"])
+        return tuple(o.clone() for o in self._enc_graphs.replay(ent, inputs))
 
     def forward_density(self, batch):
-        queue = (getattr(self, "_prefetched", None) or {}).get(id(batch))
+        queue = self._prefetched.get(id(batch))
         pf = queue.pop(0) if queue else None
         if queue is not None and not queue:
             del self._prefetched[id(batch)]
@@ -372,13 +425,6 @@ class PokeMotionModel(nn.Module):
         return out, logdet
 
     # ---- sampling -------------------------------------------------------------------------------------
-    def _poke_of(self, batch, use_kp_poke=False):
-        if use_kp_poke:
-            poke, *_ = batch["keypoint_poke"]
-            return poke.to(torch.float)
-        poke = batch[self.poke_key]
-        return poke[0] if isinstance(poke, list) else poke
-
     def _sample_device(self, X, poke, z):
         """The device side of one sample of ``forward_sample``: conditioning encoders -> reverse flow -> ConvGRU + SPADE decode.  No host
         synchronisation, no host RNG: this is what ``set_sample_graph`` captures."""
@@ -386,20 +432,8 @@ class PokeMotionModel(nn.Module):
 
     def _sample_motion(self, X, poke, z):
         """First half of ``_sample_device``: conditioning encoders -> reverse flow (the motion latent of the first stage)."""
-        if self.embed_poke_and_image:
-            poke = torch.cat([poke, X[:, 0]], dim=1)
-        poke_emb, *_ = self.poke_embedder.encoder(poke)
-        if self.use_cond:
-            cond, *_ = self.conditioner.encoder(X[:, 0])
-            if self.adapt_cond_ssize:
-                cond = self._adapt_cond(cond)
-            cond = torch.cat([cond, poke_emb], dim=1)
-        else:
-            cond = poke_emb
-        out_motion = self.flow(z, cond, reverse=True)
-        if self.augment_input:
-            out_motion = out_motion[:, :-self.config["architecture"]["augment_channels"]].contiguous()
-        return out_motion
+        cond = self._join_cond(*self._cond_parts(X[:, 0], poke))
+        return self._cut_augmentation(self.flow(z, cond, reverse=True))
 
     def sample_stream(self, batches, n_logged_vids=1, add_first_frame=False, use_keypoint_pokes=False):
         """``forward_sample(batch)[0]`` for every batch of an iterable (the validation / test loops, `second_stage_video.py:490-584`,
@@ -408,13 +442,10 @@ class PokeMotionModel(nn.Module):
         workgroup per sample), the decoder is wide convolutions -- they fill different parts of the chip.  Per batch the same kernels run
         on the same data in the same order as in ``forward_sample`` (bit-identical results, tested); the latent is drawn from the CPU
         generator per batch in the same order.  Yields one CPU tensor per batch, in order, up to two batches late."""
-        self.first_stage_model.eval(); self.poke_embedder.eval()
-        if self.use_cond:
-            self.conditioner.eval()
-        if getattr(self, "_decode_stream", None) is None:
-            from .utils.streams import overlapping_stream
+        self._eval_frozen()
+        if self._decode_stream is None:
             self._decode_stream = overlapping_stream()      # not any new stream: see utils/streams.py
-        side, spatial = self._decode_stream, self.first_stage_config["architecture"]["min_spatial_size"]
+        side = self._decode_stream
 
         # Schedule.  The decode stream never WAITS on the device for the flow: a stream parked in an event wait slows the other queue's
         # dispatch (utils/streams.py: a chain of small launches runs 1.9x slower beside a waiting stream, 3-15x on an unlucky one).
@@ -426,9 +457,7 @@ class PokeMotionModel(nn.Module):
             poke = self._poke_of(batch, use_keypoint_pokes)
             # same CPU generator draw as forward_sample, but through pinned memory: a pageable copy would make the host wait for the
             # stream to drain and give up its lead over the device
-            z = torch.randn((X.size(0), self.config["architecture"]["flow_in_channels"], spatial, spatial), pin_memory=True)
-            z = z.to(device=X.device, dtype=X.dtype, non_blocking=True)
-            motion = self._sample_motion(X, poke, z)
+            motion = self._sample_motion(X, poke, self._draw_latent(X, pinned=True))
             flow_done = torch.cuda.Event(); flow_done.record()
             return X, motion, flow_done
 
@@ -454,19 +483,14 @@ class PokeMotionModel(nn.Module):
             return item[0].clone()            # out of the pinned staging buffer, like ``.cpu()``
 
         flowing, decoding = None, None       # batch whose reverse flow is queued / batch whose decode is queued
-        for batch in batches:
-            nxt = issue_flow(batch)
+        for batch in itertools.chain(batches, [None]):       # None: nothing more to queue, the pipeline drains
+            nxt = issue_flow(batch) if batch is not None else None
             if flowing is not None:
                 out = issue_decode(flowing)
                 if decoding is not None:
                     yield fetch(decoding)
                 decoding = out
             flowing = nxt
-        if flowing is not None:
-            out = issue_decode(flowing)
-            if decoding is not None:
-                yield fetch(decoding)
-            decoding = out
         if decoding is not None:
             yield fetch(decoding)
 
@@ -476,50 +500,50 @@ class PokeMotionModel(nn.Module):
         (models/second_stage_video.py:326-382) -- as ONE captured hipGraph per input shape.  The latent is still drawn on the CPU
         generator per call, like the reference (:296-300), and copied into the graph's input buffer; results are bit-identical to the
         eager path (tests/test_bench_configs_gpu.py)."""
-        self._graph_sampling = bool(enable)
-        self._sample_graphs = {}
+        self._sample_graphs.set(enable)
 
     def _sample_graphed(self, X, poke, z):
-        key = (tuple(X.shape), tuple(poke.shape), X.dtype, poke.dtype)
-        ent = self._sample_graphs.get(key)
-        if ent is None:                                  # first call of a shape: eager (builds every lazily cached operand)
-            self._sample_graphs[key] = {"state": "warm"}
+        ent = self._sample_graphs.entry(X, poke)
+        if ent["state"] == "absent":
+            self._sample_graphs.warmed(ent)
             return self._sample_device(X, poke, z)
         if ent["state"] == "warm":
-            sX, sP, sZ = X.clone(), poke.clone(), z.clone()
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                out = self._sample_device(sX, sP, sZ)
-            ent.update(state="ready", graph=g, X=sX, poke=sP, z=sZ, out=out)
+            self._sample_graphs.capture(ent, self._sample_device, (X, poke, z), X.device)
         if self.flow.engine.shadow_stale:            # a replay skips the eager path's refresh of the flow's weight operands (same addresses)
             self.flow.engine.prepare_weights()
-        ent["X"].copy_(X); ent["poke"].copy_(poke); ent["z"].copy_(z)
-        ent["graph"].replay()
-        return ent["out"]
+        return self._sample_graphs.replay(ent, (X, poke, z))            # the static buffer itself: consumed before the next replay
+
+    def _sample_video(self, X, poke, z):
+        if self._sample_graphs.enabled:
+            return self._sample_graphed(X, poke, z)
+        return self._sample_device(X, poke, z)
+
+    def _sample_videos(self, X, pokes, add_first_frame=False):
+        """The sampling loop: one device video [B, T (+ 1), 3, H, W] per poke of ``pokes``, each from a fresh latent.  The conditioning is
+        recomputed per sample, as the reference's make_flow_input(batch, reverse=True) does (:333).  With the sample graph on, a yielded
+        video is the graph's static buffer: use or copy it before asking for the next.  Runs in the consumer's grad mode (no_grad)."""
+        for poke in pokes:
+            video = self._sample_video(X, poke, self._draw_latent(X))
+            if add_first_frame:
+                video = torch.cat([X[:, 0].unsqueeze(1), video], dim=1)
+            yield video
+
+    @staticmethod
+    def _stack_samples(videos, n):
+        """``n`` videos [B', ...] from ``_sample_videos`` as one device buffer [B', n, ...]."""
+        out = None
+        for i, video in enumerate(videos):
+            if out is None:
+                out = torch.empty((video.shape[0], n) + tuple(video.shape[1:]), dtype=video.dtype, device=video.device)
+            out[:, i].copy_(video)                 # (a graph replay hands out its static buffer: copied before the next replay)
+        return out
 
     def forward_sample(self, batch, n_samples=1, n_logged_vids=1, show_progress=False, add_first_frame=False,
                        use_keypoint_pokes=False):
-        video_samples = []
-        self.first_stage_model.eval(); self.poke_embedder.eval()
-        if self.use_cond:
-            self.conditioner.eval()
+        self._eval_frozen()
         with torch.no_grad():
-            X = batch["images"]
-            poke = self._poke_of(batch, use_keypoint_pokes)
-            spatial = self.first_stage_config["architecture"]["min_spatial_size"]
-            for _ in range(n_samples):
-                # CPU generator, then moved: torch.randn(...).type_as(X) (:296-300); the conditioning is recomputed per sample as
-                # the reference's make_flow_input(batch, reverse=True) does (:333)
-                z = torch.randn((X.size(0), self.config["architecture"]["flow_in_channels"], spatial, spatial)).type_as(X).detach()
-                if getattr(self, "_graph_sampling", False):
-                    out_video = self._sample_graphed(X, poke, z)
-                else:
-                    out_video = self._sample_device(X, poke, z)
-                if add_first_frame:
-                    out_video = torch.cat([X[:, 0].unsqueeze(1), out_video], dim=1)
-                video_samples.append(out_video[:n_logged_vids].cpu())
-        return video_samples
+            pokes = [self._poke_of(batch, use_keypoint_pokes)] * n_samples
+            return [video[:n_logged_vids].cpu() for video in self._sample_videos(batch["images"], pokes, add_first_frame)]
 
     def training_step(self, batch, batch_idx):
         out, logdet = self.forward_density(batch)
@@ -534,7 +558,6 @@ class PokeMotionModel(nn.Module):
     def attach_fvd(self, i3d=None, dtype="f32"):
         """The reference builds ``self.FVD = FVD(n_samples=...)`` with the Kinetics I3D weights in __init__ (:66); here the metric
         is attached explicitly (the I3D checkpoint is not part of the second-stage checkpoint)."""
-        from .fvd import FVD
         self.FVD = FVD(n_samples=self.config["logging"]["n_fvd_samples"], i3d=i3d, dtype=dtype)
         self._fvd_fake, self._fvd_true, self._fvd_fake_x0, self._fvd_true_x0 = [], [], [], []
         return self.FVD
@@ -552,12 +575,11 @@ class PokeMotionModel(nn.Module):
         # I3D is attached; only the clip lists kept for the epoch's FVD need the FVD object
         if batch_id <= int(self.config["logging"]["n_fvd_samples"] / X.size(0)):
             X_hat = self.forward_sample(batch, n_logged_vids=X.size(0))[0].to(X.device)
-            if getattr(self, "FVD", None) is not None:
+            if self.FVD is not None:
                 self._fvd_fake.append(X_hat)
                 self._fvd_true.append(X[:, 1:])
                 self._fvd_fake_x0.append(torch.cat([X[:, 0].unsqueeze(1), X_hat], dim=1))
                 self._fvd_true_x0.append(X)
-            from . import metrics
             X_hat_log = X_hat.reshape(-1, *X_hat.shape[2:]).type_as(X)
             X_log = X[:, 1:].reshape(-1, *X_hat.shape[2:])
             both = metrics.psnr_ssim(X_hat_log, X_log)
@@ -568,7 +590,6 @@ class PokeMotionModel(nn.Module):
         return {"loss": loss, "batch_idx": batch_id, "loss_dict": loss_dict}
 
     def validation_epoch_end(self, outputs=None):
-        from .fvd import calculate_FVD
         bs = self.first_stage_config["logging"]["bs_i3d"]
         fvd_score = calculate_FVD(self.FVD.i3d, torch.cat(self._fvd_fake), torch.cat(self._fvd_true), batch_size=bs)
         self.log("FVD-val", fvd_score)
@@ -596,43 +617,16 @@ class PokeMotionModel(nn.Module):
         # host addresses, which is an illegal memory access on the device, reported at some later call
         if self.device_.type != "cuda":
             raise RuntimeError(f"ipoke_amd has no CPU path: the model must be on the GPU (it was built on {self.device_})")
-        self.first_stage_model.eval(); self.poke_embedder.eval()
-        if self.use_cond:
-            self.conditioner.eval()
-        out = None
+        self._eval_frozen()
         with torch.no_grad():
-            X = batch["images"]
-            poke = self._poke_of(batch, use_keypoint_pokes)
-            spatial = self.first_stage_config["architecture"]["min_spatial_size"]
-            for i in range(n_samples):
-                z = torch.randn((X.size(0), self.config["architecture"]["flow_in_channels"], spatial, spatial)).type_as(X).detach()
-                if getattr(self, "_graph_sampling", False):
-                    video = self._sample_graphed(X, poke, z)
-                else:
-                    video = self._sample_device(X, poke, z)
-                if add_first_frame:
-                    video = torch.cat([X[:, 0].unsqueeze(1), video], dim=1)
-                video = video[:n_logged_vids]
-                if out is None:
-                    out = torch.empty((video.shape[0], n_samples) + tuple(video.shape[1:]), dtype=video.dtype, device=video.device)
-                out[:, i].copy_(video)                 # (a graph replay hands out its static buffer: copied before the next replay)
-        return out
+            pokes = [self._poke_of(batch, use_keypoint_pokes)] * n_samples
+            videos = self._sample_videos(batch["images"], pokes, add_first_frame)
+            return self._stack_samples((video[:n_logged_vids] for video in videos), n_samples)
 
     # ---- applications (second_stage_video.py:786-852, 948-1015): the tensors; writing mp4 / png files is left to the caller ------------
-    def _sample_video(self, X, poke, z):
-        if getattr(self, "_graph_sampling", False):
-            return self._sample_graphed(X, poke, z)
-        return self._sample_device(X, poke, z)
-
-    def _cut_augmentation(self, motion):
-        if self.augment_input:
-            motion = motion[:, :-self.config["architecture"]["augment_channels"]].contiguous()
-        return motion
-
     def poke_simulator(self):
         """The ``PokeSimulator`` of ``config['data']`` (the reference reads ``poke_size`` from its test data set, :794, :951)."""
-        if getattr(self, "_poke_simulator", None) is None:
-            from .data import PokeSimulator
+        if self._poke_simulator is None:
             self._poke_simulator = PokeSimulator(self.config["data"])
         return self._poke_simulator
 
@@ -648,7 +642,6 @@ class PokeMotionModel(nn.Module):
         uses.  The random residual is ``torch.randn(r1.shape).type_as(r1)`` from the CPU generator, drawn after the forward pass -- the
         convention of ``forward_sample``; the reference's ``randn_like`` on the device is not reproducible across devices.  With
         ``augmented_input`` the noise channels are cut off before decoding, as in sampling."""
-        from . import _lib
         _lib.require_gpu()
         if not self.embed_poke_and_image:
             # :975-981: poke1_src2 is only assigned under `if self.embed_poke_and_image` and read unconditionally
@@ -660,14 +653,7 @@ class PokeMotionModel(nn.Module):
             X_2 = batch["nn"][0]
             poke1 = self._poke_of(batch)
             z_1, cond_1 = self.make_flow_input(batch)
-            poke_emb_1, *_ = self.poke_embedder.encoder(torch.cat([poke1, X_2[:, 0]], dim=1))
-            if self.use_cond:
-                cond_2, *_ = self.conditioner.encoder(X_2[:, 0])
-                if self.adapt_cond_ssize:
-                    cond_2 = self._adapt_cond(cond_2)
-                cond_2 = torch.cat([cond_2, poke_emb_1], dim=1)
-            else:
-                cond_2 = poke_emb_1
+            cond_2 = self._join_cond(*self._cond_parts(X_2[:, 0], poke1))
             r1, _ = self.flow(z_1, cond_1, reverse=False)
             z_r1_cond2 = self.flow(r1, cond_2, reverse=True)
             residual_sample = torch.randn(r1.shape).type_as(r1)
@@ -686,7 +672,6 @@ class PokeMotionModel(nn.Module):
         device; sample k is ``forward_sample`` of the batch with ``batch['poke'] = pokes[k]``.  Draw order: the uniforms, then one latent
         per poke (CPU generator).  ``batch`` is not modified (the reference overwrites ``batch['poke']``); samples without a candidate pixel
         raise ``FlowError`` before anything is sampled."""
-        from . import _lib
         _lib.require_gpu()
         n = int(self.config["testing"]["n_control_sensitivity_pokes"] if n_pokes is None else n_pokes)
         self.eval()
@@ -695,28 +680,18 @@ class PokeMotionModel(nn.Module):
             poke0, centers = batch["poke"]
             randomized, picked, status = self.poke_simulator().randomize_pokes(batch["flow"], centers, n, u=u, strict=True)
             pokes = torch.cat([poke0.float()[None], randomized])
-            spatial = self.first_stage_config["architecture"]["min_spatial_size"]
-            samples = None
-            step = dict(batch)
-            for k in range(n + 1):
-                step["poke"] = pokes[k]
-                z = torch.randn((X.size(0), self.config["architecture"]["flow_in_channels"], spatial, spatial)).type_as(X).detach()
-                video = self._sample_video(X, self._poke_of(step), z)
-                if samples is None:
-                    samples = torch.empty((video.shape[0], n + 1) + tuple(video.shape[1:]), dtype=video.dtype, device=video.device)
-                samples[:, k].copy_(video)                 # (a graph replay hands out its static buffer: copied before the next replay)
+            per_sample = (self._poke_of({**batch, "poke": pokes[k]}) for k in range(n + 1))
+            samples = self._stack_samples(self._sample_videos(X, per_sample), n + 1)
         return pokes, samples, picked, status
 
     def attach_metric_vgg(self, vgg=None, dtype="f32"):
         """The reference builds ``self.vggm = metric_vgg16()`` with torchvision's ImageNet weights (:155); here the extractor is attached
         explicitly (``ipoke_amd.vgg.metric_vgg16`` + ``load_torchvision_features``)."""
-        from .vgg import metric_vgg16
         self.vggm = (metric_vgg16(dtype=dtype) if vgg is None else vgg).to(self.device_)
         return self.vggm
 
     def _test(self):
         if self._test_state is None:
-            from . import metrics
             self._test_state = {"real_u8": [], "fake_u8": [], "real": [], "fake": [], "ssim": metrics.SSIM_custom(), "psnr": metrics.PSNR_custom(),
                                 "sample_ssim": metrics.SampleSSIM(self.n_test_samples)}
         return self._test_state
@@ -724,16 +699,15 @@ class PokeMotionModel(nn.Module):
     def _test_batch_size(self, X):
         return self.config["testing"].get("test_batch_size", X.size(0))
 
-    def _test_step_fvd(self, batch):
+    def _test_step_fvd(self, batch, batch_id):
         """:665-678 -- one sample per clip; uint8 [B, T, H, W, 3] real and generated-with-x0 clips (converted on the device)."""
-        from . import metrics
         st = self._test()
         X = batch["images"]
         sample = self.sample_videos_device(batch, 1, n_logged_vids=X.size(0))[:, 0]
         gen = torch.cat([X[:, 0].unsqueeze(1), sample.type_as(X)], dim=1)
         st["real_u8"].append(metrics.video_to_uint8(X))
         st["fake_u8"].append(metrics.video_to_uint8(gen))
-        if getattr(self, "FVD", None) is not None:
+        if self.FVD is not None:
             st["real"].append(X); st["fake"].append(gen)
 
     def _test_step_metrics(self, batch, batch_id):
@@ -750,14 +724,9 @@ class PokeMotionModel(nn.Module):
         target_act = target_vid.reshape(-1, *target_vid.shape[3:])
         for n_sample in range(samples.shape[1]):
             samples_act = samples[:, n_sample, 1:].reshape(-1, *samples.shape[3:]).type_as(target_vid)
-            both = self._psnr_ssim(samples_act, target_act)
+            both = metrics.psnr_ssim(samples_act, target_act)
             st["ssim"].update_value(both[1]); st["psnr"].update_value(both[0])
         st["sample_ssim"].update(samples[:, :, 1:], target_vid)
-
-    @staticmethod
-    def _psnr_ssim(a, b):
-        from . import metrics
-        return metrics.psnr_ssim(a, b)
 
     def _test_step_diversity(self, batch, batch_id):
         """:746-752 -- the samples stay on the device."""
@@ -767,75 +736,76 @@ class PokeMotionModel(nn.Module):
             raise NotImplementedError("testing.lpips: the LPIPS diversity term needs the lpips package's pretrained network, which is not available")
         return self.sample_videos_device(batch, self.n_test_samples, n_logged_vids=self._test_batch_size(batch["images"]))
 
+    def _n_pokes(self):
+        return self.config["testing"].get("n_pokes", self.config.get("data", {}).get("n_pokes", 1))
+
+    def _test_end_fvd(self, st, outputs):
+        savedir = os.path.join(self.dirs["generated"], "samples_fvd")
+        os.makedirs(savedir, exist_ok=True)
+        # np.stack over the per-batch arrays, as :1071-1072: [n_batches, B, T, H, W, 3] (the mp4 examples of :1075-1084 are not written)
+        real_samples = torch.stack(st["real_u8"], dim=0).cpu().numpy()
+        fake_samples = torch.stack(st["fake_u8"], dim=0).cpu().numpy()
+        np.save(os.path.join(savedir, "real_samples.npy"), real_samples)
+        np.save(os.path.join(savedir, "fake_samples.npy"), fake_samples)
+        score = None
+        if self.FVD is not None:
+            score = calculate_FVD(self.FVD.i3d, torch.cat(st["fake"]), torch.cat(st["real"]), batch_size=self.first_stage_config["logging"]["bs_i3d"])
+            self.log("FVD-test-x0", score)
+        for k in ("real_u8", "fake_u8", "real", "fake"):
+            st[k].clear()
+        return score
+
+    def _test_end_metrics(self, st, outputs):
+        n_pokes = self._n_pokes()
+        ssim_normal = st["ssim"].compute().cpu().numpy()
+        self.metrics_dict["SSIM"] = ssim_normal
+        self.metrics_dict["PSNR"] = st["psnr"].compute().cpu().numpy()
+        ssim_nn, ssim_dict = st["sample_ssim"].compute(n_pokes=n_pokes)
+        self.metrics_dict["SSIM NN"] = ssim_dict
+        self.log("ssim-test", ssim_normal); self.log("ssim-nn-test", ssim_nn)
+        st["sample_ssim"].reset(); st["ssim"].reset(); st["psnr"].reset()
+        return ssim_normal
+
+    def _test_end_diversity(self, st, outputs):
+        if self.vggm is None:
+            raise RuntimeError("test mode 'diversity' needs the VGG-16 feature extractor: call attach_metric_vgg() first")
+        n_pokes = self._n_pokes()
+        exmpls = torch.cat(outputs, dim=0)
+        div_score = metrics.compute_div_score(exmpls, self.vggm, device=self.device_)
+        div_score_mse = metrics.compute_div_score_mse(exmpls, device=self.device_)
+        self.div_scores.append(div_score)
+        savepath = os.path.join(self.dirs["generated"], "diversity")
+        metrics_dir = os.path.join(self.dirs["generated"], "metrics")
+        os.makedirs(savepath, exist_ok=True); os.makedirs(metrics_dir, exist_ok=True)
+        # the reference's line (:1145); its third term needs the lpips package and is reported as not computed
+        text = f"Similarity measure_vgg: {div_score}; similarity measure mse: {div_score_mse}; similarity measure lpips: {None}\n"
+        np.save(os.path.join(savepath, f"samples_diversity_{n_pokes}_pokes.npy"), exmpls.cpu().numpy())
+        with open(os.path.join(metrics_dir, "divscore.txt"), "a+") as f:
+            f.writelines(text)
+        return div_score
+
+    # test mode -> (test_step, test_epoch_end)
+    _TEST_MODES = {"fvd": (_test_step_fvd, _test_end_fvd), "accuracy": (_test_step_metrics, _test_end_metrics),
+                   "diversity": (_test_step_diversity, _test_end_diversity)}
+
+    def _test_mode_fns(self):
+        if self.test_mode in self._TEST_MODES_MISSING:
+            raise NotImplementedError(f"test mode '{self.test_mode}': {self._TEST_MODES_MISSING[self.test_mode]}")
+        if self.test_mode not in self._TEST_MODES:
+            raise ValueError(f'The specified test_mode is "{self.test_mode}", which is invalid...')
+        return self._TEST_MODES[self.test_mode]
+
     def test_step(self, batch, batch_id):
         self.eval()
         with torch.no_grad():
-            if self.test_mode == "fvd":
-                self._test_step_fvd(batch)
-            elif self.test_mode == "accuracy":
-                self._test_step_metrics(batch, batch_id)
-            elif self.test_mode in self._TEST_MODES_MISSING:
-                raise NotImplementedError(f"test mode '{self.test_mode}': {self._TEST_MODES_MISSING[self.test_mode]}")
-            elif self.test_mode == "diversity":
-                return self._test_step_diversity(batch, batch_id)
-            else:
-                raise ValueError(f'The specified test_mode is "{self.test_mode}", which is invalid...')
+            return self._test_mode_fns()[0](self, batch, batch_id)
 
     def test_step_end(self, out_step):
         return out_step
 
-    def _n_pokes(self):
-        return self.config["testing"].get("n_pokes", self.config.get("data", {}).get("n_pokes", 1))
-
     def test_epoch_end(self, outputs=None):
         st = self._test()
-        if self.test_mode == "fvd":
-            savedir = os.path.join(self.dirs["generated"], "samples_fvd")
-            os.makedirs(savedir, exist_ok=True)
-            # np.stack over the per-batch arrays, as :1071-1072: [n_batches, B, T, H, W, 3] (the mp4 examples of :1075-1084 are not written)
-            real_samples = torch.stack(st["real_u8"], dim=0).cpu().numpy()
-            fake_samples = torch.stack(st["fake_u8"], dim=0).cpu().numpy()
-            np.save(os.path.join(savedir, "real_samples.npy"), real_samples)
-            np.save(os.path.join(savedir, "fake_samples.npy"), fake_samples)
-            score = None
-            if getattr(self, "FVD", None) is not None:
-                from .fvd import calculate_FVD
-                score = calculate_FVD(self.FVD.i3d, torch.cat(st["fake"]), torch.cat(st["real"]), batch_size=self.first_stage_config["logging"]["bs_i3d"])
-                self.log("FVD-test-x0", score)
-            for k in ("real_u8", "fake_u8", "real", "fake"):
-                st[k].clear()
-            return score
-        if self.test_mode == "accuracy":
-            n_pokes = self._n_pokes()
-            ssim_normal = st["ssim"].compute().cpu().numpy()
-            self.metrics_dict["SSIM"] = ssim_normal
-            self.metrics_dict["PSNR"] = st["psnr"].compute().cpu().numpy()
-            ssim_nn, ssim_dict = st["sample_ssim"].compute(n_pokes=n_pokes)
-            self.metrics_dict["SSIM NN"] = ssim_dict
-            self.log("ssim-test", ssim_normal); self.log("ssim-nn-test", ssim_nn)
-            st["sample_ssim"].reset(); st["ssim"].reset(); st["psnr"].reset()
-            return ssim_normal
-        if self.test_mode == "diversity":
-            from . import metrics
-            if self.vggm is None:
-                raise RuntimeError("test mode 'diversity' needs the VGG-16 feature extractor: call attach_metric_vgg() first")
-            n_pokes = self._n_pokes()
-            exmpls = torch.cat(outputs, dim=0)
-            div_score = metrics.compute_div_score(exmpls, self.vggm, device=self.device_)
-            div_score_mse = metrics.compute_div_score_mse(exmpls, device=self.device_)
-            self.div_scores.append(div_score)
-            savepath = os.path.join(self.dirs["generated"], "diversity")
-            metrics_dir = os.path.join(self.dirs["generated"], "metrics")
-            os.makedirs(savepath, exist_ok=True); os.makedirs(metrics_dir, exist_ok=True)
-            # the reference's line (:1145); its third term needs the lpips package and is reported as not computed
-            text = f"Similarity measure_vgg: {div_score}; similarity measure mse: {div_score_mse}; similarity measure lpips: {None}\n"
-            np.save(os.path.join(savepath, f"samples_diversity_{n_pokes}_pokes.npy"), exmpls.cpu().numpy())
-            with open(os.path.join(metrics_dir, "divscore.txt"), "a+") as f:
-                f.writelines(text)
-            return div_score
-        if self.test_mode in self._TEST_MODES_MISSING:
-            raise NotImplementedError(f"test mode '{self.test_mode}': {self._TEST_MODES_MISSING[self.test_mode]}")
-        raise ValueError(f'The specified test_mode is "{self.test_mode}", which is invalid...')
+        return self._test_mode_fns()[1](self, st, outputs)
 
     def configure_optimizers(self):
         tr = self.config["training"]

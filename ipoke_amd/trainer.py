@@ -194,7 +194,7 @@ class SecondStageTrainer:
                     worker()
             if prefetch:
                 after = fwd_done
-                if getattr(m, "_graph_encoders", False):
+                if m.encoder_graph_enabled:
                     # a graph replay is ONE host call: the host, several ms ahead of the GPU here, would start it in the middle of the
                     # backward pass; the event holds it until the chain (and the ready stream's last slice) is done
                     after = torch.cuda.Event()

@@ -138,6 +138,76 @@ def test_encoder_prefetch_does_not_change_training(enc_graph, monkeypatch):
     assert (p0 - p1).abs().max().item() <= 2e-5 * p0.abs().max().item()
 
 
+def test_state_dict_load_drops_the_captured_graphs():
+    """Load after capture.  The captured graphs of ``set_sample_graph`` / ``set_encoder_graph`` hold the addresses of weight operands that a
+    state-dict load drops: ``load_state_dict`` empties both caches, and the next uses recapture on the NEW weights -- bit for bit the
+    eager results under the same seed, and different from the results before the load.  The smoke-size model, f32, B = 2.  The
+    encoder graph is driven as the trainer drives it: two prefetches of one batch object queued before either is consumed, popped in
+    order."""
+    from tests.helpers import synthetic_batch
+    m = _glue_model("f32")
+    batch = synthetic_batch(2, 16, 64, device="cuda")
+    side = torch.cuda.Stream()
+    with torch.no_grad():
+        m.forward_density(batch)                                           # the flow's data-dependent initialisation, once
+
+    def sample():
+        torch.manual_seed(7)
+        return m.forward_sample(batch, n_samples=1, n_logged_vids=2)[0]
+
+    def flow_inputs(prefetched):
+        """Two consecutive flow inputs of the batch under one seed: from make_flow_input, or through the prefetch FIFO."""
+        torch.manual_seed(11)
+        if not prefetched:
+            return [m.make_flow_input(batch) for _ in range(2)], None
+        m.prefetch_flow_input(batch, side)
+        m.prefetch_flow_input(batch, side)
+        queued = [(fi, cond) for _, fi, cond, _ in m._prefetched[id(batch)]]
+        with torch.no_grad():
+            outs = [m.forward_density(batch) for _ in range(2)]
+        assert not m._prefetched
+        torch.cuda.synchronize()
+        return queued, outs
+
+    def ready(cache):
+        return any(e.get("state") == "ready" for e in cache.values())
+
+    def same(a, b):
+        return all(torch.equal(x, y) for p, q in zip(a, b) for x, y in zip(p, q))
+
+    m.set_sample_graph(True)
+    before = [sample() for _ in range(3)]                                  # eager, capture + replay, replay
+    assert ready(m._sample_graphs) and torch.equal(before[0], before[1]) and torch.equal(before[0], before[2])
+    m.set_encoder_graph(True)
+    enc_before = [flow_inputs(True)[0] for _ in range(2)][1]               # eager + capture, then two replays
+    assert ready(m._enc_graphs)
+
+    g = torch.Generator().manual_seed(3)
+    sd = {k: v.clone() for k, v in m.state_dict().items()}
+    moved = [k for k, v in sd.items() if k.startswith(("first_stage_model.gen.", "first_stage_model.enc_motion.")) and v.is_floating_point()]
+    assert any(".gen." in k for k in moved) and any(".enc_motion." in k for k in moved)
+    for k in moved:                                                        # the decoder (and, for the encoder graph, the motion encoder)
+        sd[k] += 0.05 * torch.randn(sd[k].shape, generator=g).to(sd[k])
+    m.load_state_dict(sd)
+    assert not m._sample_graphs and not m._enc_graphs
+
+    sample()
+    graphed = sample()                                                     # eager again, then recaptured
+    assert ready(m._sample_graphs)
+    queued, outs = [flow_inputs(True) for _ in range(2)][1]
+    assert ready(m._enc_graphs)
+    m.set_sample_graph(False)
+    m.set_encoder_graph(False)
+    assert torch.equal(graphed, sample())
+    assert not torch.equal(graphed, before[0])
+    eager, _ = flow_inputs(False)
+    assert not same(eager[:1], eager[1:]), "the two draws differ, so the order of the FIFO shows"
+    assert same(queued, eager)
+    with torch.no_grad():
+        assert same(outs, [m.flow(fi.detach(), cond, reverse=False) for fi, cond in eager])
+    assert not same(queued, enc_before)
+
+
 def test_lightning_checkpoint_loads_and_reproduces_the_oracle(tmp_path):
     """f4: a Lightning-layout ``.ckpt`` written from the oracle's modules (reference state-dict keys: ``flow.flow.*`` with
     weight_g / weight_v, int64 shuffle indices, uint8 ``initialized`` flags; ``first_stage_model.*`` with spectral-norm

@@ -22,6 +22,7 @@
 #ifndef IPOKE_HIP_H
 #define IPOKE_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -932,6 +933,12 @@ int ipoke_sample_ssim(const float* pred, const float* target, int bs, int ns, in
  * mean = mean over the samples; index[bs] = the chosen sample.  The per-sample means are formed and compared in double (the reference's
  * torch.argmin sees fp32 means): samples whose means differ by less than an fp32 rounding may resolve to the other index of the two. */
 int ipoke_sample_stats(const float* vals, int bs, int ns, int s, float* nn, float* sd, float* mean, int* index, void* stream);
+/* utils/metrics.py:259-331 (KPSMetric.update, :294 and :299): out fp32 [bs][ns][s] = the mean over the K * 2 coordinates of
+ * (pred - target)^2 for pred fp32 [bs][ns][s][K][2] against target fp32 [bs][1][s][K][2], which is read in place for every sample.  fp32
+ * arithmetic, the 2 K terms added in index order, one division at the end: integer operands whose sums stay below 2^24 give the exactly
+ * rounded mean.  ipoke_sample_stats on the result gives the rest of the update (:296-302: the arg-min-mean sample's values, the unbiased
+ * std and the mean over the samples). */
+int ipoke_kps_frame_mse(const float* pred, const float* target, int bs, int ns, int s, int K, float* out, void* stream);
 /* utils/metrics.py:104-124 (compute_div_score_mse): D fp32 [n_ex][ns][ns], D[e][j][k] = mean((v_j - v_k)^2) over the L elements of the
  * videos x fp32 [n_ex][ns][L]; each element is read once per example, all ns (ns - 1) / 2 sums are formed together in double.
  * 2 <= ns <= 64.  workspace: ipoke_pair_mse_workspace_bytes(n_ex, ns, L) bytes. */
@@ -1016,6 +1023,42 @@ int ipoke_poke_stamp(const int64_t* centers, const float* values, const float* f
 int64_t ipoke_poke_randomize_workspace_bytes(int B, int H, int W, int n_s);
 int ipoke_poke_randomize(const float* flow, const int64_t* centers, const float* u, int B, int H, int W, int n_c, int n_s, int half,
                          float* pokes, int64_t* picked, int* status, void* workspace, void* stream);
+/* _get_keypoint_poke (data/base_dataset.py:462-497; the loop at :479-487) for a batch: the poke stamped from the displacement of chosen
+ * keypoints between the first and the last frame of a clip.  kp_src, kp_tgt double [B][K][2] as (x, y), relative to the frame
+ * (datadict['keypoints_rel'][start_id] and [end_id], :467-468); poke_ids int32 [B][n_max], the chosen keypoints in drawing order, padded
+ * with -1.  With (H, W) = spatial_size, per poke (:480-481):
+ *   col = (int)(x * H)   row = (int)(y * W)      -- spatial_size[0] for x and [1] for y, as the reference has them; the products are formed
+ *                                                   in double and truncated toward zero, which is why the keypoints are double here: an
+ *                                                   fp32 product lands on the other side of an integer at a boundary;
+ *   if w_lo <= col <= w_hi and h_lo <= row <= h_hi (:482, both ends inclusive; valid_w / valid_h of :185-186):
+ *       poke[b][:][row - half : row + half + 1][col - half : col + half + 1] = (tgt - src) * H        (:483-485)
+ *     under the slice rules of ipoke_poke_stamp.  BOTH channels are scaled by spatial_size[0]: the reference's own asymmetry, kept; the
+ *     value is formed in double and rounded to fp32 once (the reference's poke is a float64 array);
+ *   coords[b][j] = (row, col) whether or not the square was drawn (:487).
+ * Later pokes overwrite earlier ones, in the order of poke_ids.  Outputs: poke fp32 [B][2][H][W], every element written; coords int32
+ * [B][n_max][2], -1 for padding entries (:492).  An id >= K is treated as padding (the Python side raises).  No atomics. */
+int ipoke_keypoint_poke(const double* kp_src, const double* kp_tgt, const int32_t* poke_ids, int B, int K, int n_max, int H, int W, int half,
+                        int h_lo, int h_hi, int w_lo, int w_hi, float* poke, int32_t* coords, void* stream);
+/* get_nn (data/flow_dataset.py:628-713; its `measure` at :635-646): posture nearest neighbours.  kps fp32 [N][K][2] (keypoints_rel), vid
+ * int32 [N] (dense video codes), ids int64 [M] the query frames (device memory; NULL: the frames 0 .. M-1, M == N for all of them).
+ *   D(i, j) = sum_k || kps[i][k] - kps[j][k] ||_2                      (:638: np.linalg.norm(kps[idx][None] - kps, axis=-1).sum(-1))
+ * Candidates are ordered by (D, j) lexicographically -- a stable argsort; the reference's default argsort is unstable, so ties are only
+ * defined here.
+ *   nn_general[m]   = the SECOND entry of that order over all j, the query included (:642 sorted_ids[1]).  A duplicate of the query with
+ *                     a lower index therefore makes the query its own answer, as a stable sort would have it.
+ *   nn_other_vid[m] = the first entry with vid[j] != vid[ids[m]] (:639-641), -1 where no frame of another video exists (the reference
+ *                     dies there with an IndexError; the Python side raises ValueError).
+ *   dist (optional) fp32 [M][2] = the distances of the two answers (+inf beside a -1).
+ * fp32 arithmetic: every difference, product, the fused dy * dy + dx * dx, the correctly rounded square root and every sum is one rounded
+ * operation, the K terms added in index order.  The grid is query blocks x candidate chunks (ipoke_posture_nn_grid in ipoke_hip_dev.h);
+ * each workgroup writes its two smallest (D, j) and its smallest (D, j) of another video per query into the workspace and a second launch
+ * merges the chunks in ascending order: no atomics, bit-identical run to run.  1 <= K <= 64, N >= 2.  An id outside [0, N) cannot be seen
+ * from the host here (ids is device memory): it reads nothing and answers -1, -1; the Python wrapper validates ids on the host and raises.
+ * Non-finite keypoints are outside the contract.  workspace: ipoke_posture_nn_workspace_bytes(N, K, M) bytes (0 for an unsupported
+ * shape), 24 bytes per (chunk, query). */
+size_t ipoke_posture_nn_workspace_bytes(int N, int K, int M);
+int ipoke_posture_nn(const float* kps, const int32_t* vid, const int64_t* ids, int N, int K, int M, int64_t* nn_general,
+                     int64_t* nn_other_vid, float* dist, void* ws, void* stream);
 /* Clip augmentation (data/base_dataset.py:695-722 _get_color_transforms / _get_geometric_transforms, applied per frame at :432-440 and to
  * the flow at :683-691): brightness -> contrast -> hue -> saturation on uint8 values, then pad(S/2, reflect) -> affine(angle, translate,
  * nearest neighbour, fill 0) -> center_crop(S), bit-equal to what torchvision's PIL backend computes through Pillow.  One sample's parameters

@@ -32,6 +32,10 @@ enum { IPOKE_WGRAD_KERNEL_NONE = 0, IPOKE_WGRAD_KERNEL_TN = 1, IPOKE_WGRAD_KERNE
        IPOKE_WGRAD_KERNEL_LAT8 = 4, IPOKE_WGRAD_KERNEL_HALO = 5 };
 int ipoke_last_wgrad_kernel(void);
 
+/* Test hook: the launch grid of ipoke_posture_nn for (N, K, M): out[0..3] = query blocks, candidate chunks, candidates per chunk (a whole
+ * number of tiles; the last chunk may be shorter and end in a ragged tile), candidates per LDS tile. */
+int ipoke_posture_nn_grid(int N, int K, int M, int* out);
+
 /* developer probe: one wave spinning for about `us` microseconds on `stream` */
 int ipoke_spin_delay(int us, void* stream);
 

@@ -292,6 +292,7 @@ SIGNATURES = {
     "ipoke_sample_ssim_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "ipoke_sample_ssim": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "ipoke_sample_stats": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    "ipoke_kps_frame_mse": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "ipoke_pair_mse_workspace_bytes": (c_int64, [c_int, c_int, c_int64]),
     "ipoke_pair_mse": (c_int, [_P, c_int, c_int, c_int64, _P, _P, _P]),
     "ipoke_time_cosine_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int64]),
@@ -311,6 +312,10 @@ SIGNATURES = {
     "ipoke_aug_frame_means": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
     "ipoke_aug_frames": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P]),
     "ipoke_aug_flow": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
+    "ipoke_keypoint_poke": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "ipoke_posture_nn_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
+    "ipoke_posture_nn": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    "ipoke_posture_nn_grid": (c_int, [c_int, c_int, c_int, POINTER(c_int32)]),
     "ipoke_timing_start": (c_int, []),
     "ipoke_timing_start_all": (c_int, []),
     "ipoke_timing_stop": (c_int, [POINTER(c_int), c_int, POINTER(c_int), POINTER(ctypes.c_double)]),

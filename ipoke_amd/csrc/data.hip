@@ -634,6 +634,64 @@ extern "C" int ipoke_poke_randomize(const float* flow, const int64_t* centers, c
   return IPOKE_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- _get_keypoint_poke
+// data/base_dataset.py:462-497, the loop at :479-487 for a batch: poke j of sample b is keypoint id = poke_ids[b][j] (< 0: padding),
+// col = (int)(x * H), row = (int)(y * W) of its source position -- the products in double, truncated toward zero, spatial_size[0] for x
+// and [1] for y as the reference has them --, drawn only inside the valid window (both ends inclusive) as the slice assignment of :484-485
+// with the value (tgt - src) * H for BOTH channels (the reference's own asymmetry: spatial_size[0] scales x and y alike), formed in double
+// and rounded to fp32 once.  A pixel takes the LAST poke that covers it; the coordinates are recorded whether or not the square was drawn.
+struct KpPoke { bool drawn; int row, col; };
+__device__ __forceinline__ KpPoke keypoint_poke_of(const double* __restrict__ kp_src, const int* __restrict__ poke_ids, int b, int j, int K, int n_max,
+                                                   int H, int W, int h_lo, int h_hi, int w_lo, int w_hi, int* id_out) {
+  KpPoke p;
+  const int id = poke_ids[(long)b * n_max + j];
+  p.drawn = false; p.row = p.col = -1;
+  *id_out = id;
+  if (id < 0 || id >= K) return p;                  // padding (or an id the host side would have refused): no poke, coordinates -1
+  const double* s = kp_src + ((long)b * K + id) * 2;
+  p.row = (int)(s[1] * (double)W);
+  p.col = (int)(s[0] * (double)H);
+  p.drawn = p.col >= w_lo && p.col <= w_hi && p.row >= h_lo && p.row <= h_hi;
+  return p;
+}
+
+__global__ void keypoint_poke_kernel(const double* __restrict__ kp_src, const double* __restrict__ kp_tgt, const int* __restrict__ poke_ids, int B, int K,
+                                     int n_max, int H, int W, int half, int h_lo, int h_hi, int w_lo, int w_hi, float* __restrict__ poke,
+                                     int* __restrict__ coords) {
+  const long HW = (long)H * W, total = (long)B * HW, stride = (long)gridDim.x * blockDim.x, first = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (long i = first; i < (long)B * n_max; i += stride) {
+    int id;
+    const KpPoke p = keypoint_poke_of(kp_src, poke_ids, (int)(i / n_max), (int)(i % n_max), K, n_max, H, W, h_lo, h_hi, w_lo, w_hi, &id);
+    coords[2 * i] = p.row; coords[2 * i + 1] = p.col;
+  }
+  for (long i = first; i < total; i += stride) {
+    const int x = (int)(i % W); long t = i / W;
+    const int y = (int)(t % H); const int b = (int)(t / H);
+    float v0 = 0.f, v1 = 0.f;
+    for (int j = n_max - 1; j >= 0; --j) {
+      int id;
+      const KpPoke p = keypoint_poke_of(kp_src, poke_ids, b, j, K, n_max, H, W, h_lo, h_hi, w_lo, w_hi, &id);
+      if (!p.drawn || !square_covers(p.row, p.col, half, H, W, y, x)) continue;
+      const double* s = kp_src + ((long)b * K + id) * 2;
+      const double* g = kp_tgt + ((long)b * K + id) * 2;
+      v0 = (float)((g[0] - s[0]) * (double)H); v1 = (float)((g[1] - s[1]) * (double)H);
+      break;
+    }
+    float* o = poke + (long)b * 2 * HW + (long)y * W + x;
+    o[0] = v0; o[HW] = v1;
+  }
+}
+
+extern "C" int ipoke_keypoint_poke(const double* kp_src, const double* kp_tgt, const int32_t* poke_ids, int B, int K, int n_max, int H, int W, int half,
+                                   int h_lo, int h_hi, int w_lo, int w_hi, float* poke, int32_t* coords, void* stream) {
+  IPK_REQUIRE(kp_src && kp_tgt && poke_ids && poke && coords, "null argument");
+  IPK_REQUIRE(B >= 1 && K >= 1 && n_max >= 1 && H >= 1 && W >= 1 && half >= 0, "bad poke configuration");
+  hipLaunchKernelGGL(keypoint_poke_kernel, dim3(grid1((long)B * H * W)), dim3(256), 0, STREAM(stream), kp_src, kp_tgt, poke_ids, B, K, n_max, H, W,
+                     half, h_lo, h_hi, w_lo, w_hi, poke, coords);
+  IPK_LAUNCH_CHECK();
+  return IPOKE_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- clip augmentation
 static int aug_check_size(int S) {
   IPK_REQUIRE(S >= 2 && S % 2 == 0 && S <= 4096, "the frame size must be even and at most 4096 (16.16 fixed point in 32 bits)");

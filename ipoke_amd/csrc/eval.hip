@@ -716,6 +716,29 @@ extern "C" int ipoke_sample_stats(const float* vals, int bs, int ns, int s, floa
   IPK_LAUNCH_CHECK();
   return IPOKE_OK;
 }
+// utils/metrics.py:294, :299 (KPSMetric.update): out[e][j][f] = mean over the K * 2 coordinates of (pred - target)^2, one thread per frame, the
+// terms added in index order in fp32 (each product and each sum rounded on its own); the target is read in place for every sample
+__global__ void kps_frame_mse_kernel(const float* __restrict__ pred, const float* __restrict__ target, long total, int ns, int s, int K2,
+                                     float* __restrict__ out) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long f = i % s, e = i / ((long)ns * s);
+    const float* p = pred + i * K2;
+    const float* t = target + (e * s + f) * K2;
+    float acc = 0.f;
+    for (int k = 0; k < K2; ++k) {
+      const float d = __fsub_rn(p[k], t[k]);
+      acc = __fadd_rn(acc, __fmul_rn(d, d));
+    }
+    out[i] = __fdiv_rn(acc, (float)K2);
+  }
+}
+extern "C" int ipoke_kps_frame_mse(const float* pred, const float* target, int bs, int ns, int s, int K, float* out, void* stream) {
+  IPK_REQUIRE(pred && target && out && bs >= 1 && ns >= 1 && s >= 1 && K >= 1, "bad arguments");
+  const long total = (long)bs * ns * s;
+  hipLaunchKernelGGL(kps_frame_mse_kernel, dim3(grid1(total, 2048)), dim3(256), 0, STREAM(stream), pred, target, total, ns, s, 2 * K, out);
+  IPK_LAUNCH_CHECK();
+  return IPOKE_OK;
+}
 static int pair_mse_blocks(int n_ex, int64_t L) {
   const int64_t tiles = (L + PM_TILE - 1) / PM_TILE;
   int64_t b = 2048 / (n_ex > 0 ? n_ex : 1);

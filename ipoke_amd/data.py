@@ -10,6 +10,9 @@ poke_size, n_pokes, fix_n_pokes, equal_poke_val, scale_poke_to_res) and offers
     stamp(centers, values | flow) squares of given values, or of the flow at the centres, on a zero poke (models/second_stage_video.py
                                   :959-966, testing/gui.py:120-150)
     randomize_pokes(flow, centers, n)  the re-aimed pokes of the control-sensitivity study (models/second_stage_video.py:798-833)
+    draw_keypoint_ids / keypoint_poke  _get_keypoint_poke (:462-497): the poke stamped from the displacement of chosen keypoints
+
+``posture_nearest_neighbours`` is get_nn of data/flow_dataset.py (:628-713), the ``nn_ids`` table a loader stores once per data set;
 
 and ``ClipAugmenter`` the augmentation the shipped training configs switch on (_get_color_transforms / _get_geometric_transforms,
 :695-722: colour jitter on the frames, one reflect-padded affine warp for frames and flow), so that a loader only has to deliver raw flows
@@ -108,6 +111,63 @@ def augment_flow(flow, params):
     out = torch.empty_like(flow)
     check(_lib.lib().ipoke_aug_flow(ptr(flow), ptr(params.affine.to(flow.device)), B, C, S, ptr(out), _lib.current_stream()))
     return out
+
+
+def posture_nearest_neighbours(keypoints, vid, ids=None, return_dist=False):
+    """get_nn of the reference (data/flow_dataset.py:628-713, ``measure`` :635-646) for all queries in one launch pair
+    (``ipoke_posture_nn``): for every query frame the nearest frame in posture space, D(i, j) = sum_k ||kps[i, k] - kps[j, k]||, once over
+    all frames and once over the frames of other videos.
+
+    keypoints: numpy array or tensor [N, K, 2], float32 or float64 (``datadict['keypoints_rel']``), converted to fp32; 1 <= K <= 64.
+    vid: [N], any integer or string array (``datadict['vid']``), mapped to dense int32 codes on the host.  ids: the query frames [M], or
+    None for all N.  Returns ``(nn_general, nn_other_vid)`` as int64 numpy arrays [M] -- ``nn_other_vid`` is what the reference's get_nn
+    returns and its loader stores as ``nn_ids`` -- and with ``return_dist`` also the fp32 distances of the two answers [M, 2].
+
+    Candidates are ordered by (D, j), a stable argsort (the reference's default argsort leaves ties open): ``nn_general`` is the second
+    entry of that order, the query itself included, as ``sorted_ids[1]`` is.  Raises ValueError naming the first query for which no frame
+    of another video exists, where the reference dies with an IndexError."""
+    _lib.require_gpu()
+    kp = keypoints.detach().cpu().numpy() if isinstance(keypoints, torch.Tensor) else np.asarray(keypoints)
+    if kp.ndim != 3 or kp.shape[2] != 2 or kp.dtype not in (np.float32, np.float64):
+        raise ValueError(f"keypoints must be float32 or float64 [N, K, 2], got {kp.dtype} {kp.shape}")
+    N, K = kp.shape[:2]
+    if N < 2 or not 1 <= K <= 64:
+        raise ValueError(f"posture_nearest_neighbours needs N >= 2 frames and 1 <= K <= 64 keypoints, got N = {N}, K = {K}")
+    if not np.isfinite(kp).all():
+        raise ValueError("keypoints hold non-finite values")
+    v = vid.detach().cpu().numpy() if isinstance(vid, torch.Tensor) else np.asarray(vid)
+    if v.shape != (N,) or v.dtype.kind not in "iuUSO":
+        raise ValueError(f"vid must be an integer or string array [{N}], got {v.dtype} {v.shape}")
+    codes = np.unique(v, return_inverse=True)[1].reshape(N).astype(np.int32)
+    if ids is None:
+        q = None
+        M = N
+    else:
+        q = ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
+        if q.ndim != 1 or q.dtype.kind not in "iu" or q.size == 0:
+            raise ValueError(f"ids must be a non-empty integer array [M], got {q.dtype} {q.shape}")
+        q = q.astype(np.int64)
+        bad = np.flatnonzero((q < 0) | (q >= N))
+        if bad.size:
+            raise ValueError(f"ids[{int(bad[0])}] = {int(q[bad[0]])} is outside [0, {N})")
+        M = q.shape[0]
+    dev = torch.device("cuda", torch.cuda.current_device())
+    L = _lib.lib()
+    kp_d = torch.from_numpy(np.ascontiguousarray(kp, dtype=np.float32)).to(dev)
+    vid_d = torch.from_numpy(codes).to(dev)
+    ids_d = None if q is None else torch.from_numpy(q).to(dev)
+    nn_general = torch.empty(M, dtype=torch.int64, device=dev)
+    nn_other = torch.empty(M, dtype=torch.int64, device=dev)
+    dist = torch.empty(M, 2, dtype=torch.float32, device=dev) if return_dist else None
+    ws = torch.empty(max(int(L.ipoke_posture_nn_workspace_bytes(N, K, M)), 64), dtype=torch.uint8, device=dev)
+    check(L.ipoke_posture_nn(ptr(kp_d), ptr(vid_d), ptr(ids_d), N, K, M, ptr(nn_general), ptr(nn_other), ptr(dist), ptr(ws), _lib.current_stream()))
+    nn_general, nn_other = nn_general.cpu().numpy(), nn_other.cpu().numpy()
+    lone = np.flatnonzero(nn_other < 0)
+    if lone.size:
+        m = int(lone[0])
+        frame = m if q is None else int(q[m])
+        raise ValueError(f"query {m} (frame {frame}, video {v[frame].item()!r}): no frame of another video exists")
+    return (nn_general, nn_other, dist.cpu().numpy()) if return_dist else (nn_general, nn_other)
 
 
 class ClipAugmenter:
@@ -315,7 +375,46 @@ class PokeSimulator:
                             f"(status {status[bad].tolist()})")
         return pokes, picked, status
 
-    def make_batch(self, images, raw_flow, zero_poke=None, u=None, generator=None, augment=None, frames_u8=None, mask=None):
+    def draw_keypoint_ids(self, B, K, rng):
+        """The keypoints _get_keypoint_poke pokes (data/base_dataset.py:470-473) for ``B`` samples of ``K`` keypoints from ``rng``, a
+        ``numpy.random.RandomState``: per sample the reference's calls in its order -- ``randint(1, n_pokes, 1)`` unless fix_n_pokes,
+        then ``choice(K, n, replace=False)`` -- so that an ``rng`` seeded like ``np.random`` yields its ids.  int32 [B, n_pokes], -1 padded."""
+        out = np.full((int(B), self.n_pokes), -1, dtype=np.int32)
+        for b in range(int(B)):
+            n = self.n_pokes if self.fix_n_pokes else int(rng.randint(1, self.n_pokes, 1)[0])
+            out[b, :n] = rng.choice(int(K), n, replace=False)
+        return out
+
+    def keypoint_poke(self, kp_src, kp_tgt, poke_ids, device=None):
+        """_get_keypoint_poke (data/base_dataset.py:462-497) for a batch (``ipoke_keypoint_poke``): kp_src, kp_tgt [B, K, 2] as relative
+        (x, y) -- ``keypoints_rel`` of the clip's first and last frame --, numpy arrays or tensors, taken as float64 (the reference
+        truncates double products); poke_ids int [B, n_pokes], -1 padded (``draw_keypoint_ids``).  Returns the reference's triple
+        ``[poke fp32 [B, 2, H, W], poke_coords int32 [B, n_pokes, 2] as (row, col), poke_ids int32 [B, n_pokes]]`` on the device.  Both
+        channels of a poke are (tgt - src) * spatial_size[0], the reference's own asymmetry.  Current stream."""
+        _lib.require_gpu()
+        dev = torch.device(device if device is not None else (kp_src.device if isinstance(kp_src, torch.Tensor) and kp_src.is_cuda else "cuda"))
+        src = torch.as_tensor(kp_src).to(dev, torch.float64).contiguous()
+        tgt = torch.as_tensor(kp_tgt).to(dev, torch.float64).contiguous()
+        if src.dim() != 3 or src.shape[2] != 2 or tgt.shape != src.shape:
+            raise ValueError(f"kp_src and kp_tgt must both be [B, K, 2], got {tuple(src.shape)} and {tuple(tgt.shape)}")
+        B, K, _ = src.shape
+        ids_host = poke_ids.detach().cpu().numpy() if isinstance(poke_ids, torch.Tensor) else np.asarray(poke_ids)
+        if ids_host.ndim != 2 or ids_host.shape[0] != B or ids_host.shape[1] < 1 or ids_host.dtype.kind not in "iu":
+            raise ValueError(f"poke_ids must be an integer array [{B}, n], got {ids_host.dtype} {ids_host.shape}")
+        if (ids_host >= K).any():
+            raise ValueError(f"poke_ids name a keypoint outside [0, {K})")
+        ids = torch.from_numpy(np.where(ids_host < 0, -1, ids_host).astype(np.int32)).to(dev)
+        n_max = ids.shape[1]
+        H, W = self.spatial_size
+        poke = torch.empty(B, 2, H, W, dtype=torch.float32, device=dev)
+        coords = torch.empty(B, n_max, 2, dtype=torch.int32, device=dev)
+        check(_lib.lib().ipoke_keypoint_poke(ptr(src), ptr(tgt), ptr(ids), B, K, n_max, H, W, int(self.poke_size / 2), int(self.valid_h[0]),
+                                             int(self.valid_h[1]), int(self.valid_w[0]), int(self.valid_w[1]), ptr(poke), ptr(coords),
+                                             _lib.current_stream()))
+        return [poke, coords, ids]
+
+    def make_batch(self, images, raw_flow, zero_poke=None, u=None, generator=None, augment=None, frames_u8=None, mask=None, keypoints=None,
+                   keypoint_ids=None, rng=None):
         """The ``batch`` dict the second stage consumes (images, flow, poke = [poke, poke_centers]) from frames already on the device
         and raw flows: the part of BaseDataset.__getitem__ that follows the file reads.  With ``augment`` (the parameters of
         ``ClipAugmenter.draw`` / ``params``) the order is the reference's: _get_flow -> the warp -> _get_poke, so the pokes are taken from
@@ -327,7 +426,12 @@ class PokeSimulator:
         it in the augmented frame, no warp is applied to it.  With None the config decides: ``filter_flow`` with
         ``use_flow_for_weights`` is ``"flow"``; ``filter_flow`` alone raises, since the reference's other source is cv2.grabCut on the
         start frame (_compute_mask, :327-341), which stays with the caller's loader.  Where a mask is in play the batch gains ``"mask"`` (bool [B, H, W]); without one it is the
-        dict it was."""
+        dict it was.
+
+        ``keypoints=(kp_src, kp_tgt)`` adds ``batch["keypoint_poke"]``, the triple of ``keypoint_poke`` (what ``use_keypoint_pokes``
+        reads): ``keypoint_ids`` are the chosen keypoints [B, n_pokes], or None to draw them with ``draw_keypoint_ids`` from ``rng`` (a
+        ``numpy.random.RandomState``; None: a fresh one).  The keypoints are taken as given: the reference applies no warp to them
+        either.  Without the argument the dict is exactly what it was."""
         if mask is None and self.filter_flow:
             if not self.use_flow_for_weights:
                 raise ValueError("filter_flow is on: pass mask= (the reference's grabCut mask of the start frame, base_dataset.py:327-341, is "
@@ -351,4 +455,11 @@ class PokeSimulator:
         batch = {"images": images, "flow": flow_out, "poke": [poke, centers], "poke_status": status}
         if mask is not None:
             batch["mask"] = mask.to(flow.device).bool()
+        if keypoints is not None:
+            kp_src, kp_tgt = keypoints
+            if keypoint_ids is None:
+                keypoint_ids = self.draw_keypoint_ids(len(kp_src), np.shape(kp_src)[1], rng if rng is not None else np.random.RandomState())
+            batch["keypoint_poke"] = self.keypoint_poke(kp_src, kp_tgt, keypoint_ids, device=flow.device)
+        elif keypoint_ids is not None:
+            raise ValueError("keypoint_ids without keypoints=(kp_src, kp_tgt)")
         return batch

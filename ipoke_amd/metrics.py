@@ -4,7 +4,7 @@ the device: one pass for the ranges and the squared error, one separable-Gaussia
 
 The reductions of the test loop (reference utils/metrics.py:60-124, 149-257; second_stage_video.py:665-752) follow below: the per-frame
 SSIM of n samples against one broadcast target, the best-of-n statistics (``SampleSSIM``), the pairwise MSE and VGG time-cosine diversity
-scores and the uint8 video export.  Each is one short launch sequence over the whole batch with a single host read at the very end."""
+scores, the best-of-n keypoint error (``KPSMetric``, metrics.py:259-331) and the uint8 video export.  Each is one short launch sequence over the whole batch with a single host read at the very end."""
 import numpy as np
 import torch
 
@@ -145,6 +145,56 @@ class SampleSSIM:
         if n_pokes is not None:
             data["Number of Pokes"] = np.full_like(data[f"{name} NN"], n_pokes, dtype=int)
         return meanval, data
+
+
+def kps_frame_mse(pred, target):
+    """pred [bs, ns, s, K, 2], target [bs, 1, s, K, 2] -> fp32 [bs, ns, s]: the per-frame mean over the K * 2 coordinates of the squared
+    keypoint error (``KPSMetric.update``, metrics.py:294 and :299).  The target is not replicated."""
+    _lib.require_gpu()
+    if (pred.dim() != 5 or target.dim() != 5 or target.shape[1] != 1 or pred.shape[4] != 2 or tuple(pred.shape[2:]) != tuple(target.shape[2:])
+            or pred.shape[0] != target.shape[0]):
+        raise ValueError(f"expected pred [bs, ns, s, K, 2] and target [bs, 1, s, K, 2], got {tuple(pred.shape)} and {tuple(target.shape)}")
+    p = pred.float().contiguous()
+    t = target.to(p.device).float().contiguous()
+    bs, ns, s, K, _ = p.shape
+    out = torch.empty(bs, ns, s, dtype=torch.float32, device=p.device)
+    check(_lib.lib().ipoke_kps_frame_mse(ptr(p), ptr(t), bs, ns, s, K, ptr(out), _lib.current_stream()))
+    return out
+
+
+class KPSMetric:
+    """``KPSMetric`` of the reference (metrics.py:259-331) on the device kernels: the best-of-n keypoint error per frame, the counterpart of
+    ``SampleSSIM``.  ``update`` takes the keypoints of the caller's own pose estimator, predicted [bs, ns, s, K, 2] and ground truth
+    [bs, 1, s, K, 2]; it keeps the reference's state (nn_err_per_frame, std_per_frame, mean_per_frame, n_samples, nn_err) and its guard
+    ``if self.n_samples < self.n_max_samples``, which compares the number of processed EXAMPLES with ``n_samples`` -- kept as it is.
+    ``compute`` returns the dict of the reference's ``savedir=None`` branch (:313-320); the plot branch (``savedir``) is not built."""
+
+    def __init__(self, n_samples=1000):
+        self.n_max_samples = n_samples
+        self.reset()
+
+    def reset(self):
+        self.nn_err_per_frame, self.std_per_frame, self.mean_per_frame = [], [], []
+        self.n_samples = 0
+        self.nn_err = None
+
+    def update(self, kps_pred, kps_target):
+        if self.n_samples < self.n_max_samples:
+            nn, sd, mean, _ = sample_stats(kps_frame_mse(kps_pred, kps_target))
+            self.nn_err_per_frame.append(nn)
+            self.std_per_frame.append(sd)
+            self.mean_per_frame.append(mean)
+            self.n_samples += kps_pred.size(0)
+            v = nn.mean(1).sum()
+            self.nn_err = v if self.nn_err is None else self.nn_err + v
+
+    def compute(self, n_pokes=0):
+        nn_mse = torch.cat(self.nn_err_per_frame, dim=0).mean(0).cpu().numpy()
+        return {"NN MSE": nn_mse,
+                "Mean MSE per Frame": torch.cat(self.mean_per_frame, dim=0).mean(0).cpu().numpy(),
+                "Std per Frame": torch.cat(self.std_per_frame, dim=0).mean(0).cpu().numpy(),
+                "Time": np.arange(nn_mse.shape[0]),
+                "Number of Pokes": np.full_like(nn_mse, n_pokes, dtype=int)}
 
 
 def _offdiag_mean(D):

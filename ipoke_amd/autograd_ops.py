@@ -55,6 +55,13 @@ def pad_cols(t, ld, dtype):
     return out
 
 
+def _fit_cols(g, ld, dtype):
+    """A gradient [M, any pitch] for an input of pitch ``ld``: ``g`` itself where it fits, else its columns cut or zero padded."""
+    if g.shape[1] == ld and g.dtype == _tdt(dtype):
+        return g
+    return pad_cols(g[:, :min(g.shape[1], ld)], ld, dtype)
+
+
 def _matrix_geometry(w, transposed):
     """(rows, cols, taps) of a conv weight -- a tensor or its shape -- read as the matrix [rows][cols * taps]; ``transposed``: ConvTranspose
     storage [in][out][k]."""
@@ -716,6 +723,7 @@ class _NormFn(torch.autograd.Function):
         ctx.meta = meta
         ctx.save_for_backward(x_t, y, g32, b32, mg_t, stats)
         ctx.has = (gamma is not None, mg_t is not None, res_t is not None)
+        ctx.ld_res = None if res_t is None else res_t.shape[1]
         return y
 
     @staticmethod
@@ -735,10 +743,10 @@ class _NormFn(torch.autograd.Function):
         dres = dmg = dmb = dgamma = dbeta = None
         if has_res and m.get("res_post", False):
             # y = act(pre) + res: the residual's gradient is dy itself, act' comes from the pre-activation value recomputed from x (y is not read)
-            dres = dy
+            dres = _fit_cols(dy, ctx.ld_res, dt)       # (the residual may have another pitch than x, whose pitch dy has)
             d.act_from_pre = 1
         elif has_res:
-            dres = torch.zeros_like(x_t) if x_t.shape[1] > C else torch.empty_like(x_t)
+            dres = (torch.zeros if ctx.ld_res > C else torch.empty)(x_t.shape[0], ctx.ld_res, dtype=x_t.dtype, device=x_t.device)
             d.dres = dres.data_ptr(); d.lddres = dres.shape[1]
         mod_n = int(m.get("mod_samples", 0)) if has_mod else 0
         if has_mod:
@@ -757,7 +765,7 @@ class _NormFn(torch.autograd.Function):
         ws = _workspace(_lib.lib().ipoke_groupnorm_bwd_workspace_floats(N, S, C, G), dy.device, "normbwd")
         d.workspace = ws.data_ptr()
         d.stats = stats.data_ptr()
-        pm = m.get("producer")
+        pm = m.get("producer") if ctx.needs_input_grad[0] else None      # (no gradient for x: the convolution's backward never runs)
         if pm is not None:
             # x is the un-activated output of a frame-batched spectral-norm convolution nobody else reads: dx leaves as dx / sigma_t with
             # the frames' <dx, x - b> and the bias gradient (the convolution's own pass over (dx, x), ipoke_rowscale_bwd, folded in)
@@ -774,15 +782,19 @@ class _NormFn(torch.autograd.Function):
         return dx, dgamma, dbeta, dmg, dmb, dres, None
 
 
-def _rowscale_producer(x, mod):
+def _rowscale_producer(x, mod, dtype, res_post=False):
     """The meta of the convolution that produced ``x`` when the norm's backward may fold its row-scale pass: a frame-batched
     spectral-norm convolution without activation whose dtype output this norm alone reads (c4 37.85 ms against 38.75 with the
-    convolution's own ipoke_rowscale_bwd pass)."""
+    convolution's own ipoke_rowscale_bwd pass).  Declined where ipoke_groupnorm_bwd would refuse the folded form: its apply pass keeps
+    6 C floats (8 C with the residual behind the activation) and the fold's 256 x 16 bytes + 4 floats in the 64 KB of LDS a launch gets --
+    which bites with the residual behind the activation only (C <= 1919 in fp32, 1791 in bf16; without it the limit lies above 2048)."""
     pm = getattr(x, "conv_meta", None)
     if pm is None or mod is not None or pm.get("sn_frames") is None or pm["act"] != _lib.ACT_NONE or pm.get("out_f32", False):
         return None
     frames = int(pm["sn_frames"][0].shape[0])
     if x.N % frames or x.t.shape[1] != x.C or x.C > 2048:
+        return None
+    if 4 * ((8 if res_post else 6) * x.C + 256 * K.e16(dtype) + 4) > 64 * 1024:
         return None
     return pm
 
@@ -791,7 +803,7 @@ def group_norm(x, groups, dtype, gamma=None, beta=None, act=_lib.ACT_NONE, res=N
     """``res_post``: the residual joins behind the activation, y = act(norm(x)) + res."""
     meta = dict(N=x.N, S=x.S, C=x.C, G=groups, dtype=dtype, act=act, res_post=bool(res_post) and res is not None)
     if sole_reader:
-        meta["producer"] = _rowscale_producer(x, mod)
+        meta["producer"] = _rowscale_producer(x, mod, dtype, meta["res_post"])
     if mod is not None and mod[0].N != x.N:       # frames of a clip decoded as one batch ordered (frame, clip): shared SPADE maps
         assert x.N % mod[0].N == 0 and mod[0].S == x.S and mod[0].t.shape[0] == mod[0].N * x.S
         meta["mod_samples"] = mod[0].N
@@ -815,6 +827,7 @@ class _AddActFn(torch.autograd.Function):
                                        ops._dt(dtype), _lib.current_stream()))
         ctx.save_for_backward(y)
         ctx.args = (C, act, dtype)
+        ctx.ld_b = b_t.shape[1]
         return y
 
     @staticmethod
@@ -822,12 +835,12 @@ class _AddActFn(torch.autograd.Function):
         (y,) = ctx.saved_tensors
         C, act, dtype = ctx.args
         if act == _lib.ACT_NONE:
-            return dy, dy, None, None, None
+            return dy, _fit_cols(dy, ctx.ld_b, dtype), None, None, None
         dy = dy.contiguous()
         g = torch.empty_like(y)
         check(_lib.lib().ipoke_act_bwd(ptr(dy), dy.shape[1], ptr(y), y.shape[1], ptr(g), g.shape[1], y.shape[0], C, y.shape[1], act,
                                        ops._dt(dtype), _lib.current_stream()))
-        return g, g, None, None, None
+        return g, _fit_cols(g, ctx.ld_b, dtype), None, None, None
 
 
 def add_act(a, b, dtype, act):

@@ -375,6 +375,20 @@ def cl_to_nchw_ref(x, N, C, S):
     return out
 
 
+# ------------------------------------------------------------------ reparameterisation operands
+def reparam_data(M, Z, exact, tdt, seed):
+    """mu, logvar (values of the dtype), eps, dz, dmu, dlv (fp32 values) as float64; exact: integers with logvar = 0"""
+    gen = torch.Generator().manual_seed(seed)
+    if exact:
+        mu, lv = randint64(-20, 20, (M, Z), gen), torch.zeros((M, Z), dtype=F64)
+        eps, dz, dmu, dlv = (randint64(-8, 8, (M, Z), gen) for _ in range(4))
+        return mu, lv, eps, 2.0 * dz, dmu, dlv               # dz eps / 2 stays an integer
+    r = lambda s: torch.randn((M, Z), generator=gen, dtype=F64) * s      # noqa: E731
+    mu, lv = rnd(r(1.0), tdt), rnd(r(1.5) - 1.0, tdt)
+    eps, dz, dmu, dlv = (rnd(r(1.0), F32) for _ in range(4))
+    return mu, lv, eps, dz, dmu, dlv
+
+
 # ------------------------------------------------------------------ backward cases
 # saved: the (mean, rstd) table of the forward pass is handed over (else stats = NULL: recomputed from x); from_pre: act_from_pre (the forward
 # was act(pre) + res, act' from the recomputed pre-activation, no dres).  dy holds integers in [-4, 4] in every case, so that with ReLU or no
@@ -471,12 +485,12 @@ def frames_summed(c, out):
     return out
 
 
-def fold_ref(c, o, dx):
+def fold_ref(c, o, dx, scales=None):
     """the row-scale fold on a float64 dx [N][S][C]: (dx / sigma_t per frame, rs_dots [frames] = sum dx (x - b), rs_dbias [C] = sum dx)
-    and the magnitudes of the two sums' terms"""
+    and the magnitudes of the two sums' terms.  scales: the frames' 1 / sigma_t where they are not RS_SCALES (tests/ops_exact.py)"""
     clips, stride, with_bias, _ = c.rs
     frames = c.N // clips
-    sc = torch.tensor(RS_SCALES[:frames], dtype=F64).repeat_interleave(clips).view(c.N, 1, 1)
+    sc = torch.tensor(RS_SCALES[:frames] if scales is None else list(scales), dtype=F64).repeat_interleave(clips).view(c.N, 1, 1)
     xb = o["x"] - (o["rs_bias"] if with_bias else 0.0)
     xm = o["x"].abs() + (o["rs_bias"].abs() if with_bias else 0.0)
     per = lambda t: t.view(frames, clips * c.S * c.C).sum(dim=1)      # noqa: E731

@@ -244,17 +244,7 @@ def test_bilinear_bit_exact(name, shape):
 
 
 # ------------------------------------------------------------------ reparameterisation
-def reparam_data(M, Z, exact, tdt, seed):
-    gen = torch.Generator().manual_seed(seed)
-    if exact:
-        mu, lv = X.randint64(-20, 20, (M, Z), gen), torch.zeros((M, Z), dtype=F64)
-        eps, dz, dmu, dlv = (X.randint64(-8, 8, (M, Z), gen) for _ in range(4))
-        dz = 2.0 * dz                                     # dz eps / 2 stays an integer
-    else:
-        r = lambda s: torch.randn((M, Z), generator=gen, dtype=F64) * s      # noqa: E731
-        mu, lv = X.rnd(r(1.0), tdt), X.rnd(r(1.5) - 1.0, tdt)
-        eps, dz, dmu, dlv = (X.rnd(r(1.0), F32) for _ in range(4))
-    return mu, lv, eps, dz, dmu, dlv
+reparam_data = X.reparam_data
 
 
 @BOTH

@@ -871,6 +871,42 @@ int ipoke_l1_nll(const float* pre_cl, int ld, int act, const float* x_nchw, int 
                  const float* p, const float* perc_weight, float* out, float* rec_cl, int ld_rec, float* grad_pre, int ld_grad,
                  float* grad_p, double* partials, void* stream);
 
+/* Adversarial phase of the image autoencoder (csrc/image_gan.hip; first_stage_image_conv.py:85-168 with the PatchGAN of
+ * patchgan.py:255-325).  Outputs and partials are caller-owned; every sum runs in double in a fixed order (no float atomics, no host
+ * synchronisation: a second run gives the same bits); bad arguments are refused before any launch.
+ *
+ * ipoke_hinge_terms replaces patchgan.py:304-314 (`loss`), first_stage_image_conv.py:122 (`-torch.mean(pred_fake)`) and the
+ * `torch.sigmoid(pred).mean()` of :114 on an fp32 prediction column pred[m * ld], m < M:
+ *   out[0] = mean relu(1 - pred) (IPOKE_HINGE_REAL) | mean relu(1 + pred) (IPOKE_HINGE_FAKE) | -mean pred (IPOKE_HINGE_GENERATOR)
+ *   out[1] = mean sigmoid(pred)
+ *   grad[m * ldg] = d out[0] / d pred[m]: -1/M (real) or +1/M (fake) where 1 -+ pred > 0 and exactly 0 elsewhere (relu'(0) = 0);
+ *                   -1/M everywhere for the generator term.
+ * partials: ipoke_hinge_terms_partials() doubles. */
+enum { IPOKE_HINGE_REAL = 0, IPOKE_HINGE_FAKE = 1, IPOKE_HINGE_GENERATOR = 2 };
+long ipoke_hinge_terms_partials(void);
+int ipoke_hinge_terms(const float* pred, int ld, int64_t M, int mode, float* out, float* grad, int ldg, double* partials, void* stream);
+/* ydot[:, :C] = act'(y) * xdot from the primal OUTPUT y, ydot[:, C:Cpad] = 0: the tangent of the LeakyReLU(0.2) fused into the
+ * discriminator's first convolution (patchgan.py:275), the one activation with no GroupNorm in front of it; its own adjoint in xdot.
+ * Channels-last rows of the compute dtype; act: IPOKE_ACT_LRELU02 or IPOKE_ACT_RELU, the slope at y == 0 is that of y < 0 (0.2 / 0), as
+ * in common.h and torch.  The product is formed in double and rounded once. */
+int ipoke_act_jvp(const void* y, int ldy, const void* xdot, int ldx, void* ydot, int ldo, int64_t M, int C, int Cpad, int act, int dtype,
+                  void* stream);
+/* Gradient penalty (patchgan.py:316-325 `gp` and the `.mean()` of first_stage_image_conv.py:99) from g = d sum(pred) / d x, fp32 [N][L]
+ * dense: out[0] = mean_n sum_l g^2 (the penalty), out[1 + n] = sum_l g[n]^2, v = (2 / N) g (the direction of the tangent pass that
+ * replaces the double backward).  partials: ipoke_gp_direction_partials(N) doubles. */
+long ipoke_gp_direction_partials(int N);
+int ipoke_gp_direction(const float* g, int N, int64_t L, float* v, float* out, double* partials, void* stream);
+/* ipoke_groupnorm_jvp / _bwd (above) with every sum in a fixed order, for a step that has to be reproducible bit for bit: the group
+ * sums are ordered double sums instead of float atomics, the element-wise pass runs in double, and the gamma gradient leaves as one
+ * row per sample, dgamma_rows [N][C] (may be NULL), for the caller to add in sample order (ipoke_reduce_rows).  No residual tangent.
+ * One workgroup per (sample, group): C % G == 0 and 256 % (C / G) == 0; columns >= C are not written; y counts only with an
+ * activation (none, ReLU, LeakyReLU(0.2)). */
+int ipoke_groupnorm_tangent(const void* x, int ldx, const void* xdot, int ldxd, const void* y, int ldy, void* ydot, int ldyd,
+                            const float* gamma, int N, int S, int C, int G, int act, float eps, int dtype, void* stream);
+int ipoke_groupnorm_tangent_bwd(const void* x, int ldx, const void* xdot, int ldxd, const void* y, int ldy, const void* q, int ldq,
+                                void* dxdot, int lddxd, void* dx, int lddx, float* dgamma_rows, const float* gamma, int N, int S, int C,
+                                int G, int act, float eps, int dtype, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * FVD evaluation (reference utils/metrics.py; host side in ipoke_amd/fvd.py).  The I3D convolutions are ipoke_conv_forward
  * with the eval-mode BatchNorm folded into weight and bias; these are the element-wise / window kernels around them.

@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("IPOKE_LIB_PATH") or os.path.join(_HERE, "libipoke_hip
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_ELU, ACT_RELU, ACT_LRELU02, ACT_TANH, ACT_SIGMOID = range(6)
+HINGE_REAL, HINGE_FAKE, HINGE_GENERATOR = range(3)         # ipoke_hinge_terms
 # ipoke_groupnorm_path: IPOKE_NORM_PATH_* bits, the slab width above NORM_PATH_CS_SHIFT
 NORM_PATH_ONE_LAUNCH, NORM_PATH_LARGE, NORM_PATH_PART, NORM_PATH_NEXT_APPLY, NORM_PATH_NEXT_PASS, NORM_PATH_CS_SHIFT = 1, 2, 4, 8, 16, 16
 
@@ -266,6 +267,14 @@ SIGNATURES = {
     "ipoke_l1_loss_partials": (ctypes.c_long, []),
     "ipoke_l1_nll": (c_int, [_P, c_int, c_int, _P, c_int, c_int, c_int, c_int64, _P, _P, _P, _P, _P, c_int, _P, c_int, _P, _P, _P]),
     "ipoke_l1_nll_partials": (ctypes.c_long, []),
+    "ipoke_hinge_terms_partials": (ctypes.c_long, []),
+    "ipoke_hinge_terms": (c_int, [_P, c_int, c_int64, c_int, _P, _P, c_int, _P, _P]),
+    "ipoke_act_jvp": (c_int, [_P, c_int, _P, c_int, _P, c_int, c_int64, c_int, c_int, c_int, c_int, _P]),
+    "ipoke_gp_direction_partials": (ctypes.c_long, [c_int]),
+    "ipoke_gp_direction": (c_int, [_P, c_int, c_int64, _P, _P, _P, _P]),
+    "ipoke_groupnorm_tangent": (c_int, [_P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P]),
+    "ipoke_groupnorm_tangent_bwd": (c_int, [_P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, _P, c_int, c_int, c_int,
+                                            c_int, c_int, c_float, c_int, _P]),
     "ipoke_relayout_multi_range": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, _P]),
     "ipoke_wn_scale_multi_range": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "ipoke_flow_prepare_weights_range": (c_int, [_P, _P, _P, c_int64, c_int64, _P]),

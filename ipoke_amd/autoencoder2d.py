@@ -7,8 +7,14 @@ The parameter holders are the blocks of ``ipoke_amd.first_stage`` (reference sta
 here: the decoder, the autoencoder modules, the loss with a device-resident log-variance (``ipoke_l1_nll``, csrc/ae2d_loss.hip),
 the two trainers and the plateau scheduler.
 
-What is NOT built: the LPIPS perceptual term -- ``perceptual`` is a hook, ``None`` leaves the term out -- and
-the image autoencoder's adversarial phase (PatchGAN ``define_D`` with gradient penalty and the adaptive weight), which raises.
+The image autoencoder's adversarial phase (epochs from ``training.pretrain`` on: PatchGAN ``define_D`` with gradient penalty and the
+adaptive weight) lives in ``ipoke_amd.image_gan`` behind its own names, ``ConvAEGANModel`` and ``ImageEncoderGANTrainer``;
+``ConvAEModel.training_loss`` here keeps refusing those epochs, and ``ImageEncoderTrainer`` stays the reconstruction phase.  Two quirks of
+the reference that the new trainer keeps and states: both plateau schedulers act on the generator's optimiser (factor .5, then .1), and
+Lightning's repetition of ``training_step`` per optimiser is not reproduced.
+
+What is NOT built: the LPIPS perceptual term -- ``perceptual`` is a hook, ``None`` leaves the term out --, FID
+validation, ``bce_loss``, ``PatchDiscriminator.gp`` and multi-GPU training of these two models.
 """
 import numpy as np
 import torch

@@ -89,8 +89,9 @@ def poke_encoder_train_config(spatial_size=128, flow_ae=True, poke_and_image=Fal
 
 
 def img_encoder_train_config(spatial_size=64):
-    """img_encoder.yaml restated: the keys ``autoencoder2d.ConvAEModel`` and ``ImageEncoderTrainer`` consume.  ``pretrain``: the first
-    epoch of the adversarial phase, which is not built (the model raises there)."""
+    """img_encoder.yaml restated: the keys ``autoencoder2d.ConvAEModel`` / ``ImageEncoderTrainer`` and ``image_gan.ConvAEGANModel`` /
+    ``ImageEncoderGANTrainer`` consume.  ``pretrain``: the first epoch of the adversarial phase (18 of the 20 epochs), which the
+    ``image_gan`` pair trains with ``gp_weight`` on the discriminator's penalty; ``ConvAEModel`` alone raises there."""
     conf = encoder2d_config(spatial_size, 3)
     conf["data"].update(batch_size=128, max_frames=1, n_pokes=1)
     conf["training"] = {"lr": 2e-4, "weight_decay": 0, "n_epochs": 20, "max_val_batches": 200, "pretrain": 2, "w_kl": 1e-6,

@@ -38,6 +38,16 @@ struct PokeArgs {
   const uint8_t* mask; float* amp_filt;                        // the masked instantiation only
 };
 
+// |(vx, vy)| as torch.norm(flow, 2, dim=0) forms it in fp32: the two squares, their sum and the root each rounded on its own.  Plain operators
+// with contraction switched off (the __f*_rn intrinsics may be fused, see the augmentation code below) and sqrtf, which hipcc rounds correctly
+// by default: __fsqrt_rn is the hardware's approximate root here, one ulp off for a share of its arguments.
+__device__ __forceinline__ float flow_amplitude(float vx, float vy) {
+#pragma clang fp contract(off)
+  const float xx = vx * vx, yy = vy * vy;
+  const float ss = xx + yy;
+  return sqrtf(ss);
+}
+
 __device__ __forceinline__ double block_sum_d(double v, double* red) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -136,7 +146,7 @@ __global__ __launch_bounds__(kPokeThreads) void poke_select_kernel(PokeArgs p) {
   for (int i = tid; i < n; i += blockDim.x) {
     const int y = h0 + i / ww, x = w0 + i % ww;
     const float vx = fx[y * p.W + x], vy = fy[y * p.W + x];
-    const float v = __fsqrt_rn(__fadd_rn(__fmul_rn(vx, vx), __fmul_rn(vy, vy)));
+    const float v = flow_amplitude(vx, vy);
     a[i] = v; lo = fminf(lo, v);
   }
   lo = block_minmax(lo, false, red_f);
@@ -242,7 +252,7 @@ __global__ __launch_bounds__(kPokeThreads) void flow_mask_kernel(const float* __
   float lo = INFINITY;
   for (int i = tid; i < n; i += blockDim.x) {
     const float vx = fx[i], vy = fy[i];
-    const float v = __fsqrt_rn(__fadd_rn(__fmul_rn(vx, vx), __fmul_rn(vy, vy)));
+    const float v = flow_amplitude(vx, vy);
     a[i] = v; lo = fminf(lo, v);
   }
   lo = block_minmax(lo, false, red_f);
@@ -549,7 +559,7 @@ __global__ __launch_bounds__(kPokeThreads) void poke_randomize_select_kernel(Ran
   double s = 0.0;
   for (int i = tid; i < n; i += blockDim.x) {
     const float vx = fx[i], vy = fy[i];
-    const float v = __fsqrt_rn(__fadd_rn(__fmul_rn(vx, vx), __fmul_rn(vy, vy)));
+    const float v = flow_amplitude(vx, vy);
     a[i] = v; s += (double)v;
   }
   const double mean_d = block_sum_d(s, red_d) / (double)n;
